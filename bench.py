@@ -33,7 +33,10 @@ has touched the GPU is never re-executed.  Rank 0 relays the first successful li
 sharded evaluation sweeps and one sharded improvement sweep are compared bit for bit with the unsharded
 sweeps of the same state (`check.exchange.bit_identical`); a mismatch fails the rung.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), plus
+Prints ONE JSON line on rank 0: the headline (`value` over the timed steps, `ms_per_step`, the per-sweep times of
+those steps from HIP events on the launch stream, the residual and change count of the last one).  A plain run on one
+GPU does nothing else; `--dump-outputs DIR` writes what its last timed step computed (dump_outputs).  `--full` adds, outside
+the timed region,
   roofline      — dominant kernel of the step (pi_eval_sweep_kernel in every BASELINE config; pi_eval_live_kernel,
                   the same sweep over the listed non-terminal states, on the double cartpole grid).  The headline
                   fraction is the one the north star names: HBM-side bytes per launch — rocprofv3 FETCH_SIZE x 2.0 +
@@ -60,7 +63,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement), plus
                     hbm   the headline unit again.
                   Everything that comes from the profile is withheld (null) when no committed profile
                   matches the config and the kernel version.
-  extra_configs — N = 1, default command: the other single-GPU BASELINE configs (C2 pendulum 200^2, C3 cartpole swing-up
+  extra_configs — N = 1, default config: the other single-GPU BASELINE configs (C2 pendulum 200^2, C3 cartpole swing-up
                   50^4, C5 double cartpole 25^6 and its 9-action swing-up variant) timed the same way after the headline —
                   10 evaluation + 1 improvement sweeps per step from a synthetic resident state — each with its per-sweep
                   times, whole-step throughput and roofline fractions; a compact copy sits in `roofline.extra_configs`.
@@ -349,7 +352,7 @@ def load_profile(env: str, bins: int, n_states: int, kernel_hash: str, label: st
     return None, None
 
 
-# The other single-GPU BASELINE configs, timed by the same default command after the headline (N = 1 only):
+# The other single-GPU BASELINE configs, timed by a --full run after the headline (N = 1 only):
 # (label, env, bins, timed steps, warm-up steps).  One step = 10 evaluation sweeps + 1 improvement sweep, as the headline's.
 EXTRA_CONFIGS = [
     ("c2", "pendulum", 200, 200, 20),
@@ -461,7 +464,7 @@ def measure_extra_config(label: str, env: str, bins: int, steps: int, warmup: in
     return out
 
 
-# Runs to convergence (the metric's "sweeps-to-converge" half) the default command makes after the timed region, in this
+# Runs to convergence (the metric's "sweeps-to-converge" half) a --full run makes after the timed region, in this
 # order, each only if its estimated wall seconds still fit --time-budget: (label, env, bins, estimated seconds on one MI355X).
 # What every run must reproduce — policy-iteration rounds, evaluation sweeps, sha256[:16] of the bytes of V and of the policy
 # (host side, the env's own order) — has been the same since round 2 (profiles/r05/full_runs.txt): results are a property of
@@ -506,6 +509,30 @@ def run_to_convergence(label: str, env: str, bins: int, dev) -> dict:
     del fresh
     torch.cuda.empty_cache()
     return out
+
+
+DUMP_SAMPLES = 1 << 21
+
+
+def dump_outputs(solver, out_dir: str, residual: float, changed: int) -> None:
+    """--dump-outputs: what the timed path hands its caller after the last timed step, as .npy files in `out_dir` — V and
+    the policy in the env's own order (the host arrays run() returns), the residual of the last evaluation sweep and the
+    number of policy entries the improvement sweep changed.  Grids of more than DUMP_SAMPLES states are sampled at a fixed,
+    seeded set of flat indices (`state_index`), so that two builds can be compared array for array (32 MB at most)."""
+    n = solver.n_states
+    V = solver._to_user(solver.d_value_function[:n].cpu().numpy())
+    P = solver._to_user(solver.d_policy[:n].cpu().numpy())
+    idx = (np.arange(n) if n <= DUMP_SAMPLES
+           else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLES, replace=False)))
+    arrays = {"value_function": V[idx].astype(np.float32),
+              "policy": P[idx].astype(np.float32),              # action indices: exact in float32
+              "state_index": idx.astype(np.float64),
+              "residual": np.array([residual], dtype=np.float64),
+              "changed": np.array([changed], dtype=np.float64)}
+    path = Path(out_dir)
+    path.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(path / f"{name}.npy", a)
 
 
 def launch_command(n_gpus: int, argv: list[str], port: int | None = None) -> list[str]:
@@ -831,6 +858,13 @@ def main() -> None:
     ap.add_argument("--env", default=ENV, help="env plugin (default: the BASELINE metric config, "
                     "double_pendulum_swingup at 80 bins; other BASELINE configs: cartpole_swingup@50, "
                     "double_cartpole@25, double_cartpole_swingup@25, pendulum@200)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: the policy-iteration-state sweep, "
+                         "the other BASELINE configs, runs to convergence with their digests, the CPU baseline, per-kernel "
+                         "and roofline figures.  The --no-* options, --full-run, --cpu-sample and --time-budget shape "
+                         "that part and do nothing without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-converged-state", action="store_true",
                     help="skip the policy-iteration-state measurement (3 outer iterations, ~4 s)")
@@ -849,7 +883,7 @@ def main() -> None:
                     help="N = 1, default config only: skip the other single-GPU BASELINE configs (C2, C3, C5, C5 swing-up) "
                          "that are timed after the headline and reported under `extra_configs`")
     ap.add_argument("--time-budget", type=float, default=420.0,
-                    help="wall seconds the whole default run may take: optional parts that would not fit are skipped — the "
+                    help="wall seconds a whole --full run may take: optional parts that would not fit are skipped — the "
                          "run to convergence first, then extra configs — and say so in the line")
     ap.add_argument("--launch-dry-run", action="store_true",
                     help="with --gpus N > 1 outside torch.distributed.run: print the child command that "
@@ -969,151 +1003,22 @@ def main() -> None:
             dist.barrier()
             sys.exit(3)
 
+    if args.dump_outputs:
+        if world > 1:                     # a rank's V is current only where it sweeps and reads, its policy in its shard
+            solver._comm.all_gather(solver, solver.d_value_function)
+            solver._comm.all_gather(solver, solver.d_policy)
+        if rank == 0:
+            dump_outputs(solver, args.dump_outputs, last_delta, last_changed)
+
     eval_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev])) / EVAL_PER_STEP
     improve_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev])) / IMPROVE_PER_STEP
-
-    # Grids with many terminal states: the library listed the live states (pi_prepare_mask) and the later
-    # sweeps of a batch / the improvement sweeps run pi_eval_live_kernel / pi_improve_live_kernel over them.
-    # Their own launch time: (a 21-sweep batch - a 1-sweep batch) / 20, outside the timed region.
-    live_states = eng.info(16) if world == 1 else 0
-    first_ms = live_ms = None
-    if live_states > 0:
-        def batch_ms(k):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            solver._evaluation_sweeps(k, gamma)
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1)
-        batch_ms(2)
-        first_ms = min(batch_ms(1) for _ in range(3))
-        live_ms = (min(batch_ms(21) for _ in range(2)) - first_ms) / 20.0
     backups_per_step = n * (EVAL_PER_STEP + IMPROVE_PER_STEP * nA)
     value = backups_per_step * args.steps / elapsed
     # terminal states are COUNTED in `value` ("count terminal states too if simpler, but say which"); they do
     # no work, so the figure over the states a sweep really backs up stands beside it
     value_nonterminal = n_live * (EVAL_PER_STEP + IMPROVE_PER_STEP * nA) * args.steps / elapsed
     states_per_launch = solver._s_end - solver._s_begin
-    live_per_launch = (states_per_launch - int(solver.d_terminal_mask[solver._s_begin:solver._s_end].sum().item()))
-
-    # ── the evaluation sweep on a policy-iteration state (what a real run() sweeps) ──────────
-    converged = None
-    if world == 1 and not args.no_converged_state:
-        solver.d_value_function.zero_()
-        solver.d_new_value_function.zero_()
-        solver.d_policy.zero_()
-        keep = solver.config.max_eval_iter
-        solver.config.max_eval_iter = 2000
-        t_prep = time.perf_counter()
-        for _ in range(3):
-            solver.policy_evaluation()
-            solver.policy_improvement()
-        solver.config.max_eval_iter = keep
-        torch.cuda.synchronize()
-        t_prep = time.perf_counter() - t_prep
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        solver._evaluation_sweeps(10, gamma)
-        e0.record()
-        solver._evaluation_sweeps(50, gamma)
-        e1.record()
-        e1.synchronize()
-        converged = {"ms": e0.elapsed_time(e1) / 50, "state": "3 policy-iteration rounds from V = 0, "
-                     "policy = 0 with at most 2000 evaluation sweeps each", "prepare_seconds": t_prep,
-                     "residual": float(solver._d_delta.item())}
-
-    # ── the other single-GPU BASELINE configs on the same clock (N = 1, default config only) ──────────────
-    khash = _native.kernel_source_hash()
-    t_start = T_PROCESS_START
-    extra_configs, extra_skipped = [], []
-    cpu_cost = 0.0 if args.no_cpu_baseline else 25.0
-    if world == 1 and not args.no_extra_configs and (args.env, args.bins) == (ENV, BINS):
-        # the headline's device arrays are not needed while the extras run (25^6 wants ~4 GB): keep them, 288 GB is plenty
-        for label, x_env, x_bins, x_steps, x_warm in EXTRA_CONFIGS:
-            spent = time.perf_counter() - t_start
-            if spent + EXTRA_COST_S[label] + cpu_cost > args.time_budget:
-                extra_skipped.append({"label": label, "reason": f"time budget: {spent:.0f} s spent of {args.time_budget:.0f}"})
-                continue
-            try:
-                extra_configs.append(measure_extra_config(label, x_env, x_bins, x_steps, x_warm, dev, khash))
-            except Exception as exc:                  # never lose the headline over an extra
-                extra_skipped.append({"label": label, "reason": repr(exc)})
-
-    # ── sweeps-to-converge: full run()s from the envs' initial states with their own settings (N = 1, outside the timed
-    # region).  Default config: C3 -> C4 (the headline, `sweeps_to_converge`) -> C5, each only while its estimate fits the
-    # time budget; another --env / --bins: that config alone.  Digests of V and the policy are compared with the committed ones.
-    full_run = None
-    full_runs, full_runs_skipped = {}, []
-    if world == 1 and not args.no_full_run:
-        default_cfg = (args.env, args.bins) == (ENV, BINS)
-        plan = FULL_RUNS if default_cfg else [("this", args.env, args.bins, 0.0)]
-        for label, r_env, r_bins, est in plan:
-            spent = time.perf_counter() - t_start
-            if not default_cfg and n >= (1 << 27) and not args.full_run:
-                full_runs_skipped.append({"label": label, "reason": f"{n} states: a run to convergence takes minutes; pass --full-run"})
-                continue
-            if not args.full_run and spent + est + cpu_cost > args.time_budget:
-                full_runs_skipped.append({"label": label, "reason": f"time budget: {spent:.0f} s spent of {args.time_budget:.0f}, "
-                                                                    f"this run needs ~{est:.0f} s; pass --full-run "
-                                                                    f"(profiles/r05/full_runs.txt holds the measured runs)"})
-                continue
-            try:
-                full_runs[label] = run_to_convergence(label, r_env, r_bins, dev)
-            except Exception as exc:                  # never lose the timed result over an extra run
-                full_runs[label] = {"error": repr(exc)}
-        key = "c4" if default_cfg else "this"
-        full_run = full_runs.get(key) or next(({"skipped": x["reason"]} for x in full_runs_skipped if x["label"] == key), None)
-        for x in extra_configs:                       # C3 / C5: beside their sweep timings as well
-            if x["label"] in full_runs and "full_run" not in x:
-                x["full_run"] = full_runs[x["label"]]
-
-    # ── roofline ──────────────────────────────────────────────────────────────────────────
-    prof, prof_path = (None, None) if minimal else load_profile(args.env, args.bins, n, khash, order=eng.order)
-    # N > 1: the committed profile is the single-GPU launch of the same kernel; per-wave figures carry over, the number
-    # of waves (and every per-launch total) scales with this rank's share of the states
-    prof_scale = states_per_launch / float(n)
-    bytes_eval = algorithmic_bytes_eval(D)
-    bytes_improve = 4 * (1 << D) + (4 * D + 1 + 4) / nA
-    # cache-perfect HBM bytes of one evaluation sweep: every V value read once (4) + V' written (4) + the policy entry (4),
-    # + the mask byte on grids that have terminal states (the old-value stream is read on residual sweeps only, 1 in 25)
-    compulsory_per_state = 12.0 if solver._mask_arg() is None else 13.0
-    compulsory = compulsory_per_state * states_per_launch
-
-    def kernel_entry(name, ms, backups, alg_bytes_per_backup, counters=None):
-        return kernel_units(name, ms, backups, alg_bytes_per_backup, prof=prof, prof_scale=prof_scale, n=n, n_live=n_live,
-                            live_per_launch=live_per_launch, states_per_launch=states_per_launch, counters=counters)
-
-    if live_states > 0:
-        kernels = {
-            "eval_sweep": kernel_entry("pi_eval_live_kernel", live_ms, states_per_launch, bytes_eval),
-            "eval_sweep_first_of_batch": kernel_entry("pi_eval_sweep_kernel", first_ms, states_per_launch, bytes_eval),
-            "improve_sweep": kernel_entry("pi_improve_live_kernel", improve_ms, states_per_launch * nA, bytes_improve),
-        }
-        kernels["eval_sweep"]["live_states"] = live_states
-        kernels["eval_sweep"]["batch_average_ms"] = eval_ms
-    else:
-        kernels = {
-            "eval_sweep": kernel_entry("pi_eval_sweep_kernel", eval_ms, states_per_launch, bytes_eval),
-            "improve_sweep": kernel_entry("pi_improve_sweep_kernel", improve_ms, states_per_launch * nA, bytes_improve),
-        }
-    if converged:
-        # the same units for the policy-iteration state, from ITS committed counters
-        rprof, rpath = load_profile(args.env, args.bins, n, khash, "real", order=eng.order)
-        if rprof:
-            conv = kernel_entry("pi_eval_sweep_kernel", converged["ms"], states_per_launch, bytes_eval,
-                                counters=rprof.get("kernels", {}))
-            converged["profile"] = rpath
-            converged["units"] = conv.get("units")
-        kernels["eval_converged_policy"] = converged
     share = {"eval_sweeps": eval_ms * EVAL_PER_STEP, "improve_sweep": improve_ms * IMPROVE_PER_STEP}
-    dom = kernels["eval_sweep"] if share["eval_sweeps"] >= share["improve_sweep"] else kernels["improve_sweep"]
-    roofline = build_roofline(dom, khash, prof_path, compulsory_per_state, compulsory, None if world == 1 else prof_scale)
-    alg_gbps = dom["algorithmic"]["achieved_GBps"]
-    roofline_algorithmic = {"bound": "hbm", "kernel": dom["kernel"], "achieved": alg_gbps, "peak": HBM_PEAK_GBS,
-                            "unit": "GB/s", "frac": None, "ratio_to_hbm_peak": alg_gbps / HBM_PEAK_GBS,
-                            "bytes_per_backup": dom["algorithmic"]["bytes_per_backup"],
-                            "note": "SURVEY 8(d)'s algorithmic bytes over the launch time: above the HBM peak because the 2^D "
-                                    "corner reads are L1 / L2 / Infinity-Cache hits; not a bound, no fraction is claimed "
-                                    "against it — the measured HBM-side fraction is roofline.frac"}
 
     exchange = None
     if solver._comm is not None and getattr(solver._comm, "info", None) and minimal:
@@ -1169,15 +1074,7 @@ def main() -> None:
                    "parallelism": f"state-range shards x{world}" + (
                        f", {exchange['mode']} exchange of V' per eval sweep over {'peer-to-peer stores' if exchange.get('transport') == 'p2p' else 'RCCL'} inside libpi_mi355"
                        if exchange else "")},
-        "roofline": roofline,
-        "roofline_algorithmic": roofline_algorithmic,
-        "kernels": kernels,
         "time_share_ms": share,
-        "sweeps_to_converge": full_run,
-        "full_runs": full_runs,
-        "full_runs_skipped": full_runs_skipped,
-        "extra_configs": extra_configs,
-        "extra_configs_skipped": extra_skipped,
         "eval_backups_per_s": states_per_launch * world / (eval_ms * 1e-3),
         "improve_backups_per_s": states_per_launch * world * nA / (improve_ms * 1e-3),
         "check": {"last_residual": last_delta, "last_changed": last_changed,
@@ -1190,18 +1087,159 @@ def main() -> None:
                                            "host-side arrays and all arithmetic stay in the env's own order"},
                   "exchange": exchange},
     }
-    if extra_configs:
-        out["roofline"]["extra_configs"] = {
-            x["label"]: {"env": x["env"], "bins": x["bins"], "eval_ms": round(x["eval_ms"], 5), "improve_ms": round(x["improve_ms"], 5),
-                         "backups_per_s": float(f"{x['backups_per_s']:.4g}"), "frac_hbm": x["roofline"]["frac_hbm"],
-                         "hbm_frac_raw": x["roofline"]["hbm_frac_raw"], "valu_frac": x["roofline"]["valu_frac"],
-                         "l1_load_issue_frac": x["roofline"]["l1_load_issue_frac"],
-                         "frac_hbm_compulsory": x["roofline"].get("frac_hbm_compulsory"),
-                         "traffic_vs_compulsory": x["roofline"].get("traffic_vs_compulsory"),
-                         "floor": x["roofline"].get("floor"), "frac_of_floor": x["roofline"].get("frac_of_floor")}
-            for x in extra_configs}
-    if rank == 0 and not args.no_cpu_baseline and not minimal and os.environ.get("PI_BENCH_BONUS") != "1":   # rank 0's host cores; the other ranks wait at the barrier below
-        out["cpu_baseline"] = cpu_baseline(args.env, args.bins, args.cpu_sample)
+
+    # ── --full: everything beyond the headline, outside the timed region ──────────────────────
+    extra_configs, extra_skipped = [], []
+    full_runs, full_runs_skipped = {}, []
+    if args.full:
+        # Grids with many terminal states: the library listed the live states (pi_prepare_mask) and the later
+        # sweeps of a batch / the improvement sweeps run pi_eval_live_kernel / pi_improve_live_kernel over them.
+        # Their own launch time: (a 21-sweep batch - a 1-sweep batch) / 20, outside the timed region.
+        live_states = eng.info(16) if world == 1 else 0
+        first_ms = live_ms = None
+        if live_states > 0:
+            def batch_ms(k):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                solver._evaluation_sweeps(k, gamma)
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1)
+            batch_ms(2)
+            first_ms = min(batch_ms(1) for _ in range(3))
+            live_ms = (min(batch_ms(21) for _ in range(2)) - first_ms) / 20.0
+        live_per_launch = (states_per_launch - int(solver.d_terminal_mask[solver._s_begin:solver._s_end].sum().item()))
+
+        # ── the evaluation sweep on a policy-iteration state (what a real run() sweeps) ──────────
+        converged = None
+        if world == 1 and not args.no_converged_state:
+            solver.d_value_function.zero_()
+            solver.d_new_value_function.zero_()
+            solver.d_policy.zero_()
+            keep = solver.config.max_eval_iter
+            solver.config.max_eval_iter = 2000
+            t_prep = time.perf_counter()
+            for _ in range(3):
+                solver.policy_evaluation()
+                solver.policy_improvement()
+            solver.config.max_eval_iter = keep
+            torch.cuda.synchronize()
+            t_prep = time.perf_counter() - t_prep
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            solver._evaluation_sweeps(10, gamma)
+            e0.record()
+            solver._evaluation_sweeps(50, gamma)
+            e1.record()
+            e1.synchronize()
+            converged = {"ms": e0.elapsed_time(e1) / 50, "state": "3 policy-iteration rounds from V = 0, "
+                         "policy = 0 with at most 2000 evaluation sweeps each", "prepare_seconds": t_prep,
+                         "residual": float(solver._d_delta.item())}
+
+        # ── the other single-GPU BASELINE configs on the same clock (N = 1, default config only) ──────────────
+        khash = _native.kernel_source_hash()
+        t_start = T_PROCESS_START
+        cpu_cost = 0.0 if args.no_cpu_baseline else 25.0
+        if world == 1 and not args.no_extra_configs and (args.env, args.bins) == (ENV, BINS):
+            # the headline's device arrays are not needed while the extras run (25^6 wants ~4 GB): keep them, 288 GB is plenty
+            for label, x_env, x_bins, x_steps, x_warm in EXTRA_CONFIGS:
+                spent = time.perf_counter() - t_start
+                if spent + EXTRA_COST_S[label] + cpu_cost > args.time_budget:
+                    extra_skipped.append({"label": label, "reason": f"time budget: {spent:.0f} s spent of {args.time_budget:.0f}"})
+                    continue
+                try:
+                    extra_configs.append(measure_extra_config(label, x_env, x_bins, x_steps, x_warm, dev, khash))
+                except Exception as exc:                  # never lose the headline over an extra
+                    extra_skipped.append({"label": label, "reason": repr(exc)})
+
+        # ── sweeps-to-converge: full run()s from the envs' initial states with their own settings (N = 1, outside the timed
+        # region).  Default config: C3 -> C4 (the headline, `sweeps_to_converge`) -> C5, each only while its estimate fits the
+        # time budget; another --env / --bins: that config alone.  Digests of V and the policy are compared with the committed ones.
+        full_run = None
+        if world == 1 and not args.no_full_run:
+            default_cfg = (args.env, args.bins) == (ENV, BINS)
+            plan = FULL_RUNS if default_cfg else [("this", args.env, args.bins, 0.0)]
+            for label, r_env, r_bins, est in plan:
+                spent = time.perf_counter() - t_start
+                if not default_cfg and n >= (1 << 27) and not args.full_run:
+                    full_runs_skipped.append({"label": label, "reason": f"{n} states: a run to convergence takes minutes; pass --full-run"})
+                    continue
+                if not args.full_run and spent + est + cpu_cost > args.time_budget:
+                    full_runs_skipped.append({"label": label, "reason": f"time budget: {spent:.0f} s spent of {args.time_budget:.0f}, "
+                                                                        f"this run needs ~{est:.0f} s; pass --full-run "
+                                                                        f"(profiles/r05/full_runs.txt holds the measured runs)"})
+                    continue
+                try:
+                    full_runs[label] = run_to_convergence(label, r_env, r_bins, dev)
+                except Exception as exc:                  # never lose the timed result over an extra run
+                    full_runs[label] = {"error": repr(exc)}
+            key = "c4" if default_cfg else "this"
+            full_run = full_runs.get(key) or next(({"skipped": x["reason"]} for x in full_runs_skipped if x["label"] == key), None)
+            for x in extra_configs:                       # C3 / C5: beside their sweep timings as well
+                if x["label"] in full_runs and "full_run" not in x:
+                    x["full_run"] = full_runs[x["label"]]
+
+        # ── roofline ──────────────────────────────────────────────────────────────────────────
+        prof, prof_path = (None, None) if minimal else load_profile(args.env, args.bins, n, khash, order=eng.order)
+        # N > 1: the committed profile is the single-GPU launch of the same kernel; per-wave figures carry over, the number
+        # of waves (and every per-launch total) scales with this rank's share of the states
+        prof_scale = states_per_launch / float(n)
+        bytes_eval = algorithmic_bytes_eval(D)
+        bytes_improve = 4 * (1 << D) + (4 * D + 1 + 4) / nA
+        # cache-perfect HBM bytes of one evaluation sweep: every V value read once (4) + V' written (4) + the policy entry (4),
+        # + the mask byte on grids that have terminal states (the old-value stream is read on residual sweeps only, 1 in 25)
+        compulsory_per_state = 12.0 if solver._mask_arg() is None else 13.0
+        compulsory = compulsory_per_state * states_per_launch
+
+        def kernel_entry(name, ms, backups, alg_bytes_per_backup, counters=None):
+            return kernel_units(name, ms, backups, alg_bytes_per_backup, prof=prof, prof_scale=prof_scale, n=n, n_live=n_live,
+                                live_per_launch=live_per_launch, states_per_launch=states_per_launch, counters=counters)
+
+        if live_states > 0:
+            kernels = {
+                "eval_sweep": kernel_entry("pi_eval_live_kernel", live_ms, states_per_launch, bytes_eval),
+                "eval_sweep_first_of_batch": kernel_entry("pi_eval_sweep_kernel", first_ms, states_per_launch, bytes_eval),
+                "improve_sweep": kernel_entry("pi_improve_live_kernel", improve_ms, states_per_launch * nA, bytes_improve),
+            }
+            kernels["eval_sweep"]["live_states"] = live_states
+            kernels["eval_sweep"]["batch_average_ms"] = eval_ms
+        else:
+            kernels = {
+                "eval_sweep": kernel_entry("pi_eval_sweep_kernel", eval_ms, states_per_launch, bytes_eval),
+                "improve_sweep": kernel_entry("pi_improve_sweep_kernel", improve_ms, states_per_launch * nA, bytes_improve),
+            }
+        if converged:
+            # the same units for the policy-iteration state, from ITS committed counters
+            rprof, rpath = load_profile(args.env, args.bins, n, khash, "real", order=eng.order)
+            if rprof:
+                conv = kernel_entry("pi_eval_sweep_kernel", converged["ms"], states_per_launch, bytes_eval,
+                                    counters=rprof.get("kernels", {}))
+                converged["profile"] = rpath
+                converged["units"] = conv.get("units")
+            kernels["eval_converged_policy"] = converged
+        dom = kernels["eval_sweep"] if share["eval_sweeps"] >= share["improve_sweep"] else kernels["improve_sweep"]
+        roofline = build_roofline(dom, khash, prof_path, compulsory_per_state, compulsory, None if world == 1 else prof_scale)
+        alg_gbps = dom["algorithmic"]["achieved_GBps"]
+        roofline_algorithmic = {"bound": "hbm", "kernel": dom["kernel"], "achieved": alg_gbps, "peak": HBM_PEAK_GBS,
+                                "unit": "GB/s", "frac": None, "ratio_to_hbm_peak": alg_gbps / HBM_PEAK_GBS,
+                                "bytes_per_backup": dom["algorithmic"]["bytes_per_backup"],
+                                "note": "SURVEY 8(d)'s algorithmic bytes over the launch time: above the HBM peak because the 2^D "
+                                        "corner reads are L1 / L2 / Infinity-Cache hits; not a bound, no fraction is claimed "
+                                        "against it — the measured HBM-side fraction is roofline.frac"}
+        out.update({"roofline": roofline, "roofline_algorithmic": roofline_algorithmic, "kernels": kernels,
+                    "sweeps_to_converge": full_run, "full_runs": full_runs, "full_runs_skipped": full_runs_skipped,
+                    "extra_configs": extra_configs, "extra_configs_skipped": extra_skipped})
+        if extra_configs:
+            out["roofline"]["extra_configs"] = {
+                x["label"]: {"env": x["env"], "bins": x["bins"], "eval_ms": round(x["eval_ms"], 5), "improve_ms": round(x["improve_ms"], 5),
+                             "backups_per_s": float(f"{x['backups_per_s']:.4g}"), "frac_hbm": x["roofline"]["frac_hbm"],
+                             "hbm_frac_raw": x["roofline"]["hbm_frac_raw"], "valu_frac": x["roofline"]["valu_frac"],
+                             "l1_load_issue_frac": x["roofline"]["l1_load_issue_frac"],
+                             "frac_hbm_compulsory": x["roofline"].get("frac_hbm_compulsory"),
+                             "traffic_vs_compulsory": x["roofline"].get("traffic_vs_compulsory"),
+                             "floor": x["roofline"].get("floor"), "frac_of_floor": x["roofline"].get("frac_of_floor")}
+                for x in extra_configs}
+        if rank == 0 and not args.no_cpu_baseline and not minimal and os.environ.get("PI_BENCH_BONUS") != "1":   # rank 0's host cores; the other ranks wait at the barrier below
+            out["cpu_baseline"] = cpu_baseline(args.env, args.bins, args.cpu_sample)
     if rank == 0:
         print(json.dumps(out), flush=True)
         if extra_configs or extra_skipped:       # and in short on stderr, where a truncated log still shows it

@@ -56,7 +56,8 @@ REF_CXXFLAGS = ["-O2", "-mfma", "-msse4.1", "-ffp-contract=off", "-fno-fast-math
 
 
 def available() -> bool:
-    return (REFERENCE / "src" / "cuda_policy_iteration.py").exists()
+    """The reference tree is present and readable by this user (os.access: no PermissionError when it is not)."""
+    return os.access(REFERENCE / "src" / "cuda_policy_iteration.py", os.R_OK)
 
 
 def _method_strings(path: Path, cls_name: str, method: str) -> list[str]:

@@ -343,3 +343,43 @@ def test_a_rank_over_the_peer_to_peer_transport_never_touches_the_nccl_backend(m
     assert bench.BONUS_P2P["PI_MI355_TRANSPORT"] == "p2p"
     src = (ROOT / "bench.py").read_text()
     assert src.count('init_process_group("nccl"') == 1 and 'if over_p2p():\n            dist.init_process_group("gloo")' in src
+
+
+def test_dump_outputs_writes_the_last_step_in_the_envs_order(tmp_path, monkeypatch):
+    """--dump-outputs: V and the policy in the env's own order (what run() hands back), the residual and the change count,
+    as float32 / float64 .npy files; grids above DUMP_SAMPLES states at the same seeded, sorted sample of flat indices
+    every time, within 64 MB in all."""
+    import numpy as np
+    import torch
+    bench = _bench()
+
+    class Solver:                                        # device arrays are padded past n_states; memory order = reversed
+        n_states = 10
+        d_value_function = torch.arange(12, dtype=torch.float32) * 0.5
+        d_policy = torch.arange(12, dtype=torch.int32) % 3
+
+        @staticmethod
+        def _to_user(a):
+            return a[::-1].copy()
+
+    def dump(name):
+        bench.dump_outputs(Solver(), str(tmp_path / name), 0.125, 7)
+        return {p.stem: np.load(p) for p in (tmp_path / name).glob("*.npy")}
+
+    whole = dump("whole")
+    assert sorted(whole) == ["changed", "policy", "residual", "state_index", "value_function"]
+    assert whole["value_function"].dtype == np.float32 and whole["policy"].dtype == np.float32
+    assert all(whole[k].dtype == np.float64 for k in ("state_index", "residual", "changed"))
+    assert np.array_equal(whole["state_index"], np.arange(10))
+    assert np.array_equal(whole["value_function"], np.arange(10, dtype=np.float32)[::-1] * 0.5)
+    assert np.array_equal(whole["policy"], (np.arange(10) % 3)[::-1].astype(np.float32))
+    assert whole["residual"].tolist() == [0.125] and whole["changed"].tolist() == [7.0]
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLES", 4)
+    first, again = dump("sample"), dump("sample_again")
+    idx = first["state_index"].astype(np.int64)
+    assert len(idx) == 4 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 10
+    assert all(np.array_equal(first[k], again[k]) for k in first)
+    assert np.array_equal(first["value_function"], whole["value_function"][idx])
+    assert np.array_equal(first["policy"], whole["policy"][idx])
+    assert _bench().DUMP_SAMPLES * (4 + 4 + 8) + 2 * 8 <= 64 << 20

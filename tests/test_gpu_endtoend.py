@@ -1125,6 +1125,58 @@ def test_bench_self_check_of_sharded_sweeps(world, name, shape, cuda_device, mon
     assert not any(o["ok"] for o in bad) and not all(o["V"] for o in bad), bad
 
 
+def test_plain_bench_run_dumps_what_its_last_timed_step_computed(cuda_device, tmp_path):
+    """`bench.py --steps 2 --warmup 1 --dump-outputs DIR` without --full: the line holds the headline and nothing that
+    takes runs of its own; the dump is identical from run to run and equal, bit for bit, to V and the policy after the same
+    seeded steps through the solver here (the env's own order, at the dump's sampled indices)."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+    torch = _torch()
+    root = H.GOLDEN.parents[1]
+    spec = importlib.util.spec_from_file_location("bench_under_test", root / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines, dumps = [], []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                              "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, env=env)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines.append(json.loads(bench.result_line(res.stdout)))
+        dumps.append({p.stem: np.load(p) for p in out.glob("*.npy")})
+    line, dump = lines[0], dumps[0]
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["ms_per_step"] > 0
+    assert not {"roofline", "kernels", "sweeps_to_converge", "full_runs", "extra_configs", "cpu_baseline"} & set(line)
+    assert sorted(dump) == ["changed", "policy", "residual", "state_index", "value_function"]
+    assert all(dump[k].dtype in (np.float32, np.float64) and np.array_equal(dump[k], dumps[1][k]) for k in dump)
+    assert sum(a.nbytes for a in dump.values()) <= 64 << 20
+    assert dump["residual"].tolist() == [line["check"]["last_residual"]]
+    assert dump["changed"].tolist() == [line["check"]["last_changed"]]
+
+    cls = envs.ENVS[bench.ENV]
+    solver = envs.make(bench.ENV, bench.BINS, config=envs.CudaPIConfig(**cls.CONFIG), device=cuda_device)
+    n, nA = solver.n_states, solver.n_actions
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    solver.d_value_function[:n].copy_(torch.randn(n, generator=gen, dtype=torch.float32))
+    solver.d_new_value_function.copy_(solver.d_value_function)
+    solver.d_policy[:n].copy_(torch.randint(0, nA, (n,), generator=gen, dtype=torch.int32))
+    gamma = float(np.float32(solver.config.gamma))
+    for _ in range(3):                                   # the warm-up step and the two timed ones
+        solver._evaluation_sweeps(bench.EVAL_PER_STEP, gamma)
+        solver._improvement_sweep(gamma)
+    idx = dump["state_index"].astype(np.int64)
+    V = solver._to_user(solver.d_value_function[:n].cpu().numpy())
+    P = solver._to_user(solver.d_policy[:n].cpu().numpy())
+    solver._backend.close()
+    assert len(idx) == bench.DUMP_SAMPLES < n
+    assert np.array_equal(V[idx].view(np.uint32), dump["value_function"].view(np.uint32))
+    assert np.array_equal(P[idx], dump["policy"].astype(np.int32))
+
+
 @pytest.mark.parametrize("world,name,shape", [(8, "double_pendulum_swingup", (40, 12, 8, 6)), (4, "double_pendulum_swingup", (24, 9, 7, 5)),
                                                (3, "pendulum", (60, 33))])
 def test_row_exact_swept_first_lists(world, name, shape, cuda_device, monkeypatch):

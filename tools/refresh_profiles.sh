@@ -6,7 +6,7 @@
 #   counters_bench_<cfg>.json      PMC passes of tools/profile_counters.sh on the bench state
 #   kernel_stats_bench_<cfg>.csv   rocprofv3 --kernel-trace --stats of the same command
 #   counters_real_c4.json          the same counters on a policy-iteration state of C4
-#   bench_<cfg>.json               the line `python bench.py [--env ... --bins ...]` prints
+#   bench_<cfg>.json               the line `python bench.py --full [--env ... --bins ...]` prints
 #   kernel_stats_benchpy_c4.csv    rocprofv3 --kernel-trace --stats of the bench command's timed region on the metric config alone
 #                                  (--no-extra-configs: the other configs run the same kernel names and would mix into the averages)
 # cfg = c2 (pendulum 200^2), c3 (cartpole swing-up 50^4), c4 (double pendulum 80^4: the metric config),
@@ -40,11 +40,11 @@ if [ "$WHAT" != "counters" ]; then
 (cd /tmp && TMPDIR=/tmp timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kstats_benchpy -- \
     python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-converged-state --no-full-run --no-extra-configs > $R/$O/kstats_benchpy.log 2>&1)
 cp $O/kstats_benchpy/*/*_kernel_stats.csv $O/kernel_stats_benchpy_c4.csv
-python3 bench.py > $O/bench_c4.json 2> $O/bench_c4.err
-python3 bench.py --env pendulum --bins 200 --steps 200 --warmup 20 > $O/bench_c2.json 2> $O/bench_c2.err
-python3 bench.py --env cartpole_swingup --bins 50 --steps 50 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err
-python3 bench.py --env double_cartpole --bins 25 --steps 5 --warmup 1 --no-full-run > $O/bench_c5.json 2> $O/bench_c5.err
-python3 bench.py --env double_cartpole_swingup --bins 25 --steps 3 --warmup 1 --no-full-run --no-converged-state > $O/bench_c5_swingup.json 2> $O/bench_c5_swingup.err
+python3 bench.py --full > $O/bench_c4.json 2> $O/bench_c4.err
+python3 bench.py --full --env pendulum --bins 200 --steps 200 --warmup 20 > $O/bench_c2.json 2> $O/bench_c2.err
+python3 bench.py --full --env cartpole_swingup --bins 50 --steps 50 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err
+python3 bench.py --full --env double_cartpole --bins 25 --steps 5 --warmup 1 --no-full-run > $O/bench_c5.json 2> $O/bench_c5.err
+python3 bench.py --full --env double_cartpole_swingup --bins 25 --steps 3 --warmup 1 --no-full-run --no-converged-state > $O/bench_c5_swingup.json 2> $O/bench_c5_swingup.err
 rm -rf $O/kstats_benchpy/
 python3 - <<PY
 import json, glob
