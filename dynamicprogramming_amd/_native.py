@@ -9,6 +9,7 @@ still succeeds (so ``load()``-only workflows work on machines without ROCm) but
 from __future__ import annotations
 
 import ctypes
+import enum
 import os
 from pathlib import Path
 
@@ -91,6 +92,93 @@ SIGNATURES = {
 ABI_VERSION = 10
 _lib = None
 _load_error: Exception | None = None
+
+
+# Selector codes of pi_info / pi_set_option / pi_comm_info and the categories they report: a literal copy of the
+# enums of include/pi_mi355.h, which documents every member (tests/test_native_abi.py checks that the two agree).
+class Info(enum.IntEnum):
+    """enum pi_info_code (PI_INFO_*): the `what` of Engine.info."""
+    N_STATES = 0
+    N_ACTIONS = 1
+    DIMS = 2
+    EVAL_CPW = 3
+    EVAL_VGPRS = 4
+    IMPROVE_VGPRS = 5
+    COMPUTE_UNITS = 6
+    CACHE_HIT = 7
+    IMPROVE_CPW = 8
+    CACHED_GRAPHS = 9
+    GRAPHS_ENABLED = 10
+    EVAL_BLOCK = 11
+    IMPROVE_BLOCK = 12
+    RESIDENT_STATES_PER_THREAD = 13
+    RESIDENT_ENABLED = 14
+    DEBUG_CHECKS = 15
+    LIVE_STATES = 16
+    EVAL_LIST_ENTRIES = 17
+    MEMORY_ORDER = 18
+    FLOW_WORKGROUPS = 19
+    RECIPROCAL_DIV = 20         # base: RECIPROCAL_DIV + d for dimension d < D
+    XCD_ENABLED = 30
+    XCD_EVALUATIONS = 31
+    XCD_FALLBACKS = 32
+    WHOLE_RUNS = 33
+    WHOLE_RUN_AVAILABLE = 34
+    STRIP_STATES = 35
+
+
+class Option(enum.IntEnum):
+    """enum pi_option_code (PI_OPTION_*): the `what` of Engine.set_option."""
+    EVAL_CPW = 0
+    IMPROVE_CPW = 1
+    GRAPHS = 2
+    RESIDENT = 3
+    MEMORY_ORDER = 4
+    BUILD_PUSH = 5
+    KEEP_LIVE_LIST = 6
+    STRIP_STATES = 7
+    XCD_RUN_FAILED = 8
+
+
+class XcdFailure(enum.IntEnum):
+    """enum pi_xcd_failure (PI_XCD_FAILURE_*): the values of Option.XCD_RUN_FAILED."""
+    COUNT = 1
+    SWITCH_OFF = 2
+
+
+class CommInfo(enum.IntEnum):
+    """enum pi_comm_info_code (PI_COMM_INFO_*): the `what` of Engine.comm_info."""
+    RANK = 0
+    WORLD = 1
+    TRANSPORT = 2
+    PLAN = 3
+    REACH_UNITS = 4
+    ROW_EXACT = 5
+    FUSED = 6
+    PAIR_EXACT = 7
+    FUSED_VALUES = 8
+    FIRST_ENTRIES = 9
+    INTERIOR_ENTRIES = 10
+
+
+class Transport(enum.IntEnum):
+    """enum pi_transport (PI_TRANSPORT_*): CommInfo.TRANSPORT."""
+    RCCL = 1
+    IN_PROCESS = 2
+    P2P = 3
+
+
+class Plan(enum.IntEnum):
+    """enum pi_plan (PI_PLAN_*): CommInfo.PLAN, and the `mode` of Engine.exchange_plan (NONE: let the library choose)."""
+    NONE = 0
+    ALLGATHER = 1
+    HALO = 2
+
+
+class ReachUnits(enum.IntEnum):
+    """enum pi_reach_unit (PI_REACH_*): CommInfo.REACH_UNITS, the `depth` of Engine.reach_units."""
+    PLANES = 1
+    ROWS = 2
 
 
 class NativeError(RuntimeError):
@@ -191,7 +279,7 @@ class Engine:
 
     def __init__(self, D, grid_shape, lo, hi, bins, actions, device: int = -1, order=None):
         """`order` (optional): memory order of the dimensions — order[k] is the user dimension stored as memory
-        dimension k, 0 = slowest (pi_set_option 4).  Every flat state index and every device array of this engine
+        dimension k, 0 = slowest (Option.MEMORY_ORDER).  Every flat state index and every device array of this engine
         is then in that order (`to_memory` / `to_user` convert whole-grid arrays); results do not depend on it."""
         L = lib()
         self.D = int(D)
@@ -208,14 +296,14 @@ class Engine:
         if not self._h:
             raise NativeError(f"pi_create failed: {last_error()}")
         self.device = int(device)
-        self.n_states = int(L.pi_info(self._h, 0))
+        self.n_states = self.info(Info.N_STATES)
         self.compile_log = ""
         self.order = tuple(range(self.D))
         if order is not None and tuple(int(d) for d in order) != self.order:
             order = tuple(int(d) for d in order)
             if sorted(order) != list(range(self.D)):
                 raise NativeError(f"memory order {order} is not a permutation of the {self.D} dimensions")
-            self.set_option(4, sum(d << (3 * k) for k, d in enumerate(order)))
+            self.set_option(Option.MEMORY_ORDER, sum(d << (3 * k) for k, d in enumerate(order)))
             self.order = order
 
     # -- memory order of the dimensions ----------------------------------------
@@ -272,7 +360,7 @@ class Engine:
         else:
             _check(lib().pi_prepare_mask_range(self._h, term or None, int(s_begin), int(s_end), stream or None),
                    "pi_prepare_mask_range")
-        return self.info(16)
+        return self.info(Info.LIVE_STATES)
 
     def live_list(self, d_out=0, capacity=0, stream=0) -> int:
         """Copy the live-state list into the device buffer at `d_out` (`capacity` int32 entries); returns its length
@@ -286,7 +374,7 @@ class Engine:
         """Start of one policy evaluation under the policy at `policy`: returns the length of the shorter list the
         following whole-grid batches may use (0: none).  Pair with eval_end()."""
         _check(lib().pi_eval_begin(self._h, policy, term or None, stream or None), "pi_eval_begin")
-        return self.info(17)
+        return self.info(Info.EVAL_LIST_ENTRIES)
 
     def eval_end(self) -> None:
         _check(lib().pi_eval_end(self._h), "pi_eval_end")
@@ -346,7 +434,7 @@ class Engine:
         """{grid_x, grid_y, period, phase, cpw} of the launch the sweeps would make (pi_plan_schedule)."""
         out = (ctypes.c_uint64 * 6)()
         _check(lib().pi_plan_schedule(self._h, int(block), int(first), int(count),
-                                      int(self.info(0) if total is None else total), int(chunks_per_workgroup), out),
+                                      int(self.info(Info.N_STATES) if total is None else total), int(chunks_per_workgroup), out),
                "pi_plan_schedule")
         return dict(zip(("grid_x", "grid_y", "period", "phase", "cpw"), (int(v) for v in out)))
 
@@ -406,15 +494,16 @@ class Engine:
     def allreduce_sum_u32(self, d_value, stream=0):
         _check(lib().pi_allreduce_sum_u32(self._h, d_value, stream or None), "pi_allreduce_sum_u32")
 
-    def exchange_plan(self, term, per, mode=0, overlap=True, stream=0):
+    def exchange_plan(self, term, per, mode=Plan.NONE, overlap=True, stream=0):
         info = (ctypes.c_int64 * 5)()
         _check(lib().pi_exchange_plan(self._h, term, int(per), int(mode), int(bool(overlap)), info,
                                       stream or None), "pi_exchange_plan")
-        return {"mode": "halo" if info[0] == 2 else "allgather", "recv_elems": int(info[1]),
+        units = self.comm_info(CommInfo.REACH_UNITS)
+        return {"mode": "halo" if info[0] == Plan.HALO else "allgather", "recv_elems": int(info[1]),
                 "send_elems": int(info[2]), "send_ranges": int(info[3]), "interior_ranges": int(info[4]),
-                "row_exact": int(lib().pi_comm_info(self._h, 5)) == 1,
-                "reach_units": {1: "planes of dimension 0", 2: "rows (i0, i1)"}.get(
-                    int(lib().pi_comm_info(self._h, 4)), "none")}
+                "row_exact": self.comm_info(CommInfo.ROW_EXACT) == 1,
+                "reach_units": ("planes of dimension 0" if units == ReachUnits.PLANES else
+                                "rows (i0, i1)" if units == ReachUnits.ROWS else "none")}
 
     def plan_ranges(self):
         """[(kind, begin, end)] of the current exchange plan: kind 0 = swept first, 1 = interior."""

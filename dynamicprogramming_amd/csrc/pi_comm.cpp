@@ -499,17 +499,22 @@ int pi_comm_destroy(pi_handle* h) {
 int pi_comm_info(pi_handle* h, int what) {
     if (!h || !h->comm) return -1;
     switch (what) {
-        case 0: return h->comm->rank;
-        case 1: return h->comm->world;
-        case 2: return std::strcmp(h->comm->kind(), "rccl") == 0 ? 1 : std::strcmp(h->comm->kind(), "p2p") == 0 ? 3 : 2;
-        case 3: return h->plan ? (h->plan->halo ? 2 : 1) : 0;
-        case 4: return h->plan ? h->plan->depth : 0;
-        case 5: return h->plan && h->plan->row_exact ? 1 : 0;
-        case 6: return h->plan && ((h->plan->row_exact && h->plan->push_ok) || h->plan->live_push_ok) ? 1 : 0;
-        case 7: return h->plan && h->plan->pair_exact ? 1 : 0;
-        case 8: return h->plan ? (int)std::min<int64_t>(h->plan->fused_send_elems, INT32_MAX) : -1;
-        case 9: return h->plan && (h->plan->row_exact || h->plan->live_exact) ? (int)std::min<int64_t>(h->plan->n_first, INT32_MAX) : -1;
-        case 10: return h->plan && (h->plan->row_exact || h->plan->live_exact) ? (int)std::min<int64_t>(h->plan->n_inner, INT32_MAX) : -1;
+        case PI_COMM_INFO_RANK: return h->comm->rank;
+        case PI_COMM_INFO_WORLD: return h->comm->world;
+        case PI_COMM_INFO_TRANSPORT:
+            return std::strcmp(h->comm->kind(), "rccl") == 0  ? PI_TRANSPORT_RCCL
+                 : std::strcmp(h->comm->kind(), "p2p") == 0 ? PI_TRANSPORT_P2P
+                                                            : PI_TRANSPORT_IN_PROCESS;
+        case PI_COMM_INFO_PLAN: return h->plan ? (h->plan->halo ? PI_PLAN_HALO : PI_PLAN_ALLGATHER) : PI_PLAN_NONE;
+        case PI_COMM_INFO_REACH_UNITS: return h->plan ? h->plan->depth : 0;
+        case PI_COMM_INFO_ROW_EXACT: return h->plan && h->plan->row_exact ? 1 : 0;
+        case PI_COMM_INFO_FUSED: return h->plan && ((h->plan->row_exact && h->plan->push_ok) || h->plan->live_push_ok) ? 1 : 0;
+        case PI_COMM_INFO_PAIR_EXACT: return h->plan && h->plan->pair_exact ? 1 : 0;
+        case PI_COMM_INFO_FUSED_VALUES: return h->plan ? (int)std::min<int64_t>(h->plan->fused_send_elems, INT32_MAX) : -1;
+        case PI_COMM_INFO_FIRST_ENTRIES:
+            return h->plan && (h->plan->row_exact || h->plan->live_exact) ? (int)std::min<int64_t>(h->plan->n_first, INT32_MAX) : -1;
+        case PI_COMM_INFO_INTERIOR_ENTRIES:
+            return h->plan && (h->plan->row_exact || h->plan->live_exact) ? (int)std::min<int64_t>(h->plan->n_inner, INT32_MAX) : -1;
         default: return -1;
     }
 }
@@ -576,9 +581,9 @@ int64_t pi_plan_segments(int world, int64_t g0, int64_t stride0, int64_t n_state
     return count;
 }
 
-// mode: 0 = choose (halo unless a rank would receive > 60 % of an all-gather), 1 = all-gather,
-// 2 = halo.  `overlap` = 0 disables the send-first / interior-while-travelling split.
-// info[0] = mode chosen (1 all-gather, 2 halo), info[1] = elements this rank receives per sweep,
+// mode: PI_PLAN_NONE = choose (halo unless a rank would receive > 60 % of an all-gather), PI_PLAN_ALLGATHER,
+// PI_PLAN_HALO.  `overlap` = 0 disables the send-first / interior-while-travelling split.
+// info[0] = mode chosen (PI_PLAN_ALLGATHER | PI_PLAN_HALO), info[1] = elements this rank receives per sweep,
 // info[2] = elements it sends, info[3] = number of send ranges, info[4] = interior ranges.
 int pi_exchange_plan(pi_handle* h, const uint8_t* term, int64_t per, int mode, int overlap,
                      int64_t* info, void* stream) {
@@ -600,7 +605,7 @@ int pi_exchange_plan(pi_handle* h, const uint8_t* term, int64_t per, int mode, i
     plan->depth = depth;
     plan->s_begin = std::min((int64_t)c->rank * per, n);
     plan->s_end = std::min(plan->s_begin + per, n);
-    if (mode != 1) {
+    if (mode != PI_PLAN_ALLGATHER) {
         // reach bitmap of this shard -> all ranks
         std::vector<uint8_t> reach;
         if (gather_reach(c, g0, [&](uint32_t* d_bits) { return pi_reach_units(h, term, plan->s_begin, plan->s_end, depth, d_bits, stream); },
@@ -613,7 +618,7 @@ int pi_exchange_plan(pi_handle* h, const uint8_t* term, int64_t per, int mode, i
         for (int64_t i = 0; i < count; ++i) recv[segs[4 * i + 1]] += segs[4 * i + 3] - segs[4 * i + 2];
         const int64_t full = per * (c->world - 1);
         const int64_t worst = *std::max_element(recv.begin(), recv.end());
-        plan->halo = mode == 2 || (double)worst <= 0.6 * (double)full;
+        plan->halo = mode == PI_PLAN_HALO || (double)worst <= 0.6 * (double)full;
         if (plan->halo) {
             for (int64_t i = 0; i < count; ++i) {
                 pi::ShardPlan::Seg s = {(int)segs[4 * i], (int)segs[4 * i + 1], segs[4 * i + 2], segs[4 * i + 3]};
@@ -888,7 +893,7 @@ int pi_exchange_plan(pi_handle* h, const uint8_t* term, int64_t per, int mode, i
         plan->send_elems = per;
     }
     if (info) {
-        info[0] = plan->halo ? 2 : 1;
+        info[0] = plan->halo ? PI_PLAN_HALO : PI_PLAN_ALLGATHER;
         info[1] = plan->recv_elems;
         info[2] = plan->send_elems;
         info[3] = (int64_t)plan->send_ranges.size();

@@ -97,7 +97,7 @@ struct pi_handle {
     std::vector<int32_t> shape;
     std::vector<float> lo, span, rcp;
     std::vector<int> fastdiv;
-    // Memory order of the dimensions (pi_set_option 4): memory dimension k (0 = slowest) is user dimension user_of_mem[k];
+    // Memory order of the dimensions (PI_OPTION_MEMORY_ORDER): memory dimension k (0 = slowest) is user dimension user_of_mem[k];
     // user dimension d lives in memory dimension mem_of_user[d].  shape / lo / span / rcp / fastdiv / the bin tables
     // are kept in MEMORY order; every flat state index of the C ABI is an index in that order.  Identity by default.
     std::vector<int> mem_of_user, user_of_mem;
@@ -117,7 +117,7 @@ struct pi_handle {
     int num_cu = 0;
     int block_eval = 256, block_improve = 256;   // threads per workgroup = states per chunk
     int cpw_eval = 1, cpw_improve = 1;           // chunks a workgroup sweeps
-    // Strip schedule of the sweeps (pi_set_option 7, PI_MI355_STRIP): states per period — a plane of a slow memory
+    // Strip schedule of the sweeps (PI_OPTION_STRIP_STATES, PI_MI355_STRIP): states per period — a plane of a slow memory
     // dimension; every XCD takes its eighth of every period.  0 = the slab schedule (an XCD walks one contiguous run).
     int64_t strip_states = 0;
     int64_t strip_mode = -1;             // -1 the library's choice (resolve_strip), 0 off, > 0 states per period as given
@@ -126,7 +126,7 @@ struct pi_handle {
     bool debug_bounds = false;           // PI_MI355_DEBUG=1 at pi_create: checked kernels (pi_debug_report)
     bool use_graphs = true;
     // LDS-resident evaluation batches (grids of up to ~12 k states): states per thread of the one
-    // workgroup (resident_block threads), 0 = this grid is too big; the switch is pi_set_option 3
+    // workgroup (resident_block threads), 0 = this grid is too big; the switch is PI_OPTION_RESIDENT
     int resident_k = 0, resident_block = 1024;
     bool use_resident = true;
     // Dataflow evaluation (pi_eval_flow_kernel): launch-bound grids that do not fit one CU's LDS run a whole policy
@@ -141,8 +141,8 @@ struct pi_handle {
     // XCD-local evaluation / whole run (pi_xcd_kernel, csrc/pi_onelaunch_kernels.hip): one 1 024-thread workgroup per CU of
     // ONE XCD, the iterates as tagged granules through that XCD's L2, flag granules as the barrier every 32nd sweep.
     // xcd: this grid qualifies; xcd_off: switched off after repeated failures (pi_policy_evaluation counts its own; a failed
-    // whole run is reported back through pi_set_option 8).  d_xcd: ring of xcd_ring versions | scratch policy | control
-    // words (owned).  Counters for pi_info 30-33.
+    // whole run is reported back through PI_OPTION_XCD_RUN_FAILED).  d_xcd: ring of xcd_ring versions | scratch policy | control
+    // words (owned).  Counters for PI_INFO_XCD_ENABLED - PI_INFO_WHOLE_RUNS.
     bool xcd = false, xcd_off = false;
     int xcd_states = 1024;                               // states per workgroup (PI_XCD_S)
     int xcd_ring = 64;                                   // granule versions of V the kernel keeps (PI_XCD_RING)
@@ -158,7 +158,7 @@ struct pi_handle {
     const uint8_t* live_term = nullptr;
     int32_t* d_live = nullptr;
     int64_t live_count = 0;
-    bool live_force = false;             // pi_set_option 6: keep the list whatever the share of idle lanes
+    bool live_force = false;             // PI_OPTION_KEEP_LIVE_LIST: keep the list whatever the share of idle lanes
     int64_t live_lo = 0, live_hi = 0;    // the state range the list covers (pi_prepare_mask_range; the whole grid otherwise)
     // pi_eval_begin .. pi_eval_end: the live states that bootstrap under the policy at eval_policy (device list,
     // capacity live_count); eval_count < 0: none.  eval_holds: buffers every live state of which has been written

@@ -33,6 +33,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _native
+from ._native import Info, Option, XcdFailure
 
 try:  # the reference logs through loguru; use it when present, stdlib logging otherwise
     from loguru import logger  # type: ignore
@@ -119,9 +120,10 @@ class HipSweepBackend:
     def resident(self) -> bool:
         """True when the library runs a whole policy evaluation (all sweeps and residual checks) of this grid in one
         launch: the LDS-resident kernel for grids one CU holds, the dataflow kernel for launch-bound grids beyond."""
-        if self.one_launch_failures >= 2 and self.engine.info(13) == 0:
+        if self.one_launch_failures >= 2 and self.engine.info(Info.RESIDENT_STATES_PER_THREAD) == 0:
             return False                                             # the dataflow kernel keeps timing out on this box
-        return (self.engine.info(13) > 0 or self.engine.info(19) > 0) and self.engine.info(14) == 1
+        return ((self.engine.info(Info.RESIDENT_STATES_PER_THREAD) > 0 or self.engine.info(Info.FLOW_WORKGROUPS) > 0)
+                and self.engine.info(Info.RESIDENT_ENABLED) == 1)
 
     def policy_evaluation(self, V, policy, term, gamma, theta, max_sweeps, check_interval):
         """The whole evaluation loop on the device (pi_policy_evaluation): returns (sweeps done,
@@ -148,10 +150,11 @@ class HipSweepBackend:
 
     @property
     def whole_run(self) -> bool:
-        """True when the library runs evaluation AND improvement rounds in one launch on this grid (pi_info 34: grids
-        one CU's LDS holds, and 2-D grids of up to 2^16 states beyond those); PI_MI355_WHOLE_RUN=0 keeps the
-        round-by-round loop."""
-        return self.resident and self.engine.info(34) > 0 and os.environ.get("PI_MI355_WHOLE_RUN", "1") != "0"
+        """True when the library runs evaluation AND improvement rounds in one launch on this grid
+        (Info.WHOLE_RUN_AVAILABLE: grids one CU's LDS holds, and 2-D grids of up to 2^16 states beyond those);
+        PI_MI355_WHOLE_RUN=0 keeps the round-by-round loop."""
+        return (self.resident and self.engine.info(Info.WHOLE_RUN_AVAILABLE) > 0
+                and os.environ.get("PI_MI355_WHOLE_RUN", "1") != "0")
 
     def policy_iteration(self, V, policy, term, gamma, theta, max_eval_sweeps, check_interval, max_pi_iter, retried=False):
         """The whole run on the device (pi_policy_iteration).  Returns (rounds done, stable, [(sweeps, residual,
@@ -167,12 +170,13 @@ class HipSweepBackend:
             # the XCD-local launch did not go through (placement, a bounded wait): V and the policy are untouched.  The
             # library cannot count that itself (the call is asynchronous): report it, and where one CU's LDS holds the
             # grid run the whole-run kernel that cannot fail instead of going back to the round-by-round loop.
-            if not retried and self.engine.info(13) > 0 and self.engine.info(14) == 1:
-                self.engine.set_option(8, 2)
+            if (not retried and self.engine.info(Info.RESIDENT_STATES_PER_THREAD) > 0
+                    and self.engine.info(Info.RESIDENT_ENABLED) == 1):
+                self.engine.set_option(Option.XCD_RUN_FAILED, XcdFailure.SWITCH_OFF)
                 return self.policy_iteration(V, policy, term, gamma, theta, max_eval_sweeps, check_interval, max_pi_iter,
                                              retried=True)
             if not retried:
-                self.engine.set_option(8, 1)
+                self.engine.set_option(Option.XCD_RUN_FAILED, XcdFailure.COUNT)
             return None
         log = host[2:2 + 4 * rounds].reshape(rounds, 4)
         residuals = log[:, 1].copy().view(np.float32)
@@ -206,9 +210,10 @@ class HipSweepBackend:
                                 0 if d_changed is None else d_changed.data_ptr(), self._stream())
 
     def close(self):
-        # what the XCD-local kernel did, kept past the handle (pi_info 31 - 33): evaluations run in it, how many of
-        # those were run again in the placement-independent kernel, whole runs launched in it
-        self.xcd_evaluations, self.xcd_fallbacks, self.whole_runs = (self.engine.info(k) for k in (31, 32, 33))
+        # what the XCD-local kernel did, kept past the handle: evaluations run in it, how many of those were run again
+        # in the placement-independent kernel, whole runs launched in it
+        self.xcd_evaluations, self.xcd_fallbacks, self.whole_runs = (
+            self.engine.info(k) for k in (Info.XCD_EVALUATIONS, Info.XCD_FALLBACKS, Info.WHOLE_RUNS))
         self.engine.close()
 
 
@@ -630,7 +635,7 @@ class _CudaPolicyIterationBase(abc.ABC):
                 if getattr(self._comm, "delivers_per_state", False) and os.environ.get("PI_MI355_P2P_FUSED", "1") != "0":
                     # the fused exchange of a grid with terminal states delivers from the list sweeps: keep the list
                     # even where it fills no idle lanes
-                    self._backend.engine.set_option(6, 1)
+                    self._backend.engine.set_option(Option.KEEP_LIVE_LIST, 1)
                 self._backend.prepare_mask(self._term_arg, self._s_begin, self._s_end)
             else:
                 self._backend.prepare_mask(self._term_arg)

@@ -29,6 +29,7 @@ import os
 import numpy as np
 
 from . import _native
+from ._native import Plan
 
 
 def shard_bounds(n: int, rank: int, world: int):
@@ -72,7 +73,7 @@ class NativeTransport:
             self.engine.comm_init(self.rank, self.world, self._unique_id)
 
     def plan(self, solver) -> None:
-        mode = {"auto": 0, "allgather": 1, "halo": 2}[os.environ.get("PI_MI355_EXCHANGE", "auto")]
+        mode = {"auto": Plan.NONE, "allgather": Plan.ALLGATHER, "halo": Plan.HALO}[os.environ.get("PI_MI355_EXCHANGE", "auto")]
         overlap = os.environ.get("PI_MI355_OVERLAP", "1") != "0"
         self.info = self.engine.exchange_plan(solver._backend._ptr(solver._mask_arg()), solver._shard_len,
                                               mode, overlap, self._stream())

@@ -119,7 +119,7 @@ int pi_eval_sweeps(pi_handle* h, float* Va, float* Vb, const int32_t* policy,
  * on `stream`).  Worth it where terminal regions cut through many waves — double cartpole 25^6: 35 % of the
  * states are terminal and 16 % of the waves are partly idle — and skipped where it is not: the list is kept
  * only when at least 3 % of the grid's lane slots would be idle otherwise and the grid has 2^20 states or more
- * (pi_info 16 = length of the list in use, 0 = none).  Results are identical with and without it.
+ * (PI_INFO_LIVE_STATES = length of the list in use, 0 = none).  Results are identical with and without it.
  * Contract: the bytes behind d_term must not change while the list is in use; call again after changing
  * them, or with d_term == NULL to drop the list.  Calls given another mask pointer, or a state range that is not
  * inside the listed one, ignore the list.  pi_prepare_mask lists the whole grid (4 B per live state on the device,
@@ -141,7 +141,7 @@ int64_t pi_live_list(pi_handle* h, int32_t* d_out, int64_t capacity, void* strea
  * kept when it saves at least 3 %), and until pi_eval_end whole-grid pi_eval_sweeps batches with this policy
  * pointer use it for every sweep whose source AND destination buffer have been written by a full sweep since
  * pi_eval_begin (the library tracks the buffers; with the reference's ping-pong that is every sweep after the
- * evaluation's second).  Results are identical with and without the bracket.  pi_info 17 = entries in use.
+ * evaluation's second).  Results are identical with and without the bracket.  PI_INFO_EVAL_LIST_ENTRIES = entries in use.
  * Contract: between begin and end neither the policy array nor the value buffers are written by anyone but
  * the evaluation sweeps; pi_improve_sweep / pi_value_sweep end the bracket by themselves.
  */
@@ -150,8 +150,8 @@ int pi_eval_end(pi_handle* h);
 
 /*
  * The whole policy_evaluation loop (:300-336) in ONE launch, for grids the LDS-resident kernel
- * holds (pi_info 13 > 0: up to 12 288 states in 2-D, 4 096 in 4-D, 1 024 in 6-D) and, beyond those, for
- * launch-bound grids of up to 2^17 states in 2-D / 4-D (pi_info 19 > 0 = workgroups of the dataflow kernel:
+ * holds (PI_INFO_RESIDENT_STATES_PER_THREAD > 0: up to 12 288 states in 2-D, 4 096 in 4-D, 1 024 in 6-D) and, beyond those, for
+ * launch-bound grids of up to 2^17 states in 2-D / 4-D (PI_INFO_FLOW_WORKGROUPS > 0 = workgroups of the dataflow kernel:
  * the iterates travel between workgroups as tagged 8-byte granules, no grid barrier between sweeps; BASELINE
  * config C2, pendulum 200 x 200, is one); fails on every other grid: up to max_sweeps Jacobi sweeps of the whole grid under
  * `policy`, the residual looked at on sweeps 0, check_interval, 2 check_interval, ... (the
@@ -160,7 +160,7 @@ int pi_eval_end(pi_handle* h);
  * *d_delta (nullable) the last residual looked at, d_residual_log[k] every residual looked at
  * (k-th look; at least max_sweeps / check_interval + 2 floats).  Same arithmetic, same sweep
  * count and same V as the same loop driven from the host through pi_eval_sweeps.
- * On 2-D grids of ~4 000 to 2^16 states among those (pi_info 30 > 0) the evaluation first runs on the CUs of ONE XCD, with
+ * On 2-D grids of ~4 000 to 2^16 states among those (PI_INFO_XCD_ENABLED) the evaluation first runs on the CUs of ONE XCD, with
  * the hand-off through that XCD's L2 (pi_xcd_kernel; placement checked at run time; the call then synchronises `stream`
  * once); when that launch cannot go through V is untouched and the LDS-resident or the dataflow kernel runs the evaluation.
  * Dataflow kernel: every device-side wait is bounded (PI_MI355_FLOW_TIMEOUT seconds, default 2; the kernel needs all its
@@ -174,9 +174,9 @@ int pi_policy_evaluation(pi_handle* h, float* V, const int32_t* policy, const ui
 
 /*
  * The reference's whole run() (:357-370) — policy_evaluation (:300-336), policy_improvement (:338-355), until no entry
- * of the policy changes or max_pi_iter rounds are done — in ONE launch (pi_info 34 > 0), for grids the LDS-resident
- * kernel holds (pi_info 13 > 0; BASELINE config C1, pendulum 50 x 50, is one: V and the policy stay in one CU's LDS) and
- * for 2-D grids of ~4 000 to 2^16 states (pi_info 30 > 0; BASELINE config C2, pendulum 200 x 200, is one: the
+ * of the policy changes or max_pi_iter rounds are done — in ONE launch (PI_INFO_WHOLE_RUN_AVAILABLE), for grids the
+ * LDS-resident kernel holds (PI_INFO_RESIDENT_STATES_PER_THREAD > 0; BASELINE config C1, pendulum 50 x 50, is one: V and
+ * the policy stay in one CU's LDS) and for 2-D grids of ~4 000 to 2^16 states (PI_INFO_XCD_ENABLED; BASELINE config C2, pendulum 200 x 200, is one: the
  * kernel runs on the CUs of one XCD, the iterates travel through that XCD's L2 as tagged granules, a thread keeps the
  * actions of its states in registers).  V and policy are updated in place (the last iterate, the last policy); each
  * evaluation does up to max_eval_sweeps sweeps with the residual looked at every check_interval sweeps exactly as
@@ -186,7 +186,7 @@ int pi_policy_evaluation(pi_handle* h, float* V, const int32_t* policy, const ui
  * Same arithmetic, sweep counts, V and policy as the same loop driven through pi_policy_evaluation / pi_improve_sweep.
  * XCD-local kernel: every device-side wait is bounded and workgroup placement is checked, not assumed: when the launch
  * could not go through, d_result[0] < 0 and V and policy hold what they held before the call — the caller runs the loop
- * itself.  Asynchronous on `stream`.  pi_info 33 = whole runs launched.
+ * itself.  Asynchronous on `stream`.  PI_INFO_WHOLE_RUNS = whole runs launched.
  */
 int pi_policy_iteration(pi_handle* h, float* V, int32_t* policy, const uint8_t* term, float gamma, double theta,
                         int max_eval_sweeps, int check_interval, int max_pi_iter, int32_t* d_result, uint32_t* d_iter_log,
@@ -279,18 +279,46 @@ int pi_p2p_describe(pi_handle* h, int rank, int world, const void* const* bufs, 
 int pi_comm_init_p2p(pi_handle* h, int rank, int world, const void* descs, const char* cache_dir);
 int pi_p2p_compile_check(const char* cache_dir);
 int pi_comm_destroy(pi_handle* h);
-/* Fused exchange: when the plan is row-exact (pi_comm_info(h, 5)) and the transport is the peer-to-peer one, the
+/* Fused exchange: when the plan is row-exact (PI_COMM_INFO_ROW_EXACT) and the transport is the peer-to-peer one, the
  * swept-first launch of every sharded evaluation sweep is pi_eval_push_kernel (csrc/pi_push_kernels.hip): the lane that
  * stores V'(s) stores it into the peers that read the row as well, one-wave kernels hand-shake in front of it and behind
- * it, everything on the caller's stream — no copy kernel, no second stream (pi_comm_info(h, 6) == 1;
+ * it, everything on the caller's stream — no copy kernel, no second stream (PI_COMM_INFO_FUSED;
  * PI_MI355_P2P_FUSED=0 keeps the copy kernel); on grids with terminal states whose shard keeps a live-state list
  * (pi_prepare_mask_range) the later sweeps of every batch are fused the same way.  The kernel lives in a second module of the handle that is built on
- * demand from the same translation unit (pi_set_option 5 builds it ahead of time). */
-/* 0 rank, 1 world, 2 transport (1 RCCL, 2 in-process, 3 peer-to-peer), 3 plan (0 none, 1 all-gather, 2 halo),
- * 4 granularity of the plan's reach probe (1 planes of dimension 0, 2 rows (i0, i1)), 5 row-exact plan (0 | 1),
- * 6 fused exchange (0 | 1), 7 destination masks cut down to the pairs (i_0, i_v) each peer reads (0 | 1; any memory order
- * with dimension 0 slowest), 8 values one fused sweep delivers, counted per receiver (-1: not a fused plan), 9 / 10 entries of
- * the swept-first / interior state lists of a row-exact or state-exact plan (-1: the plan sweeps ranges). */
+ * demand from the same translation unit (PI_OPTION_BUILD_PUSH builds it ahead of time). */
+/* The `what` of pi_comm_info.  Every other code, and every code on a handle without a communicator, returns -1. */
+enum pi_comm_info_code {
+    PI_COMM_INFO_RANK = 0,              /* this rank */
+    PI_COMM_INFO_WORLD = 1,             /* number of ranks */
+    PI_COMM_INFO_TRANSPORT = 2,         /* enum pi_transport */
+    PI_COMM_INFO_PLAN = 3,              /* enum pi_plan */
+    PI_COMM_INFO_REACH_UNITS = 4,       /* granularity of the plan's reach probe: enum pi_reach_unit (0: no plan) */
+    PI_COMM_INFO_ROW_EXACT = 5,         /* row-exact plan (0 | 1) */
+    PI_COMM_INFO_FUSED = 6,             /* fused exchange (0 | 1) */
+    PI_COMM_INFO_PAIR_EXACT = 7,        /* destination masks cut down to the pairs (i_0, i_v) each peer reads (0 | 1; any
+                                           memory order with dimension 0 slowest) */
+    PI_COMM_INFO_FUSED_VALUES = 8,      /* values one fused sweep delivers, counted per receiver (-1: not a fused plan) */
+    PI_COMM_INFO_FIRST_ENTRIES = 9,     /* entries of the swept-first state list of a row-exact or state-exact plan (-1:
+                                           the plan sweeps ranges) */
+    PI_COMM_INFO_INTERIOR_ENTRIES = 10  /* entries of the interior state list of such a plan (-1: the plan sweeps ranges) */
+};
+/* PI_COMM_INFO_TRANSPORT */
+enum pi_transport {
+    PI_TRANSPORT_RCCL = 1,              /* RCCL (pi_comm_init) */
+    PI_TRANSPORT_IN_PROCESS = 2,        /* in-process test transport (pi_comm_init_local) */
+    PI_TRANSPORT_P2P = 3                /* peer-to-peer stores (pi_comm_init_p2p) */
+};
+/* PI_COMM_INFO_PLAN; also the `mode` of pi_exchange_plan and the mode it reports in info[0] */
+enum pi_plan {
+    PI_PLAN_NONE = 0,                   /* no plan; as the `mode` of pi_exchange_plan: let the library choose */
+    PI_PLAN_ALLGATHER = 1,              /* all-gather V after every sweep */
+    PI_PLAN_HALO = 2                    /* send only the values peers read */
+};
+/* PI_COMM_INFO_REACH_UNITS; also the `depth` of pi_reach_units and what pi_reach_depth_max returns */
+enum pi_reach_unit {
+    PI_REACH_PLANES = 1,                /* planes of dimension 0 */
+    PI_REACH_ROWS = 2                   /* rows (i0, i1) */
+};
 int pi_comm_info(pi_handle* h, int what);
 
 /* In-place collectives on the caller's stream: shard r of the buffer lives at r * shard_elems. */
@@ -311,10 +339,10 @@ int64_t pi_plan_segments(int world, int64_t g0, int64_t stride0, int64_t n_state
 
 /*
  * Collective: measure this shard's reach (pi_reach_units at pi_reach_depth_max), all-gather the
- * bitmaps, derive the segments and choose the exchange.  mode 0 = choose (halo unless some rank would receive more
- * than 60 % of an all-gather), 1 = all-gather, 2 = halo; overlap != 0 sweeps the planes peers
+ * bitmaps, derive the segments and choose the exchange.  mode (enum pi_plan): PI_PLAN_NONE = choose (halo unless some
+ * rank would receive more than 60 % of an all-gather), PI_PLAN_ALLGATHER, PI_PLAN_HALO; overlap != 0 sweeps the planes peers
  * wait for first and sends them on a second stream while the interior is swept.
- * info (nullable, 5 values): mode chosen (1 | 2), elements received / sent per sweep by this rank,
+ * info (nullable, 5 values): mode chosen (PI_PLAN_ALLGATHER | PI_PLAN_HALO), elements received / sent per sweep by this rank,
  * number of send ranges, number of interior ranges.  Blocks on `stream` (one-off).
  */
 int pi_exchange_plan(pi_handle* h, const uint8_t* term, int64_t per, int mode, int overlap,
@@ -322,13 +350,13 @@ int pi_exchange_plan(pi_handle* h, const uint8_t* term, int64_t per, int mode, i
 /* The launch ranges of the current plan: up to cap triples {kind, begin, end}, kind 0 = swept first
  * (peers wait for rows inside it), 1 = interior (swept while the halo travels).  Returns how many
  * there are (-1 without a plan).  A plan without overlap reports the shard as one kind-0 range; a plan whose swept-first
- * set is a list of single states (pi_comm_info(h, 7): the fused exchange in a memory order whose rows are all reachable)
+ * set is a list of single states (PI_COMM_INFO_PAIR_EXACT: the fused exchange in a memory order whose rows are all reachable)
  * reports the coarse row ranges it was cut from. */
 int64_t pi_plan_ranges(pi_handle* h, int64_t* ranges, int64_t cap);
 /*
  * One part of a sharded evaluation sweep WITHOUT the exchange, launched exactly as pi_eval_sweeps_sharded launches it:
  * part 0 = what the peers wait for (swept first), part 1 = the interior; both together are one sweep of the shard.
- * On grids without terminal states the plan may be ROW-EXACT (pi_comm_info(h, 5) == 1; PI_MI355_ROW_EXACT=0 / 1
+ * On grids without terminal states the plan may be ROW-EXACT (PI_COMM_INFO_ROW_EXACT; PI_MI355_ROW_EXACT=0 / 1
  * forces it): part 0 is then the list of exactly the rows that travel, swept in one launch of the list kernel, and
  * part 1 the list of all other states of the shard, instead of a few contiguous ranges that also hold rows nobody
  * waits for.  No reference counterpart (src/cuda_policy_iteration.py:300-336 is a single-device loop); for measurements
@@ -371,8 +399,8 @@ int pi_probe_coords(pi_handle* h, int64_t s_begin, int64_t s_end, float* out, in
  * `block`-thread workgroups taking `chunks_per_workgroup` chunks each over `count` units (states, or entries of a state
  * list) from unit `first`, where `total` units stand for the whole grid (n_states for a state range).
  * out6 = {grid x, grid y, period, phase, chunks per workgroup, 0}: period == 0 is the slab schedule (grid y = 1; XCD x =
- * workgroup index mod 8 walks the x-th contiguous eighth of the groups); otherwise the STRIP schedule (pi_set_option 7,
- * PI_MI355_STRIP, pi_info 35): the groups are cut into periods of `period` groups — a plane of a slow memory
+ * workgroup index mod 8 walks the x-th contiguous eighth of the groups); otherwise the STRIP schedule (PI_OPTION_STRIP_STATES,
+ * PI_MI355_STRIP, PI_INFO_STRIP_STATES): the groups are cut into periods of `period` groups — a plane of a slow memory
  * dimension —, the launch is two-dimensional (y = period p, x = 8 r + XCD) and XCD x takes groups
  * [floor((x period + rot) / 8), floor(((x + 1) period + rot) / 8)), rot = 3 p mod 8, of EVERY period p, so that what an
  * XCD's L2 sees between the two sweeps that read a line of V is an eighth of a plane instead of a whole one.  Placement only: results do not depend on it.  No reference counterpart
@@ -408,36 +436,74 @@ int pi_infer_set_policy(pi_infer* h, const int32_t* policy, int64_t n_states, co
 int pi_infer_query(pi_infer* h, const float* d_points, int64_t m, float* d_actions_out, float* d_weights_out,
                    int32_t* d_indices_out, void* stream);
 
-/* Tuning: 0 = chunks per workgroup of the evaluation sweeps, 1 = of the improvement / value sweeps
- * (1..64), 2 = replay small evaluation batches as hipGraphs (0 | 1), 3 = run whole-grid batches of
- * small grids in the LDS-resident kernel (0 | 1), 5 = build the fused swept-first kernel of the peer-to-peer exchange
- * now (value != 0; after pi_compile; a compile check on host-only handles), 6 = keep the live-state list of
- * pi_prepare_mask even when it fills no idle lanes (0 | 1; the fused exchange of a sharded run delivers from the list sweeps),
- * 8 = report that the last pi_policy_iteration launch on the XCD-local kernel did not go through (1: count it — two
- * failures switch that kernel off for the handle —, 2: and switch it off now),
- * 7 = STRIP SCHEDULE of the sweeps: states per period (see pi_plan_schedule; -1 = the library's choice for the grid, the
- * default; 0 = slab schedule; PI_MI355_STRIP in the environment at pi_create sets the same), 4 = MEMORY ORDER of the dimensions (before pi_compile, once):
- * digit k (base 8) of the value is the dimension — numbered as in pi_create and in step_dynamics' arguments —
- * that is stored as memory dimension k, 0 = slowest; e.g. 03120 (octal) = order (0, 2, 1, 3).  From then on
- * EVERY flat state index of this ABI (s_begin / s_end, the entries of V, policy and the mask, the indices the
+/* Tuning: the `what` of pi_set_option. */
+enum pi_option_code {
+    PI_OPTION_EVAL_CPW = 0,          /* chunks per workgroup of the evaluation sweeps (1..64) */
+    PI_OPTION_IMPROVE_CPW = 1,       /* chunks per workgroup of the improvement / value sweeps (1..64) */
+    PI_OPTION_GRAPHS = 2,            /* replay small evaluation batches as hipGraphs (0 | 1) */
+    PI_OPTION_RESIDENT = 3,          /* run whole-grid batches of small grids in the LDS-resident kernel (0 | 1) */
+    PI_OPTION_MEMORY_ORDER = 4,      /* MEMORY ORDER of the dimensions (before pi_compile, once; see below) */
+    PI_OPTION_BUILD_PUSH = 5,        /* value != 0: build the fused swept-first kernel of the peer-to-peer exchange now
+                                        (after pi_compile; a compile check on host-only handles) */
+    PI_OPTION_KEEP_LIVE_LIST = 6,    /* keep the live-state list of pi_prepare_mask even when it fills no idle lanes
+                                        (0 | 1; the fused exchange of a sharded run delivers from the list sweeps) */
+    PI_OPTION_STRIP_STATES = 7,      /* STRIP SCHEDULE of the sweeps: states per period (see pi_plan_schedule; -1 = the
+                                        library's choice for the grid, the default; 0 = slab schedule; PI_MI355_STRIP in
+                                        the environment at pi_create sets the same) */
+    PI_OPTION_XCD_RUN_FAILED = 8     /* the last pi_policy_iteration launch on the XCD-local kernel did not go through
+                                        (value: enum pi_xcd_failure) */
+};
+/* The values PI_OPTION_XCD_RUN_FAILED takes. */
+enum pi_xcd_failure {
+    PI_XCD_FAILURE_COUNT = 1,        /* count it: two failures switch that kernel off for the handle */
+    PI_XCD_FAILURE_SWITCH_OFF = 2    /* count it and switch that kernel off now */
+};
+/* PI_OPTION_MEMORY_ORDER: digit k (base 8) of the value is the dimension — numbered as in pi_create and in
+ * step_dynamics' arguments — that is stored as memory dimension k, 0 = slowest; e.g. 03120 (octal) = order (0, 2, 1, 3).
+ * From then on EVERY flat state index of this ABI (s_begin / s_end, the entries of V, policy and the mask, the indices the
  * interpolation probe returns) refers to that order: index = sum_k i_{order[k]} * stride_k with row-major
  * strides over the permuted shape.  The reference has one order, the meshgrid's (:84-87); which dimensions
  * are slow decides how far apart in memory the 2^D corners of a successor cell lie and how long a value
  * stays useful in an XCD's L2 — the best order beats the user's by 7-11 % on the evaluation sweeps of the
  * big BASELINE grids (tools/dim_order_sweep.py).  The order-sensitive arithmetic (corner weights as products
  * over the dimensions, the fmaf chain over the corners, :580-614, :616-649) stays in the caller's dimension
- * order, so results do not depend on the memory order, bit for bit; neither do they depend on options 0-3 and 7. */
+ * order, so results do not depend on the memory order, bit for bit; neither do they depend on PI_OPTION_EVAL_CPW,
+ * PI_OPTION_IMPROVE_CPW, PI_OPTION_GRAPHS, PI_OPTION_RESIDENT and PI_OPTION_STRIP_STATES. */
 int pi_set_option(pi_handle* h, int what, int64_t value);
 
-/* Introspection: 0 n_states, 1 n_actions, 2 D, 3 chunks per workgroup (evaluation), 4 VGPRs of the
- * eval kernel, 5 VGPRs of the improve kernel, 6 compute units, 7 = 1 if the last pi_compile was
- * served from the cache, 8 chunks per workgroup (improvement), 9 cached graphs, 10 graphs enabled,
- * 11 / 12 threads per workgroup (evaluation / improvement), 13 states per thread of the LDS-resident
- * batch kernel (0: grid too big for it), 14 that kernel enabled, 15 checked kernels (pi_debug_report),
- * 35 states per period of the strip schedule in use (0: slab schedule),
- * 16 live states listed by pi_prepare_mask (0: no list in use), 17 entries of the per-evaluation list of
- * pi_eval_begin (0: none), 18 the memory order as set with pi_set_option 4 (octal digits, identity by default),
- * 20+d = 1 if dimension d's interpolation division runs through the proven reciprocal path. */
+/* Introspection: the `what` of pi_info.  Every other code returns -1. */
+enum pi_info_code {
+    PI_INFO_N_STATES = 0,                     /* states of the grid */
+    PI_INFO_N_ACTIONS = 1,                    /* actions */
+    PI_INFO_DIMS = 2,                         /* D */
+    PI_INFO_EVAL_CPW = 3,                     /* chunks per workgroup of the evaluation sweeps */
+    PI_INFO_EVAL_VGPRS = 4,                   /* VGPRs of the evaluation kernel (-1 until a device loads it) */
+    PI_INFO_IMPROVE_VGPRS = 5,                /* VGPRs of the improvement kernel (-1 until a device loads it) */
+    PI_INFO_COMPUTE_UNITS = 6,                /* compute units of the device */
+    PI_INFO_CACHE_HIT = 7,                    /* 1 if the last pi_compile was served from the cache */
+    PI_INFO_IMPROVE_CPW = 8,                  /* chunks per workgroup of the improvement sweeps */
+    PI_INFO_CACHED_GRAPHS = 9,                /* hipGraphs cached by the handle */
+    PI_INFO_GRAPHS_ENABLED = 10,              /* 1 if PI_OPTION_GRAPHS is on */
+    PI_INFO_EVAL_BLOCK = 11,                  /* threads per workgroup of the evaluation sweeps */
+    PI_INFO_IMPROVE_BLOCK = 12,               /* threads per workgroup of the improvement sweeps */
+    PI_INFO_RESIDENT_STATES_PER_THREAD = 13,  /* states per thread of the LDS-resident batch kernel (0: grid too big) */
+    PI_INFO_RESIDENT_ENABLED = 14,            /* 1 if that kernel is enabled (PI_OPTION_RESIDENT) */
+    PI_INFO_DEBUG_CHECKS = 15,                /* 1 if the handle's kernels are checked (pi_debug_report) */
+    PI_INFO_LIVE_STATES = 16,                 /* live states listed by pi_prepare_mask (0: no list in use) */
+    PI_INFO_EVAL_LIST_ENTRIES = 17,           /* entries of the per-evaluation list of pi_eval_begin (0: none) */
+    PI_INFO_MEMORY_ORDER = 18,                /* the memory order as set with PI_OPTION_MEMORY_ORDER (octal digits,
+                                                 identity by default) */
+    PI_INFO_FLOW_WORKGROUPS = 19,             /* workgroups of the dataflow evaluation kernel (0: not for this grid; 1 on
+                                                 a host-only handle whose grid it serves) */
+    PI_INFO_RECIPROCAL_DIV = 20,              /* base: code + d (d < D) = 1 if dimension d's interpolation division
+                                                 runs through the proven reciprocal path */
+    PI_INFO_XCD_ENABLED = 30,                 /* 1 if the XCD-local evaluation kernel is in use */
+    PI_INFO_XCD_EVALUATIONS = 31,             /* evaluations attempted in it */
+    PI_INFO_XCD_FALLBACKS = 32,               /* ... run again after a placement failure or a time-out */
+    PI_INFO_WHOLE_RUNS = 33,                  /* whole runs launched (pi_policy_iteration) */
+    PI_INFO_WHOLE_RUN_AVAILABLE = 34,         /* 1 if pi_policy_iteration serves this grid */
+    PI_INFO_STRIP_STATES = 35                 /* states per period of the strip schedule in use (0: slab schedule) */
+};
 int64_t pi_info(pi_handle* h, int what);
 
 /*

@@ -19,6 +19,7 @@ import torch
 import torch.distributed as dist
 
 from dynamicprogramming_amd import envs
+from dynamicprogramming_amd._native import CommInfo, Transport
 
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
@@ -33,8 +34,9 @@ for name, shape in (("double_pendulum_swingup", (16, 10, 12, 10)), ("double_cart
     cfg = dict(cls.CONFIG, max_pi_iter=3, max_eval_iter=60)
     sharded = cls(bins, cls.ACTIONS, envs.CudaPIConfig(**cfg), device=dev)
     eng = sharded._backend.engine
-    comm = {"world": eng.comm_info(1), "transport": {1: "rccl", 2: "in-process", 3: "p2p"}.get(eng.comm_info(2), "none"),
-            "rank": eng.comm_info(0), "plan": dict(sharded._comm.info) if sharded._comm is not None else None}
+    transport = {Transport.RCCL: "rccl", Transport.IN_PROCESS: "in-process", Transport.P2P: "p2p"}
+    comm = {"world": eng.comm_info(CommInfo.WORLD), "transport": transport.get(eng.comm_info(CommInfo.TRANSPORT), "none"),
+            "rank": eng.comm_info(CommInfo.RANK), "plan": dict(sharded._comm.info) if sharded._comm is not None else None}
     sharded.run()
     alone = cls(bins, cls.ACTIONS, envs.CudaPIConfig(**cfg), device=dev, transport=False)
     alone.run()

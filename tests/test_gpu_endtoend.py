@@ -17,6 +17,7 @@ import pytest
 
 import oracle
 from dynamicprogramming_amd import _native, envs
+from dynamicprogramming_amd._native import Info, Option
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -559,14 +560,14 @@ def test_checked_build_reports_bad_indices_and_changes_nothing_else(name, shape,
         return [t.cpu().numpy() for t in (a, b, d, single, p2, c)]
 
     plain = engine()
-    assert plain.info(15) == 0
+    assert plain.info(Info.DEBUG_CHECKS) == 0
     with pytest.raises(_native.NativeError, match="PI_MI355_DEBUG"):
         plain.debug_report()
     want = sweeps(plain, pol)
     plain.close()
     monkeypatch.setenv("PI_MI355_DEBUG", "1")
     chk = engine()
-    assert chk.info(15) == 1 and "#define PI_DEBUG_BOUNDS 1" in chk.kernel_source(envs.dynamics_source(name))
+    assert chk.info(Info.DEBUG_CHECKS) == 1 and "#define PI_DEBUG_BOUNDS 1" in chk.kernel_source(envs.dynamics_source(name))
     got = sweeps(chk, pol)
     assert chk.debug_report() == {"violations": 0, "kind": 0, "where": 0, "value": 0}
     for x, y in zip(want, got):
@@ -703,10 +704,10 @@ def test_live_state_list_changes_speed_not_results(name, shape, cuda_device, mon
     pad = np.concatenate([term, np.ones(-n % 64, bool)]).reshape(-1, 64)
     idle = ((~pad).any(axis=1).sum() * 64 - (~term).sum()) / n          # lane slots idle in partly live waves
     if idle < 0.03:                                            # the crane: terminal states come in whole planes
-        assert listed == 0 and eng.info(16) == 0
+        assert listed == 0 and eng.info(Info.LIVE_STATES) == 0
         eng.close()
         return
-    assert listed == int((~term).sum()) and eng.info(16) == listed
+    assert listed == int((~term).sum()) and eng.info(Info.LIVE_STATES) == listed
     for (k, r), want in plain.items():
         got = batch(d_term, k, r)
         for x, y in zip(want[:2], got[:2]):
@@ -730,7 +731,7 @@ def test_live_state_list_changes_speed_not_results(name, shape, cuda_device, mon
     got = batch(d_term, 5, True)
     H.assert_bits_equal(got[1], cur, "5 sweeps through the live list vs oracle")
     assert np.float32(got[2]) == np.float32(o_delta)
-    assert eng.prepare_mask(0) == 0 and eng.info(16) == 0
+    assert eng.prepare_mask(0) == 0 and eng.info(Info.LIVE_STATES) == 0
     eng.close()
 
 
@@ -748,7 +749,7 @@ def test_live_state_list_in_the_sharded_driver(world, name, shape, mode, cuda_de
     cfg_kw = {**cls.CONFIG, "max_pi_iter": 3, "max_eval_iter": 60}
     monkeypatch.setenv("PI_MI355_LIVE", "0")
     single = cls(H.env_bins_space(name, shape), cls.ACTIONS, envs.CudaPIConfig(**cfg_kw), device=cuda_device)
-    assert single._backend.engine.info(16) == 0
+    assert single._backend.engine.info(Info.LIVE_STATES) == 0
     single.run()
     monkeypatch.setenv("PI_MI355_LIVE", "1")
     monkeypatch.setenv("PI_MI355_LIVE_MIN", "1")
@@ -764,7 +765,7 @@ def test_live_state_list_in_the_sharded_driver(world, name, shape, mode, cuda_de
             with torch.cuda.stream(stream):
                 s = cls(H.env_bins_space(name, shape), cls.ACTIONS, envs.CudaPIConfig(**cfg_kw), device=cuda_device,
                         transport=T.NativeTransport.local(r, world, group))
-                listed = s._backend.engine.info(16)
+                listed = s._backend.engine.info(Info.LIVE_STATES)
                 s.run()
             out[r] = (s.value_function, s.policy, list(s.stats["sweeps_per_iter"]), listed)
         except Exception as exc:  # noqa: BLE001
@@ -836,9 +837,9 @@ def test_per_evaluation_list_changes_speed_not_results(name, shape, cuda_device,
             assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), pattern
         assert want[2] == got[2], pattern
     # an improvement sweep ends the bracket by itself (the policy may have changed)
-    assert eng.eval_begin(pol.data_ptr(), d_term.data_ptr()) > 0 and eng.info(17) > 0
+    assert eng.eval_begin(pol.data_ptr(), d_term.data_ptr()) > 0 and eng.info(Info.EVAL_LIST_ENTRIES) > 0
     eng.improve_sweep(V0.data_ptr(), pol.clone().data_ptr(), d_term.data_ptr(), 0, n, gamma, 0)
-    assert eng.info(17) == 0
+    assert eng.info(Info.EVAL_LIST_ENTRIES) == 0
     eng.close()
     # solver level
     runs = {}
@@ -860,7 +861,7 @@ def test_live_state_list_at_full_c5_size(cuda_device):
     solver = envs.make("double_cartpole", 25)
     eng = solver._backend.engine
     n = solver.n_states
-    assert eng.info(16) == int((solver.d_terminal_mask[:n] == 0).sum().item()) > 0
+    assert eng.info(Info.LIVE_STATES) == int((solver.d_terminal_mask[:n] == 0).sum().item()) > 0
     gen = torch.Generator(device="cpu").manual_seed(3)
     solver.d_value_function[:n].copy_(torch.randn(n, generator=gen, dtype=torch.float32))
     solver.d_policy[:n].copy_(torch.randint(0, solver.n_actions, (n,), generator=gen, dtype=torch.int32))
@@ -1347,7 +1348,7 @@ def test_live_state_list_is_built_on_the_device(name, shape, rng_lo, rng_hi, cud
     eng = _native.Engine(cls._D, [len(b) for b in bins], [b.min() for b in bins], [b.max() for b in bins], bins,
                          np.asarray(cls.ACTIONS, np.float32), device=cuda_device.index or 0)
     eng.compile(envs.dynamics_source(name))
-    eng.set_option(6, 1)                                      # keep the list whatever it saves: this test reads it
+    eng.set_option(Option.KEEP_LIVE_LIST, 1)                  # keep the list whatever it saves: this test reads it
     states = oracle.states_from_bins(bins)
     term, _ = H.terminal_mask(name, states)
     n = len(states)
@@ -1378,7 +1379,7 @@ def test_live_state_list_is_built_on_the_device(name, shape, rng_lo, rng_hi, cud
     assert torch.equal(with_list[0].view(torch.int32), plain[0].view(torch.int32))
     assert torch.equal(with_list[1].view(torch.int32), plain[1].view(torch.int32))
     # without the "keep it anyway" option a mask that leaves no lane idle is not listed
-    eng.set_option(6, 0)
+    eng.set_option(Option.KEEP_LIVE_LIST, 0)
     none = torch.zeros(n, dtype=torch.uint8, device=cuda_device)
     none[: (n // 64) * 32] = 1                                 # whole waves terminal: no partly idle wave
     assert eng.prepare_mask(none.data_ptr()) == 0
@@ -1400,7 +1401,7 @@ def test_live_state_list_of_the_full_c5_grid_is_the_sorted_set_of_live_states(cu
     eng = solver._backend.engine
     n = solver.n_states
     count = eng.live_list()
-    assert count == eng.info(16) > 0
+    assert count == eng.info(Info.LIVE_STATES) > 0
     out = torch.empty(count, dtype=torch.int32, device=cuda_device)
     assert eng.live_list(out.data_ptr(), count) == count
     want = torch.nonzero(solver.d_terminal_mask[:n] == 0).reshape(-1).to(torch.int32)

@@ -19,6 +19,7 @@ import pytest
 
 import oracle
 from dynamicprogramming_amd import _native, envs
+from dynamicprogramming_amd._native import Info
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -281,7 +282,7 @@ def _whole_grid_reference(solver, V_user, pol_user, n_eval, cuda_device, begin_e
     eng = _native.Engine(D, solver.grid_shape, solver.bounds_low, solver.bounds_high, solver._bins, solver.action_space,
                          device=cuda_device.index or 0)
     eng.compile(solver._dynamics_cuda_src())
-    assert eng.info(16) == 0                                     # no live-state list on this engine
+    assert eng.info(Info.LIVE_STATES) == 0                       # no live-state list on this engine
     term_user = solver._to_user(solver.d_terminal_mask[:n]) if solver._mask_arg() is not None else None
     tptr = 0 if term_user is None else term_user.data_ptr()
     A, B, P = V_user.clone(), V_user.clone(), pol_user.clone()
@@ -325,11 +326,11 @@ def test_the_bench_path_in_its_memory_order_equals_the_identity_order_engine(nam
     solver.d_policy[:n].copy_(solver._to_memory(pol_user))
     eng = solver._backend.engine
     if name == "double_cartpole":
-        assert eng.info(16) > 0                                  # the live-state list is in use on this grid
+        assert eng.info(Info.LIVE_STATES) > 0                    # the live-state list is in use on this grid
     solver._backend.eval_begin(solver.d_policy, solver._mask_arg())         # as policy_evaluation() brackets its loop
     try:
         if name == "double_cartpole":
-            assert eng.info(17) > 0                              # ... and so is the per-evaluation list
+            assert eng.info(Info.EVAL_LIST_ENTRIES) > 0          # ... and so is the per-evaluation list
         solver._evaluation_sweeps(n_eval, gamma)
     finally:
         solver._backend.eval_end()

@@ -40,6 +40,7 @@ def _worker(rank: int, world: int, port: int, name: str, shape, cfg_kw: dict, ou
     import torch
     import torch.distributed as dist
     from dynamicprogramming_amd import envs
+    from dynamicprogramming_amd._native import CommInfo, Info, Transport
     from dynamicprogramming_amd.solver import CudaPIConfig
     from tests import helpers as H
     torch.set_num_threads(1)
@@ -51,9 +52,10 @@ def _worker(rank: int, world: int, port: int, name: str, shape, cfg_kw: dict, ou
         s = cls(H.env_bins_space(name, shape), cls.ACTIONS, CudaPIConfig(**cfg_kw), device="cuda:0")
         assert s._world == world and s._rank == rank
         eng = s._backend.engine
-        assert eng.comm_info(2) == 3, "the solver is not on the peer-to-peer transport"
+        assert eng.comm_info(CommInfo.TRANSPORT) == Transport.P2P, "the solver is not on the peer-to-peer transport"
         info = dict(s._comm.info)
-        row_exact, fused, live, pairs = eng.comm_info(5), eng.comm_info(6), eng.info(16), eng.comm_info(7)   # before run()
+        row_exact, fused, live, pairs = (eng.comm_info(CommInfo.ROW_EXACT), eng.comm_info(CommInfo.FUSED),    # before run()
+                                         eng.info(Info.LIVE_STATES), eng.comm_info(CommInfo.PAIR_EXACT))
         if env.get("TEST_POISON") == "1":
             # Everything this rank neither owns nor is DELIVERED becomes NaN: both Jacobi buffers outside its shard are
             # poisoned, then its peers deliver the starting values it can reach (one whole-row exchange).  From here on a
@@ -232,7 +234,7 @@ def test_p2p_descriptor_validation(cuda_device):
     mine = eng.p2p_describe(0, 2, bufs)
     with pytest.raises(_native.NativeError, match="not one of pi_p2p_describe"):
         eng.comm_init_p2p(0, 2, [mine, b"\0" * 512])
-    assert eng.comm_info(0) == -1                           # no communicator was installed by the failed attempts
+    assert eng.comm_info(_native.CommInfo.RANK) == -1                   # no communicator was installed by the failed attempts
 
 
 def _worker_vi(rank: int, world: int, port: int, name: str, shape, cfg_kw: dict, out_dir: str, exchange: str) -> None:

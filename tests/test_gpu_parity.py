@@ -17,6 +17,7 @@ import pytest
 
 import oracle
 from dynamicprogramming_amd import _native, envs
+from dynamicprogramming_amd._native import CommInfo, Info, Option, Plan, Transport
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -252,7 +253,8 @@ def test_c2_full_run_matches_oracle(cuda_device):
     solver = envs.make("pendulum", 200, device=cuda_device)
     solver.run()
     # the run compared with the oracle below IS the one-launch path (pi_policy_iteration on the XCD-local kernel): one whole
-    # run launched, no fallback to the round-by-round loop (pi_info 33 / 32, read when run() released the device)
+    # run launched, no fallback to the round-by-round loop (Info.WHOLE_RUNS / Info.XCD_FALLBACKS, read when run() released
+    # the device)
     assert solver._backend.whole_runs == 1 and solver._backend.xcd_fallbacks == 0
     bins = H.env_bins("pendulum", (200, 200))
     lo, hi, gshape, strides = oracle.grid_metadata(bins)
@@ -412,8 +414,8 @@ def test_chunks_per_workgroup_change_speed_not_results(name, shape, cuda_device)
         o_Vn, o_delta = chk.eval_sweep(states, acts, pol, V, term, lo, hi, gshape, strides, gamma, a, b)
         o_pol, o_changed = chk.improve_sweep(states, acts, pol, V, term, lo, hi, gshape, strides, gamma, a, b)
         for cpw in (1, 2, 3, 8, 64):
-            eng.set_option(0, cpw)
-            eng.set_option(1, cpw)
+            eng.set_option(Option.EVAL_CPW, cpw)
+            eng.set_option(Option.IMPROVE_CPW, cpw)
             d_Vn = d_V.clone()
             eng.eval_sweep(d_V.data_ptr(), d_Vn.data_ptr(), d_pol.data_ptr(), d_term.data_ptr(), a, b,
                            gamma, d_delta.data_ptr())
@@ -435,7 +437,7 @@ def test_chunks_per_workgroup_change_speed_not_results(name, shape, cuda_device)
 @pytest.mark.parametrize("name,shape", [("double_pendulum_swingup", (13, 19, 17, 23)), ("cartpole", (11, 21, 19, 17)),
                                          ("double_cartpole", (5, 4, 6, 5, 7, 8))])
 def test_the_strip_schedule_changes_placement_not_results(name, shape, cuda_device, monkeypatch):
-    """Round 6: the strip schedule (every XCD takes its eighth of every period of groups, pi_set_option 7) against the
+    """Round 6: the strip schedule (every XCD takes its eighth of every period of groups, Option.STRIP_STATES) against the
     slab schedule and the oracle — V', residual, policy, changed count on the whole grid and on ragged ranges that start
     inside a period, state ranges and the live-state list alike, for periods that are and are not whole numbers of
     groups; pi_probe_coords walks the same schedule and must write every state of the range exactly once."""
@@ -453,10 +455,10 @@ def test_the_strip_schedule_changes_placement_not_results(name, shape, cuda_devi
         o_Vn, o_delta = chk.eval_sweep(states, acts, pol, V, term, lo, hi, gshape, strides, gamma, a, b)
         o_pol, o_changed = chk.improve_sweep(states, acts, pol, V, term, lo, hi, gshape, strides, gamma, a, b)
         for period, cpw in ((plane, 1), (plane, 2), (256 * 16, 1), (256 * 37 + 100, 3), (0, 2)):
-            eng.set_option(7, period)
-            eng.set_option(0, cpw)
-            eng.set_option(1, cpw)
-            assert eng.info(35) == period
+            eng.set_option(Option.STRIP_STATES, period)
+            eng.set_option(Option.EVAL_CPW, cpw)
+            eng.set_option(Option.IMPROVE_CPW, cpw)
+            assert eng.info(Info.STRIP_STATES) == period
             used += eng.plan_schedule(256, a, b - a, chunks_per_workgroup=cpw)["period"] > 0
             d_Vn = d_V.clone()
             eng.eval_sweep(d_V.data_ptr(), d_Vn.data_ptr(), d_pol.data_ptr(), d_term.data_ptr(), a, b, gamma, d_delta.data_ptr())
@@ -473,15 +475,15 @@ def test_the_strip_schedule_changes_placement_not_results(name, shape, cuda_devi
             H.assert_bits_equal(out.cpu().numpy().reshape(-1, D), states[a:b], "state coordinates")
     assert used >= 5, "the strip schedule was hardly ever taken"
     # batches of sweeps (graphs on this size; the live-state list on grids with terminal states) and the value sweep
-    eng.set_option(0, 1)
-    eng.set_option(1, 1)
+    eng.set_option(Option.EVAL_CPW, 1)
+    eng.set_option(Option.IMPROVE_CPW, 1)
     if term.any():
         monkeypatch.setenv("PI_MI355_LIVE_MIN", "1")
-        eng.set_option(6, 1)
+        eng.set_option(Option.KEEP_LIVE_LIST, 1)
         assert eng.prepare_mask(d_term.data_ptr()) == int((~term).sum())
     res = {}
     for period in (0, plane, 256 * 23):
-        eng.set_option(7, period)
+        eng.set_option(Option.STRIP_STATES, period)
         d_a, d_b = d_V.clone(), d_V.clone()
         eng.eval_sweeps(d_a.data_ptr(), d_b.data_ptr(), d_pol.data_ptr(), d_term.data_ptr(), 0, n, gamma, 7, d_delta.data_ptr())
         d_p2, d_c = d_pol.clone(), d_V.clone()
@@ -516,15 +518,16 @@ def test_small_grids_run_whole_batches_in_lds(name, shape, cuda_device):
     torch = _torch()
     eng, acts, (lo, hi, gshape, strides), states, term, V, pol = _sweep_case(name, shape, cuda_device, seed=11)
     n = len(states)
-    assert eng.info(13) > 0 and eng.info(14) == 1, "this grid should qualify for the resident kernel"
+    assert eng.info(Info.RESIDENT_STATES_PER_THREAD) > 0 and eng.info(Info.RESIDENT_ENABLED) == 1, \
+        "this grid should qualify for the resident kernel"
     gamma = float(np.float32(0.985))
     d_pol, d_term = _dev(pol, cuda_device), _dev(term.astype(np.uint8), cuda_device)
     junk = np.random.default_rng(1).standard_normal(n).astype(np.float32)
     for n_sweeps in (2, 3, 25, 26):
         out = {}
         for resident in (1, 0):
-            eng.set_option(3, resident)
-            eng.set_option(2, 0)                   # the comparison path: plain launches, no graph
+            eng.set_option(Option.RESIDENT, resident)
+            eng.set_option(Option.GRAPHS, 0)       # the comparison path: plain launches, no graph
             A, B = _dev(V, cuda_device), _dev(junk, cuda_device)
             d_delta = torch.full((1,), -1.0, dtype=torch.float32, device=cuda_device)
             eng.eval_sweeps(A.data_ptr(), B.data_ptr(), d_pol.data_ptr(), d_term.data_ptr(), 0, n, gamma,
@@ -539,7 +542,7 @@ def test_small_grids_run_whole_batches_in_lds(name, shape, cuda_device):
     cur = V.copy()
     for _ in range(3):
         cur, o_delta = chk.eval_sweep(states, acts, pol, cur, term, lo, hi, gshape, strides, gamma)
-    eng.set_option(3, 1)
+    eng.set_option(Option.RESIDENT, 1)
     A, B = _dev(V, cuda_device), torch.zeros(n, dtype=torch.float32, device=cuda_device)
     d_delta = torch.zeros(1, dtype=torch.float32, device=cuda_device)
     eng.eval_sweeps(A.data_ptr(), B.data_ptr(), d_pol.data_ptr(), d_term.data_ptr(), 0, n, gamma, 3,
@@ -550,7 +553,7 @@ def test_small_grids_run_whole_batches_in_lds(name, shape, cuda_device):
     a, b = n // 5, n - n // 7
     res = {}
     for resident in (1, 0):
-        eng.set_option(3, resident)
+        eng.set_option(Option.RESIDENT, resident)
         A, B = _dev(V, cuda_device), _dev(junk, cuda_device)
         eng.eval_sweeps(A.data_ptr(), B.data_ptr(), d_pol.data_ptr(), d_term.data_ptr(), a, b, gamma, 4, 0)
         res[resident] = (A.cpu().numpy(), B.cpu().numpy())
@@ -585,9 +588,10 @@ def test_small_grid_policy_evaluation_in_one_launch(name, bins, max_eval, kernel
         assert s._backend.resident == (resident == "1")
         solvers[resident] = s
     a, b = solvers["1"], solvers["0"]
-    assert (a._backend.engine.info(13) > 0) == (kernel == "lds")
-    assert (a._backend.engine.info(19) > 0) == (kernel in ("flow", "xcd")) and (a._backend.engine.info(30) > 0) == (kernel == "xcd")
-    assert b._backend.engine.info(13) == 0 and b._backend.engine.info(19) == 0 and b._backend.engine.info(30) == 0
+    ea, eb = a._backend.engine, b._backend.engine
+    assert (ea.info(Info.RESIDENT_STATES_PER_THREAD) > 0) == (kernel == "lds")
+    assert (ea.info(Info.FLOW_WORKGROUPS) > 0) == (kernel in ("flow", "xcd")) and (ea.info(Info.XCD_ENABLED) > 0) == (kernel == "xcd")
+    assert eb.info(Info.RESIDENT_STATES_PER_THREAD) == 0 and eb.info(Info.FLOW_WORKGROUPS) == 0 and eb.info(Info.XCD_ENABLED) == 0
     # one evaluation from the same start (zero V, zero policy; cartpole has terminal states)
     da, db = a.policy_evaluation(), b.policy_evaluation()
     assert a.stats["sweeps_per_iter"] == b.stats["sweeps_per_iter"]
@@ -659,8 +663,9 @@ def test_whole_run_in_one_launch_through_the_c_abi(name, bins, rounds, max_eval,
         monkeypatch.setenv("PI_MI355_XCD", "0")
     torch = _torch()
     s = envs.make(name, bins, device=cuda_device)
-    assert s._backend.whole_run and (s._backend.engine.info(30) > 0) == (kernel == "xcd")
-    assert (s._backend.engine.info(13) > 0) == (s.n_states <= {2: 12288, 4: 4096, 6: 1024}[len(s.grid_shape)])
+    assert s._backend.whole_run and (s._backend.engine.info(Info.XCD_ENABLED) > 0) == (kernel == "xcd")
+    resident_max = {2: 12288, 4: 4096, 6: 1024}[len(s.grid_shape)]
+    assert (s._backend.engine.info(Info.RESIDENT_STATES_PER_THREAD) > 0) == (s.n_states <= resident_max)
     n = s.n_states
     gamma = float(np.float32(0.97))
     gen = torch.Generator(device="cpu").manual_seed(5)
@@ -672,7 +677,7 @@ def test_whole_run_in_one_launch_through_the_c_abi(name, bins, rounds, max_eval,
     V, pol = V0.clone(), pol0.clone()
     got = s._backend.policy_iteration(V, pol, term, gamma, theta, max_eval, 25, rounds)
     assert got is not None
-    assert s._backend.engine.info(33) == 1 and s._backend.engine.info(32) == 0
+    assert s._backend.engine.info(Info.WHOLE_RUNS) == 1 and s._backend.engine.info(Info.XCD_FALLBACKS) == 0
     # the same loop, call by call, sweep batch by sweep batch
     monkeypatch.setenv("PI_MI355_RESIDENT", "0")
     ref = envs.make(name, bins, device=cuda_device)
@@ -711,7 +716,7 @@ def test_whole_run_in_one_launch_through_the_c_abi(name, bins, rounds, max_eval,
 def test_whole_run_falls_back_when_it_cannot_be_placed(cuda_device, monkeypatch):
     """Every wait of the XCD-local kernel is bounded and nothing is written before a clean end: with a time limit no
     barrier can meet (100 ns) the one-launch run reports failure with V and the policy untouched (and, round 6, is COUNTED:
-    pi_set_option 8), run() goes on round by round, the first evaluation fails the same way — the second failure: the form
+    Option.XCD_RUN_FAILED), run() goes on round by round, the first evaluation fails the same way — the second failure: the form
     is switched off — and the dataflow kernel finishes the run with the results of the sweep-by-sweep loop."""
     monkeypatch.setenv("PI_MI355_XCD_TIMEOUT", "0.0000001")
     cfg = envs.CudaPIConfig(**dict(envs.ENVS["mountain_car"].CONFIG, max_pi_iter=4))
@@ -723,7 +728,8 @@ def test_whole_run_falls_back_when_it_cannot_be_placed(cuda_device, monkeypatch)
     # the LDS-resident whole-run kernel, which cannot fail — still no round-by-round loop
     cfg2 = envs.CudaPIConfig(**dict(envs.ENVS["pendulum"].CONFIG, max_pi_iter=4))
     s2 = envs.make("pendulum", 80, config=cfg2, device=cuda_device)
-    assert s2._backend.whole_run and s2._backend.engine.info(30) > 0 and s2._backend.engine.info(13) > 0
+    assert s2._backend.whole_run and s2._backend.engine.info(Info.XCD_ENABLED) > 0
+    assert s2._backend.engine.info(Info.RESIDENT_STATES_PER_THREAD) > 0
     s2.run()
     assert (s2._backend.whole_runs, s2._backend.xcd_evaluations, s2._backend.xcd_fallbacks) == (2, 0, 1)
     monkeypatch.delenv("PI_MI355_XCD_TIMEOUT")
@@ -763,9 +769,9 @@ def test_small_batches_replay_as_graphs(cuda_device):
     gamma = float(np.float32(0.99))
     d_pol, d_term = _dev(pol, cuda_device), _dev(term.astype(np.uint8), cuda_device)
     results = {}
-    eng.set_option(3, 0)                           # keep the LDS-resident kernel out of this test
+    eng.set_option(Option.RESIDENT, 0)             # keep the LDS-resident kernel out of this test
     for graphs in (1, 0):
-        eng.set_option(2, graphs)
+        eng.set_option(Option.GRAPHS, graphs)
         A, B = _dev(V, cuda_device), torch.zeros(n, dtype=torch.float32, device=cuda_device)
         d_delta = torch.zeros(1, dtype=torch.float32, device=cuda_device)
         deltas = []
@@ -776,9 +782,9 @@ def test_small_batches_replay_as_graphs(cuda_device):
             deltas.append(float(d_delta.item()))
         results[graphs] = (A.cpu().numpy(), B.cpu().numpy(), deltas)
         if graphs:
-            assert eng.info(9) == 2                # (A,B) and (B,A)
+            assert eng.info(Info.CACHED_GRAPHS) == 2  # (A,B) and (B,A)
         else:
-            assert eng.info(10) == 0
+            assert eng.info(Info.GRAPHS_ENABLED) == 0
     H.assert_bits_equal(results[1][0], results[0][0], "newest iterate, graph vs eager")
     H.assert_bits_equal(results[1][1], results[0][1], "previous iterate, graph vs eager")
     assert results[1][2] == results[0][2]
@@ -800,7 +806,7 @@ def test_interpolation_division_guard_edges(cuda_device):
     torch = _torch()
     name, shape = "cartpole", (9, 7, 11, 5)
     eng, bins, acts = _engine(name, shape, cuda_device)
-    assert [eng.info(20 + d) for d in range(4)] == [1, 1, 1, 1]
+    assert [eng.info(Info.RECIPROCAL_DIV + d) for d in range(4)] == [1, 1, 1, 1]
     lo, hi, gshape, strides = oracle.grid_metadata(bins)
     rng = np.random.default_rng(5)
     pts = H.sample_states(rng, bins, 4096)
@@ -952,10 +958,11 @@ def test_rccl_entry_points_world_1(cuda_device):
     uid = _native.comm_unique_id()
     assert len(uid) == 128
     eng.comm_init(0, 1, uid)
-    assert (eng.comm_info(0), eng.comm_info(1), eng.comm_info(2)) == (0, 1, 1)
+    assert (eng.comm_info(CommInfo.RANK), eng.comm_info(CommInfo.WORLD)) == (0, 1)
+    assert eng.comm_info(CommInfo.TRANSPORT) == Transport.RCCL
     d_pol, d_term = _dev(pol, cuda_device), _dev(term.astype(np.uint8), cuda_device)
-    info = eng.exchange_plan(d_term.data_ptr(), n, 0, True)
-    assert info["recv_elems"] == 0 and eng.comm_info(3) in (1, 2)
+    info = eng.exchange_plan(d_term.data_ptr(), n, Plan.NONE, True)
+    assert info["recv_elems"] == 0 and eng.comm_info(CommInfo.PLAN) in (Plan.ALLGATHER, Plan.HALO)
     A, B = _dev(V, cuda_device), torch.zeros(n, dtype=torch.float32, device=cuda_device)
     A2, B2 = A.clone(), B.clone()
     d1 = torch.zeros(1, dtype=torch.float32, device=cuda_device)
@@ -984,7 +991,7 @@ def test_rccl_entry_points_world_1(cuda_device):
     eng.close()
 
 
-# ── memory order of the dimensions (pi_set_option 4 / solver.MEMORY_ORDER) ───────────────────────────────
+# ── memory order of the dimensions (Option.MEMORY_ORDER / solver.MEMORY_ORDER) ───────────────────────────────
 ORDER_CASES = [("pendulum", (23, 17), (1, 0)),
                ("cartpole_swingup", (9, 7, 11, 5), (0, 2, 1, 3)),
                ("double_pendulum_swingup", (8, 9, 7, 10), (2, 0, 3, 1)),
@@ -1194,7 +1201,7 @@ def test_one_launch_evaluation_with_any_look_interval(name, bins, xcd, interval,
     monkeypatch.setenv("PI_MI355_XCD", xcd)
     s = envs.make(name, bins, device=cuda_device)
     eng = s._backend.engine
-    assert s._backend.resident and (eng.info(30) > 0) == ((name, bins, xcd) == ("pendulum", 200, "1"))
+    assert s._backend.resident and (eng.info(Info.XCD_ENABLED) > 0) == ((name, bins, xcd) == ("pendulum", 200, "1"))
     n = s.n_states
     gamma = float(np.float32(0.9))
     gen = torch.Generator(device="cpu").manual_seed(17)
@@ -1235,7 +1242,7 @@ def test_one_launch_evaluation_gives_up_loudly_instead_of_hanging(cuda_device, m
     torch = _torch()
     monkeypatch.setenv("PI_MI355_XCD", "0")              # the XCD-local kernel has its own fallback: the dataflow kernel is the one that gives up
     s = envs.make("pendulum", 200, device=cuda_device)
-    assert s._backend.engine.info(19) > 0 and s._backend.engine.info(30) == 0
+    assert s._backend.engine.info(Info.FLOW_WORKGROUPS) > 0 and s._backend.engine.info(Info.XCD_ENABLED) == 0
     n = s.n_states
     gen = torch.Generator(device="cpu").manual_seed(23)
     V0 = torch.randn(n, generator=gen, dtype=torch.float32).to(cuda_device)

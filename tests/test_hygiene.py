@@ -179,3 +179,15 @@ def test_tools_parse_and_name_only_existing_entry_points():
         for node in ast.walk(tree):
             if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id == "_native":
                 assert hasattr(_native, node.attr), f"{path.name}: _native.{node.attr} does not exist"
+
+
+def test_selector_codes_are_named_not_numbered():
+    """pi_info / pi_set_option / pi_comm_info selectors are spelled with the enums of _native.py (Info, Option,
+    CommInfo): a bare number that names the wrong code does not fail, it quietly reads another one."""
+    pat = re.compile(r"\.(?:info|set_option|comm_info)\(\s*[-+]?\d|\bpi_(?:info|set_option|comm_info)\([^,()]*,\s*[-+]?\d")
+    offenders = []
+    for d in ("dynamicprogramming_amd", "tests", "tools"):
+        for p in sorted((ROOT / d).rglob("*.py")):
+            text = p.read_text()
+            offenders += [f"{p.relative_to(ROOT)}:{text.count(chr(10), 0, m.start()) + 1}" for m in pat.finditer(text)]
+    assert not offenders, offenders

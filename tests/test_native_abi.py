@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from dynamicprogramming_amd import _native, envs
+from dynamicprogramming_amd._native import Info, Option
 from tests import helpers as H
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -41,6 +42,56 @@ def test_no_torch_types_in_the_abi():
     assert "at::" not in text and "c10::" not in text
 
 
+# C enum of include/pi_mi355.h -> (its mirror in _native.py, the prefix the C names carry)
+SELECTOR_ENUMS = {
+    "pi_info_code": (_native.Info, "PI_INFO_"),
+    "pi_option_code": (_native.Option, "PI_OPTION_"),
+    "pi_xcd_failure": (_native.XcdFailure, "PI_XCD_FAILURE_"),
+    "pi_comm_info_code": (_native.CommInfo, "PI_COMM_INFO_"),
+    "pi_transport": (_native.Transport, "PI_TRANSPORT_"),
+    "pi_plan": (_native.Plan, "PI_PLAN_"),
+    "pi_reach_unit": (_native.ReachUnits, "PI_REACH_"),
+}
+
+
+def declared_enums():
+    """{enum tag: {enumerator: value}} of every enum include/pi_mi355.h declares."""
+    text = (ROOT / "include" / "pi_mi355.h").read_text()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return {tag: {name: int(value) for name, value in re.findall(r"\b(PI_\w+)\s*=\s*(\d+)", body)}
+            for tag, body in re.findall(r"\benum\s+(\w+)\s*\{([^}]*)\}", text)}
+
+
+def test_python_selector_enums_mirror_the_header():
+    declared = declared_enums()
+    assert set(declared) == set(SELECTOR_ENUMS)
+    for tag, members in declared.items():
+        py, prefix = SELECTOR_ENUMS[tag]
+        assert all(name.startswith(prefix) for name in members), tag
+        assert {name[len(prefix):]: value for name, value in members.items()} == \
+            {m.name: m.value for m in py}, f"{py.__name__} differs from enum {tag}"
+
+
+def test_every_info_code_answers_and_no_other_does(tmp_path):
+    name = "cartpole_swingup"
+    eng = _host_engine(name, (9, 7, 11, 5))
+    eng.compile(envs.dynamics_source(name), cache_dir=tmp_path)
+    unloaded = {Info.EVAL_VGPRS, Info.IMPROVE_VGPRS}          # -1 until a device loads the kernels
+    for code in Info:
+        assert (eng.info(code) == -1) == (code in unloaded), code.name
+    reciprocal = {Info.RECIPROCAL_DIV + d for d in range(eng.D)}
+    for code in reciprocal:
+        assert eng.info(code) in (0, 1)
+    known = set(Info) | reciprocal
+    assert {29, 36} <= set(range(-2, 64)) - known
+    for code in set(range(-2, 64)) - known:
+        assert eng.info(code) == -1, code
+    for code in (-1, max(Option) + 1, 99):
+        with pytest.raises(_native.NativeError, match="unknown option"):
+            eng.set_option(code, 1)
+    eng.close()
+
+
 def _host_engine(name, shape):
     cls = envs.ENVS[name]
     bins = H.env_bins(name, shape)
@@ -53,13 +104,13 @@ def test_every_env_compiles_for_gfx950_without_a_gpu(name, tmp_path):
     shape = {2: (24, 17), 4: (9, 7, 11, 5), 6: (5, 4, 6, 4, 5, 4)}[envs.ENVS[name]._D]
     eng = _host_engine(name, shape)
     eng.compile(envs.dynamics_source(name), cache_dir=tmp_path)
-    assert eng.info(7) == 0                       # compiled, not cached
+    assert eng.info(Info.CACHE_HIT) == 0          # compiled, not cached
     objs = list(tmp_path.glob("pi_*.hsaco"))
     assert len(objs) == 1 and objs[0].stat().st_size > 4096
     assert objs[0].read_bytes()[:4] == b"\x7fELF"
     eng2 = _host_engine(name, shape)
     eng2.compile(envs.dynamics_source(name), cache_dir=tmp_path)
-    assert eng2.info(7) == 1                      # second handle: served from the cache
+    assert eng2.info(Info.CACHE_HIT) == 1         # second handle: served from the cache
     src = eng.kernel_source(envs.dynamics_source(name))
     assert "pi_eval_sweep_kernel" in src and "step_dynamics" in src and "#define sinf pi_sinf" in src
     eng.close()
@@ -109,7 +160,7 @@ def test_the_references_literal_plugin_strings_compile_unchanged(name, tmp_path)
         shape = (80,) * 4
     eng = _host_engine(name, shape)
     eng.compile(text, cache_dir=tmp_path)                       # hipRTC, --offload-arch=gfx950
-    assert eng.info(7) == 0
+    assert eng.info(Info.CACHE_HIT) == 0
     (obj,) = list(tmp_path.glob("pi_*.hsaco"))
     assert obj.read_bytes()[:4] == b"\x7fELF"
     # same code path as the shipped string: the translation unit differs only in the plugin text
@@ -158,7 +209,7 @@ def test_grids_beyond_32_bit_byte_offsets_compile(tmp_path):
     eng = _host_engine("double_cartpole", (32,) * 6)
     assert eng.n_states == 1 << 30
     eng.compile(envs.dynamics_source("double_cartpole"), cache_dir=tmp_path)
-    assert eng.info(7) == 0 and len(list(tmp_path.glob("pi_*.hsaco"))) == 1
+    assert eng.info(Info.CACHE_HIT) == 0 and len(list(tmp_path.glob("pi_*.hsaco"))) == 1
     eng.close()
 
 
@@ -168,7 +219,7 @@ def test_checked_build_compiles_for_gfx950(tmp_path, monkeypatch):
     monkeypatch.setenv("PI_MI355_DEBUG", "1")
     for name, shape in (("pendulum", (24, 17)), ("cartpole_swingup", (9, 7, 11, 5)), ("double_cartpole", (5, 4, 6, 4, 5, 4))):
         eng = _host_engine(name, shape)
-        assert eng.info(15) == 1
+        assert eng.info(Info.DEBUG_CHECKS) == 1
         eng.compile(envs.dynamics_source(name), cache_dir=tmp_path)
         src = eng.kernel_source(envs.dynamics_source(name))
         assert "#define PI_DEBUG_BOUNDS 1" in src
@@ -177,7 +228,7 @@ def test_checked_build_compiles_for_gfx950(tmp_path, monkeypatch):
         eng.close()
     monkeypatch.delenv("PI_MI355_DEBUG")
     eng = _host_engine("pendulum", (24, 17))
-    assert eng.info(15) == 0 and "#define PI_DEBUG_BOUNDS 1" not in eng.kernel_source(envs.dynamics_source("pendulum"))
+    assert eng.info(Info.DEBUG_CHECKS) == 0 and "#define PI_DEBUG_BOUNDS 1" not in eng.kernel_source(envs.dynamics_source("pendulum"))
     eng.close()
 
 
@@ -237,14 +288,14 @@ def _markstein_f32(a, span):
 def test_reciprocal_division_is_enabled_and_exact_for_every_env_divisor(name, monkeypatch):
     """pi_create proves the reciprocal-multiply division per divisor by enumerating all 2^23
     significands (C++); this checks the verdict independently: the reference grids' divisors are
-    accepted (pi_info 20 + d), PI_MI355_IEEE_DIV switches the path off, the generated source carries
+    accepted (Info.RECIPROCAL_DIV + d), PI_MI355_IEEE_DIV switches the path off, the generated source carries
     the span and its reciprocal as exact hex-float literals, and a numpy restatement of the sequence
     equals IEEE division on a million dividends spread over the guarded exponent range."""
     cls = envs.ENVS[name]
     bins = [np.asarray(b, np.float32) for b in cls.bins_space(cls.DEFAULT_BINS).values()]
     eng = _native.Engine(cls._D, [len(b) for b in bins], [b.min() for b in bins], [b.max() for b in bins],
                          bins, cls.ACTIONS, device=-1)
-    assert [eng.info(20 + d) for d in range(cls._D)] == [1] * cls._D
+    assert [eng.info(Info.RECIPROCAL_DIV + d) for d in range(cls._D)] == [1] * cls._D
     src = eng.kernel_source(envs.dynamics_source(name))
 
     def literals(macro):
@@ -267,7 +318,7 @@ def test_reciprocal_division_is_enabled_and_exact_for_every_env_divisor(name, mo
     monkeypatch.setenv("PI_MI355_IEEE_DIV", "1")
     off = _native.Engine(cls._D, [len(b) for b in bins], [b.min() for b in bins], [b.max() for b in bins],
                          bins, cls.ACTIONS, device=-1)
-    assert [off.info(20 + d) for d in range(cls._D)] == [0] * cls._D
+    assert [off.info(Info.RECIPROCAL_DIV + d) for d in range(cls._D)] == [0] * cls._D
     assert "PI_FASTDIV_INIT {" + ",".join(["0"] * cls._D) + "}" in off.kernel_source(envs.dynamics_source(name))
     off.close()
 
@@ -278,7 +329,7 @@ def test_reciprocal_division_refuses_out_of_range_divisors():
     bins = [np.linspace(0, 1e-12, 5, dtype=np.float32), np.linspace(-1.0, 1.0, 7, dtype=np.float32)]
     eng = _native.Engine(2, [5, 7], [b.min() for b in bins], [b.max() for b in bins], bins,
                          np.array([0.0], np.float32), device=-1)
-    assert [eng.info(20), eng.info(21)] == [0, 1]
+    assert [eng.info(Info.RECIPROCAL_DIV + d) for d in range(2)] == [0, 1]
     eng.close()
 
 
@@ -494,7 +545,7 @@ def test_p2p_bootstrap_failure_reaches_every_rank():
 def test_fused_exchange_kernels_build_and_keep_the_register_budget(tmp_path):
     """The handle's second module (csrc/pi_push_kernels.hip appended to the sweep translation unit: the swept-first
     kernel that delivers its rows itself, and the pair-level reach probe) builds for gfx950 in the sharded memory
-    orders through the library (pi_set_option 5 on a host-only handle) and through hipcc, where pi_eval_push_kernel
+    orders through the library (Option.BUILD_PUSH on a host-only handle) and through hipcc, where pi_eval_push_kernel
     must stay inside the budget of the kernel it replaces in a sharded sweep: 64 VGPRs and 80 SGPRs on the 80^4 grid
     (two 1 024-thread workgroups per CU), no scratch anywhere."""
     import subprocess
@@ -508,7 +559,7 @@ def test_fused_exchange_kernels_build_and_keep_the_register_budget(tmp_path):
         dyn = envs.dynamics_source(name)
         eng.compile(dyn, cache_dir=tmp_path)
         before = len(list(tmp_path.glob("pi_*.hsaco")))
-        eng.set_option(5, 1)                                  # second module -> cache
+        eng.set_option(Option.BUILD_PUSH, 1)                  # second module -> cache
         assert len(list(tmp_path.glob("pi_*.hsaco"))) == before + 1
         src = tmp_path / f"{name}_push.hip"
         src.write_text(eng.kernel_source(dyn) + push)
@@ -536,5 +587,5 @@ def test_fused_exchange_kernels_build_and_keep_the_register_budget(tmp_path):
     # before pi_compile there is nothing to append to
     eng = _host_engine("pendulum", (24, 17))
     with pytest.raises(_native.NativeError, match="pi_compile has not run"):
-        eng.set_option(5, 1)
+        eng.set_option(Option.BUILD_PUSH, 1)
     eng.close()

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from dynamicprogramming_amd import _native, envs
+from dynamicprogramming_amd._native import Info, Option
 from tests import helpers as H
 
 
@@ -32,10 +33,10 @@ def _check_cover(sched, block, count):
 
 def test_strips_on_the_headline_grid_are_a_plane_of_the_slowest_dimension_when_asked_for():
     eng = _engine("double_pendulum_swingup", (80, 80, 80, 80), order=(0, 2, 1, 3))
-    eng.set_option(7, -1)
-    assert eng.info(35) == 0                           # the library's choice for 4-D grids: slab (measured slower with strips)
-    eng.set_option(7, 80 ** 3)
-    assert eng.info(35) == 80 ** 3
+    eng.set_option(Option.STRIP_STATES, -1)
+    assert eng.info(Info.STRIP_STATES) == 0            # the library's choice for 4-D grids: slab (measured slower with strips)
+    eng.set_option(Option.STRIP_STATES, 80 ** 3)
+    assert eng.info(Info.STRIP_STATES) == 80 ** 3
     s = eng.plan_schedule(1024, 0, 80 ** 4, chunks_per_workgroup=2)
     assert (s["period"], s["phase"]) == (250, 0) and (s["grid_x"], s["grid_y"]) == (32 * 8, 80)
     g = _check_cover(s, 1024, 80 ** 4)
@@ -46,7 +47,7 @@ def test_strips_on_the_headline_grid_are_a_plane_of_the_slowest_dimension_when_a
         assert set(plane[mine]) == set(range(80))
         assert pos[mine].min() >= x * 250 // 8 and pos[mine].max() <= ((x + 1) * 250 + 7) // 8
         assert abs(int(mine.sum()) - 80 * 250 // 8) <= 1
-    eng.set_option(7, 0)
+    eng.set_option(Option.STRIP_STATES, 0)
     s0 = eng.plan_schedule(1024, 0, 80 ** 4, chunks_per_workgroup=2)
     assert s0["period"] == 0 and (s0["grid_x"], s0["grid_y"]) == (20000, 1)
     _check_cover(s0, 1024, 80 ** 4)
@@ -55,8 +56,8 @@ def test_strips_on_the_headline_grid_are_a_plane_of_the_slowest_dimension_when_a
 
 def test_the_librarys_choice_on_big_6d_grids_is_a_few_sub_planes():
     eng = _engine("double_cartpole_swingup", (25,) * 6, order=(4, 5, 2, 3, 0, 1))
-    eng.set_option(7, -1)
-    assert eng.info(35) == 5 * 25 ** 4                 # ~2^21 states, whole (i0, i1) sub-planes
+    eng.set_option(Option.STRIP_STATES, -1)
+    assert eng.info(Info.STRIP_STATES) == 5 * 25 ** 4  # ~2^21 states, whole (i0, i1) sub-planes
     s = eng.plan_schedule(256, 0, 25 ** 6, chunks_per_workgroup=4)
     assert s["period"] == round(5 * 25 ** 4 / 1024) and s["grid_y"] == -(-(-(-25 ** 6 // 1024)) // s["period"])
     _check_cover(s, 256, 25 ** 6)
@@ -72,8 +73,8 @@ def test_small_and_2d_grids_keep_the_slab_schedule():
     for name, shape in (("pendulum", (200, 200)), ("cartpole_swingup", (50, 50, 50, 50)), ("double_cartpole", (7,) * 6),
                         ("double_pendulum_swingup", (80, 80, 80, 80))):
         eng = _engine(name, shape)
-        eng.set_option(7, -1)
-        assert eng.info(35) == 0, (name, shape)
+        eng.set_option(Option.STRIP_STATES, -1)
+        assert eng.info(Info.STRIP_STATES) == 0, (name, shape)
         eng.close()
 
 
@@ -81,12 +82,12 @@ def test_small_and_2d_grids_keep_the_slab_schedule():
 def test_every_group_is_taken_exactly_once_whatever_the_period_and_the_range(seed):
     rng = np.random.default_rng(seed)
     eng = _engine("cartpole", (31, 23, 29, 19))
-    n = eng.info(0)
+    n = eng.info(Info.N_STATES)
     for _ in range(40):
         block = int(rng.choice([64, 256, 512, 1024]))
         cpw = int(rng.integers(1, 5))
         period_states = int(rng.integers(block * cpw * 16, n // 2))
-        eng.set_option(7, period_states)
+        eng.set_option(Option.STRIP_STATES, period_states)
         first = int(rng.integers(0, n // 2))
         if rng.random() < 0.5:
             first -= first % (block * cpw)             # ranges that start on a group boundary and ranges that do not
@@ -100,11 +101,11 @@ def test_every_group_is_taken_exactly_once_whatever_the_period_and_the_range(see
 
 def test_a_period_of_too_few_groups_and_a_range_inside_one_period_fall_back_to_the_slab():
     eng = _engine("cartpole", (31, 23, 29, 19))
-    eng.set_option(7, 1024 * 8)                       # 8 groups of 1 024: under the 16-group minimum
-    assert eng.plan_schedule(1024, 0, eng.info(0))["period"] == 0
-    eng.set_option(7, 1024 * 64)
-    assert eng.plan_schedule(1024, 0, eng.info(0))["period"] == 64
+    eng.set_option(Option.STRIP_STATES, 1024 * 8)     # 8 groups of 1 024: under the 16-group minimum
+    assert eng.plan_schedule(1024, 0, eng.info(Info.N_STATES))["period"] == 0
+    eng.set_option(Option.STRIP_STATES, 1024 * 64)
+    assert eng.plan_schedule(1024, 0, eng.info(Info.N_STATES))["period"] == 64
     assert eng.plan_schedule(1024, 0, 1024 * 40)["period"] == 0          # the whole range is less than one period
     with pytest.raises(RuntimeError):
-        eng.set_option(7, eng.info(0) + 1)
+        eng.set_option(Option.STRIP_STATES, eng.info(Info.N_STATES) + 1)
     eng.close()

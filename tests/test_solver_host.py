@@ -11,6 +11,7 @@ import pytest
 
 import oracle
 from dynamicprogramming_amd import envs
+from dynamicprogramming_amd._native import Info
 from dynamicprogramming_amd.solver import CudaPIConfig, CudaPolicyIteration2D
 from tests import helpers as H
 
@@ -477,7 +478,7 @@ def test_memory_order_index_algebra(grid):
         digits_mem = np.stack(np.unravel_index(np.arange(n), mshape), axis=1)        # memory coordinates of slot m
         for k, d in enumerate(eng.order):
             assert np.array_equal(digits_mem[:, k], digits_user[:, d])
-        assert eng.info(18) == sum(d << (3 * k) for k, d in enumerate(eng.order))
+        assert eng.info(Info.MEMORY_ORDER) == sum(d << (3 * k) for k, d in enumerate(eng.order))
     finally:
         eng.close()
 

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from dynamicprogramming_amd import envs
+from dynamicprogramming_amd._native import Info
 
 AB_KERNELS = r'''
 // ---- experiment: successor records (tools/ab_eval_replay.py) ----
@@ -171,7 +172,7 @@ def main():
 
     reps = 20 if n < (1 << 27) else 5
     out = {"env": env, "bins": bins, "states": n, "memory_order": list(eng.order), "A_product_ms": timed(run_a, reps),
-           "product_geometry": [eng.info(11), eng.info(3)], "B": []}
+           "product_geometry": [eng.info(Info.EVAL_BLOCK), eng.info(Info.EVAL_CPW)], "B": []}
     recA = torch.empty((n, 4), dtype=torch.float32, device="cuda:0")
     recB = torch.empty((n if D == 6 else 1, 4), dtype=torch.float32, device="cuda:0")
     recR = torch.empty(n if D == 4 else 1, dtype=torch.float32, device="cuda:0")

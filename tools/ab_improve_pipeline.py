@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from dynamicprogramming_amd import envs
+from dynamicprogramming_amd._native import Info
 
 AB_KERNEL = r'''
 // ---- experiment: action loop pipelined by one action (tools/ab_improve_pipeline.py) ----
@@ -155,7 +156,7 @@ def main():
     torch.cuda.synchronize()
     ref_policy, ref_changed = pol_a.clone(), int(ch_a.item())
     out = {"env": env, "bins": bins, "states": n, "actions": nA, "A_product_ms": timed(run_a, 5),
-           "product_geometry": [eng.info(12), eng.info(8)], "B": []}
+           "product_geometry": [eng.info(Info.IMPROVE_BLOCK), eng.info(Info.IMPROVE_CPW)], "B": []}
     src_text = eng.kernel_source(envs.dynamics_source(env))
     hip = ctypes.CDLL("libamdhip64.so")
     tmp = Path(tempfile.mkdtemp(prefix="ab_pipe_"))

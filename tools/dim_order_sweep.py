@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from dynamicprogramming_amd import envs
+from dynamicprogramming_amd._native import Info
 from dynamicprogramming_amd.solver import CudaPolicyIteration2D, CudaPolicyIteration4D, CudaPolicyIteration6D
 
 env, bins = sys.argv[1], int(sys.argv[2])
@@ -110,7 +111,8 @@ for perm in perms:
     V = s.d_value_function[:n]
     row = {"perm": list(perm), "dims": [keys[d] for d in perm], "eval_ms": min(ms), "improve_ms": imp,
            "checksum_sum": float(V.double().sum().item()), "checksum_max": float(V.max().item()),
-           "residual": float(s._d_delta.item()), "changed": int(s._d_changed.item()), "live_list": s._backend.engine.info(16)}
+           "residual": float(s._d_delta.item()), "changed": int(s._d_changed.item()),
+           "live_list": s._backend.engine.info(Info.LIVE_STATES)}
     out.append(row)
     print(json.dumps(row), flush=True)
     s._backend.close()

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from dynamicprogramming_amd import _native
+from dynamicprogramming_amd._native import Info
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--shapes", default="640,40,40,40;80,80,80,80;25,25,25,25,25,25")
@@ -52,7 +53,8 @@ for spec in args.shapes.split(";"):
         ms.append(e0.elapsed_time(e1))
         V, Vn = Vn, V
     out.append({"shape": shape, "states": n, "known_read_bytes": 8 * n, "known_write_bytes": 4 * n,
-                "ms_per_sweep": min(ms[1:]), "threads_per_workgroup": eng.info(11), "chunks_per_workgroup": eng.info(3)})
+                "ms_per_sweep": min(ms[1:]), "threads_per_workgroup": eng.info(Info.EVAL_BLOCK),
+                "chunks_per_workgroup": eng.info(Info.EVAL_CPW)})
     eng.close()
     del V, Vn, pol
 print(json.dumps({"identity_sweeps": out, "sweeps_each": args.sweeps}))

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from dynamicprogramming_amd import envs
+from dynamicprogramming_amd._native import Info
 
 cases = [("pendulum", 200), ("mountain_car", 200), ("double_pendulum_swingup", 15), ("cartpole", 15)]
 if len(sys.argv) > 1:
@@ -25,8 +26,8 @@ for name, bins in cases:
         best = None
         for rep in range(3):
             s = envs.make(name, bins, device="cuda:0")
-            kind = {True: "flow" if s._backend.engine.info(19) else "lds", False: "graphs"}[bool(s._backend.resident)]
-            if s._backend.engine.info(30) > 0:
+            kind = {True: "flow" if s._backend.engine.info(Info.FLOW_WORKGROUPS) else "lds", False: "graphs"}[bool(s._backend.resident)]
+            if s._backend.engine.info(Info.XCD_ENABLED) > 0:
                 kind = "xcd"
             elif xcd == "1":
                 continue                                   # this grid has no XCD-local kernel: nothing to time

@@ -25,6 +25,7 @@ import torch
 
 from dynamicprogramming_amd import envs
 from dynamicprogramming_amd import transport as T
+from dynamicprogramming_amd._native import CommInfo, Info
 
 env, bins, world = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
 sweeps = int(sys.argv[4]) if len(sys.argv) > 4 else 3
@@ -138,8 +139,8 @@ for o in out:
         later[kind] = (min(batches(9) for _ in range(2)) - min(batches(1) for _ in range(2))) / 8.0
     o["first_ms"], o["interior_ms"] = parts[0], parts[1]
     o["first_later_sweeps_ms"], o["interior_later_sweeps_ms"] = later[0], later[1]
-    o["live_states_listed"] = eng.info(16)
-    o["row_exact"] = bool(eng.comm_info(5) == 1)
+    o["live_states_listed"] = eng.info(Info.LIVE_STATES)
+    o["row_exact"] = bool(eng.comm_info(CommInfo.ROW_EXACT) == 1)
     o["first_launches"] = sum(1 for k, _, _ in o["ranges"] if k == 0)
     o["interior_launches"] = sum(1 for k, _, _ in o["ranges"] if k == 1)
     o["first_states"] = sum(b - a for k, a, b in o["ranges"] if k == 0)

@@ -54,7 +54,7 @@ int main(int argc, char** argv) {
         CHECK(make(2, tiny, 2) == nullptr);
         std::vector<int32_t> huge(6, 40);
         CHECK(make(6, huge, 1) == nullptr);
-        CHECK(pi_info(nullptr, 0) == -1 || std::strlen(pi_last_error()) > 0);
+        CHECK(pi_info(nullptr, PI_INFO_N_STATES) == -1 || std::strlen(pi_last_error()) > 0);
     }
     // 2-D and 4-D handles: source generation, compilation for gfx950, cache round trip, options, info
     for (int D : {2, 4}) {
@@ -73,8 +73,10 @@ int main(int argc, char** argv) {
         CHECK(pi_compile(h, "__device__ void step_dynamics(float a) { nonsense; }", cache, log.data(), log.size()) != 0);
         CHECK(std::strlen(log.data()) > 0);
         CHECK(pi_compile(h, plugin, cache, nullptr, 0) == 0);          // no log buffer
-        CHECK(pi_info(h, 0) == (D == 2 ? 231 : 840) && pi_info(h, 1) == 3 && pi_info(h, 2) == D);
-        CHECK(pi_set_option(h, 0, 4) == 0 && pi_info(h, 3) == 4 && pi_set_option(h, 0, 0) != 0 && pi_set_option(h, 99, 1) != 0);
+        CHECK(pi_info(h, PI_INFO_N_STATES) == (D == 2 ? 231 : 840) && pi_info(h, PI_INFO_N_ACTIONS) == 3 &&
+              pi_info(h, PI_INFO_DIMS) == D);
+        CHECK(pi_set_option(h, PI_OPTION_EVAL_CPW, 4) == 0 && pi_info(h, PI_INFO_EVAL_CPW) == 4 &&
+              pi_set_option(h, PI_OPTION_EVAL_CPW, 0) != 0 && pi_set_option(h, 99, 1) != 0);
         float dummy = 0.0f;
         CHECK(pi_eval_sweep(h, &dummy, &dummy, nullptr, nullptr, 0, 1, 0.9f, nullptr, nullptr) != 0);   // host-only: refuses
         uint32_t rep[4];
@@ -142,7 +144,7 @@ int main(int argc, char** argv) {
         CHECK(pi_p2p_describe(nullptr, 0, 2, bufs, sizes, 1, desc) != 0);
         CHECK(pi_comm_init_p2p(h, 0, 2, desc, cache) != 0);              // nothing was described
         CHECK(pi_comm_init_p2p(h, 0, 2, nullptr, cache) != 0);
-        CHECK(pi_comm_info(h, 2) == -1);
+        CHECK(pi_comm_info(h, PI_COMM_INFO_TRANSPORT) == -1);
         pi_destroy(h);
     }
     pi_destroy(nullptr);

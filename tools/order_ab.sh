@@ -5,7 +5,7 @@
 # path (envs.make -> solver -> C ABI) on the bench state through tools/eval_states.py, with the live-state lists, the
 # per-evaluation lists and the strip schedule as a real run has them.  One process per order, the list run twice so
 # that box drift shows.  One line per run into OUT (jsonl), a table on stdout.  How MEMORY_ORDER of an env class is chosen
-# since round 6 (tools/dim_order_sweep.py permutes the ENV instead and predates pi_set_option 4).
+# since round 6 (tools/dim_order_sweep.py permutes the ENV instead and predates PI_OPTION_MEMORY_ORDER).
 O=$1; E=$2; B=$3; S=$4; I=$5; shift 5
 mkdir -p "$(dirname "$O")"
 for rep in 1 2; do

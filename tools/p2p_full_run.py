@@ -27,6 +27,7 @@ def worker(rank, world, port, name, bins, out):
     import torch
     import torch.distributed as dist
     from dynamicprogramming_amd import envs
+    from dynamicprogramming_amd._native import CommInfo
     if rank == 0:                                  # progress (one line per policy evaluation) on stderr
         logging.basicConfig(level=logging.INFO, stream=sys.stderr, format="%(asctime)s %(message)s")
     dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world,
@@ -34,7 +35,8 @@ def worker(rank, world, port, name, bins, out):
     try:
         s = envs.make(name, bins, device="cuda:0")
         eng = s._backend.engine
-        info = {"transport": eng.comm_info(2), "plan": dict(s._comm.info), "row_exact": eng.comm_info(5), "fused": eng.comm_info(6),
+        info = {"transport": eng.comm_info(CommInfo.TRANSPORT), "plan": dict(s._comm.info),
+                "row_exact": eng.comm_info(CommInfo.ROW_EXACT), "fused": eng.comm_info(CommInfo.FUSED),
                 "memory_order": list(eng.order)}
         torch.cuda.synchronize()
         dist.barrier()

@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from dynamicprogramming_amd import envs
+from dynamicprogramming_amd._native import Info
 
 PT_KERNELS = r'''
 // ---- diagnostic copies of pi_eval_sweep_kernel (tools/phase_timeline.py) ----
@@ -616,7 +617,7 @@ def main():
                              cls.ACTIONS, device=-1)
         text = eng.kernel_source(envs.dynamics_source(args.env))
         tmp = Path(tempfile.mkdtemp(prefix="pt_"))
-        for blk in sorted({eng.info(11)} | {int(p.split("x")[0]) for p in args.persistent.split(",") if p}):
+        for blk in sorted({eng.info(Info.EVAL_BLOCK)} | {int(p.split("x")[0]) for p in args.persistent.split(",") if p}):
             for tr_on in (0, 1):
                 print(blk, "trace" if tr_on else "plain", json.dumps(build(text, tr_on, blk, tmp, f"c{blk}_{tr_on}")[1]))
         fits = [affine_fit(b) for b in tables]
@@ -632,7 +633,7 @@ def main():
                 d += ("#define PT_AFFINE 1\n#define PT_AFF_A_INIT {" + ",".join(float(f[0]).hex() for f in fits) + "}\n"
                       "#define PT_AFF_B_INIT {" + ",".join(float(f[1]).hex() for f in fits) + "}\n")
             for tr_on in (0, 1):
-                print(v, tr_on, json.dumps(build(text, tr_on, eng.info(11), tmp, f"v{v}{tr_on}", d)[1]["pt_eval_kernel"]))
+                print(v, tr_on, json.dumps(build(text, tr_on, eng.info(Info.EVAL_BLOCK), tmp, f"v{v}{tr_on}", d)[1]["pt_eval_kernel"]))
         return
     solver = envs.make(args.env, args.bins, device="cuda:0")
     eng = solver._backend.engine
@@ -651,7 +652,7 @@ def main():
             solver._improvement_sweep(gamma)
     V = solver.d_value_function
     pol = solver.d_policy
-    block, cpw = eng.info(11), eng.info(3)
+    block, cpw = eng.info(Info.EVAL_BLOCK), eng.info(Info.EVAL_CPW)
     src_text = eng.kernel_source(envs.dynamics_source(args.env))
     user_tables = [np.asarray(b, np.float32) for b in cls.bins_space(args.bins).values()]
     tab = torch.from_numpy(np.concatenate([np.asarray(solver.action_space, np.float32)] +

@@ -8,6 +8,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch
 
 from dynamicprogramming_amd import envs
+from dynamicprogramming_amd._native import Info
 
 for name, bins in (("double_cartpole", 25), ("double_cartpole_swingup", 25), ("cartpole_swingup", 50)):
     cls = envs.ENVS[name]
@@ -17,7 +18,7 @@ for name, bins in (("double_cartpole", 25), ("double_cartpole_swingup", 25), ("c
         t0 = time.perf_counter()
         s = klass(cls.bins_space(bins), cls.ACTIONS, envs.CudaPIConfig(**cls.CONFIG), device="cuda:0")
         torch.cuda.synchronize()
-        row[label] = {"seconds": time.perf_counter() - t0, "live_list": s._backend.engine.info(16),
+        row[label] = {"seconds": time.perf_counter() - t0, "live_list": s._backend.engine.info(Info.LIVE_STATES),
                       "states_space_materialised": s._states_space is not None}
         s._backend.close()
         del s
