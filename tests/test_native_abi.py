@@ -211,6 +211,31 @@ def test_grids_beyond_32_bit_byte_offsets_compile(tmp_path):
     eng.compile(envs.dynamics_source("double_cartpole"), cache_dir=tmp_path)
     assert eng.info(Info.CACHE_HIT) == 0 and len(list(tmp_path.glob("pi_*.hsaco"))) == 1
     eng.close()
+    # ... and the 4-D form of it (8 pair loads, another stride mix), on the ragged grid tests/test_gpu_addr64.py runs:
+    # no stride a power of two, a ragged last chunk, in the env's order and in a permuted one
+    shape = (181, 183, 179, 182)
+    n = int(np.prod(shape, dtype=np.int64))
+    assert n == 1_079_081_094 and 4 * n >= 1 << 32 and n < 1 << 31 and n % 256 != 0
+    bins = H.env_bins("double_pendulum_swingup", shape)
+    assert 4 * (sum(shape) + len(envs.ENVS["double_pendulum_swingup"].ACTIONS)) <= 60 * 1024       # pi_create's LDS budget
+    src = envs.dynamics_source("double_pendulum_swingup")
+    for k, order in enumerate((None, (0, 2, 1, 3))):
+        eng = _native.Engine(4, list(shape), [b.min() for b in bins], [b.max() for b in bins], bins,
+                             envs.ENVS["double_pendulum_swingup"].ACTIONS, device=-1, order=order)
+        assert eng.n_states == n and 4 * eng.n_states >= 1 << 32 and eng.n_states < 1 << 31
+        text = eng.kernel_source(src)
+        assert "#define PI_D 4\n" in text and "PI_OFF32" in text
+        eng.compile(src, cache_dir=tmp_path)
+        assert eng.info(Info.CACHE_HIT) == 0 and len(list(tmp_path.glob("pi_*.hsaco"))) == 2 + k
+        eng.close()
+
+
+def test_a_2d_grid_of_2_pow_30_states_is_refused_for_its_bin_tables():
+    """Why no 2-D grid appears among the n >= 2^30 tests: (32768, 32768) has 2^30 states, below the 2^31 limit, but its
+    bin tables (256 KiB) do not fit the 60 KiB LDS budget of the sweep kernels; pi_create says so."""
+    bins = [np.linspace(-1.0, 1.0, 32768, dtype=np.float32)] * 2
+    with pytest.raises(_native.NativeError, match="60 KiB LDS budget"):
+        _native.Engine(2, [32768, 32768], [-1.0, -1.0], [1.0, 1.0], bins, [0.0, 1.0], device=-1)
 
 
 def test_checked_build_compiles_for_gfx950(tmp_path, monkeypatch):
