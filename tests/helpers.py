@@ -289,3 +289,169 @@ def schedule_groups(sched: dict, n_chunks: int) -> np.ndarray:
         valid = (r < b1 - b0) & (g >= 0)
     valid &= g * cpw < n_chunks
     return np.stack([np.where(valid, g, -1), b % 8], axis=1)
+
+
+# -- dispatch thresholds and degenerate grids (tests/test_edge_dispatch.py, tests/test_gpu_edges.py) ---------------------
+def edge_actions(name: str, actions=None) -> np.ndarray:
+    return np.asarray(envs.ENVS[name].ACTIONS if actions is None else actions, np.float32)
+
+
+def table_floats(name: str, shape, actions=None) -> int:
+    """Floats pi_stage_table copies to LDS for this specialisation: the actions and every dimension's bin table."""
+    return len(edge_actions(name, actions)) + int(sum(int(g) for g in shape))
+
+
+# What pi_create must decide at every threshold of its dispatch, WRITTEN OUT from the design (DESIGN.md; the comments on
+# the launch geometry and the one-launch kernels in csrc/pi_api.cpp's pi_create), not computed by the code under test: a
+# threshold that moves has to be moved here as well, on purpose.  Per row: env, shape, then
+#   k        states per thread of the LDS-resident kernels (Info.RESIDENT_STATES_PER_THREAD; 0: not resident).  Limits
+#            12 288 (2-D, 1024 threads), 4 096 (4-D, 512 threads), 1 024 (6-D, 512 threads); k = ceil(n / threads)
+#   flow     pi_eval_flow_kernel is built: 2-D and 4-D, resident limit < n <= 2^17 (2-D: from 4 096 < n where the
+#            XCD-local kernel is wanted)
+#   xcd_s    states per workgroup of pi_xcd_kernel, None where it is not built: 2-D, 4 096 < n <= 2^16;
+#            ceil(ceil(n / 32) / 32) * 32 (n over the 32 CUs of an XCD, whole 128-byte lines)
+#   eb, ib   threads per workgroup of the evaluation / improvement sweeps: 1024 / 512 on 2-D and 4-D grids of >= 2^24
+#            states, 256 / 256 otherwise
+#   ecpw, icpw  chunks per workgroup: evaluation 2 from 2^20 states on; 6-D grids of >= 2^24 states 4 and 3
+#   placed   (rows with flow) whether a 256-CU MI355X HAS the dataflow kernel after loading it: all ceil(n / 256) workgroups
+#            must be resident at once within 3/4 (rounded down) of the occupancy the runtime reports.  The 2-D plugins are
+#            reported 3 or more workgroups per CU and place 512; every 4-D plugin is reported 2, which leaves ONE per CU:
+#            256 workgroups, 2^16 states.  pi_create's 4-D limit of 2^17 is therefore never reached on this device
+#            (measured: cartpole, cartpole_swingup, double_pendulum_swingup and overhead_crane are all placed at 16^4 and
+#            all refused at 16.16.16.24 and 16.16.16.32); the refusals are pinned as such, the sweeps serve those grids
+#   live     (rows whose solver path is run) whether the solver's sweeps go through a live-state list: from 2^20 states
+#            on (PI_MI355_LIVE_MIN), on grids with terminal states, where at least 3 % of the lanes of the waves that
+#            hold a live state are dead (pi_prepare_mask).  The list then holds every non-terminal state
+DISPATCH_TABLE = [
+    # resident limit, 2-D (12 288) — both sides lie inside the XCD window
+    dict(name="mountain_car", shape=(96, 128), k=12, flow=True, xcd_s=384, eb=256, ib=256, ecpw=1, icpw=1),
+    dict(name="mountain_car", shape=(97, 127), k=0, flow=True, xcd_s=416, eb=256, ib=256, ecpw=1, icpw=1),
+    # XCD_MIN (4 096): at the limit one CU serves the grid alone, one state more and the XCD-local kernel is preferred
+    dict(name="pendulum", shape=(64, 64), k=4, flow=False, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    dict(name="pendulum", shape=(64, 65), k=5, flow=True, xcd_s=160, eb=256, ib=256, ecpw=1, icpw=1),
+    # XCD_MAX (2^16)
+    dict(name="pendulum", shape=(256, 256), k=0, flow=True, xcd_s=2048, eb=256, ib=256, ecpw=1, icpw=1),
+    dict(name="pendulum", shape=(256, 257), k=0, flow=True, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    # dataflow kernel, 2-D (2^17)
+    dict(name="mountain_car", shape=(256, 512), k=0, flow=True, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    dict(name="mountain_car", shape=(363, 362), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    # dataflow kernel, 4-D (2^17)
+    dict(name="cartpole_swingup", shape=(16, 16, 16, 32), k=0, flow=True, placed=False, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    dict(name="cartpole_swingup", shape=(16, 16, 16, 33), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    # ... and where the 4-D dataflow kernel stops being placed on 256 CUs: one workgroup per CU
+    dict(name="cartpole_swingup", shape=(16, 16, 16, 16), k=0, flow=True, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    dict(name="cartpole_swingup", shape=(16, 16, 16, 17), k=0, flow=True, placed=False, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    # resident limit, 4-D (4 096): beyond it the dataflow kernel
+    dict(name="cartpole", shape=(8, 8, 8, 8), k=8, flow=False, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    dict(name="cartpole", shape=(8, 8, 8, 9), k=0, flow=True, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    # resident limit, 6-D (1 024): beyond it no one-launch kernel at all
+    dict(name="double_cartpole", shape=(2, 2, 4, 4, 4, 4), k=2, flow=False, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    dict(name="double_cartpole", shape=(2, 2, 4, 4, 4, 5), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1),
+    # 2^20: two chunks per evaluation workgroup, and the live-state list (which only a device can build: `live`)
+    dict(name="cartpole", shape=(32, 32, 32, 31), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1, live=False),
+    dict(name="cartpole", shape=(32, 32, 32, 32), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=2, icpw=1, live=True),
+    dict(name="double_cartpole", shape=(8, 8, 8, 8, 16, 15), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=1, icpw=1, live=False),
+    dict(name="double_cartpole", shape=(8, 8, 8, 8, 16, 16), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=2, icpw=1, live=True),
+    # ... cartpole_swingup has terminal states too, but whole rows of them: no wave mixes live and dead lanes, no list
+    dict(name="cartpole_swingup", shape=(32, 32, 32, 32), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=2, icpw=1, live=False),
+    # 2^22: nothing changes in pi_create; the solver applies / measures a memory order (SOLVER_ORDER_TABLE)
+    dict(name="double_pendulum_swingup", shape=(64, 64, 32, 31), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=2, icpw=1, live=False),
+    dict(name="double_pendulum_swingup", shape=(64, 64, 32, 32), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=2, icpw=1, live=False),
+    # 2^24, 4-D: 1024- and 512-thread workgroups
+    dict(name="double_pendulum_swingup", shape=(64, 64, 64, 63), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=2, icpw=1, live=False),
+    dict(name="double_pendulum_swingup", shape=(64, 64, 64, 64), k=0, flow=False, xcd_s=None, eb=1024, ib=512, ecpw=2, icpw=1, live=False),
+    # 2^24, 6-D: four and three chunks per workgroup
+    dict(name="double_cartpole", shape=(16, 16, 16, 16, 16, 15), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=2, icpw=1, live=True),
+    dict(name="double_cartpole", shape=(16, 16, 16, 16, 16, 16), k=0, flow=False, xcd_s=None, eb=256, ib=256, ecpw=4, icpw=3, live=True),
+]
+
+# (env, shape) -> the memory order a single-rank solver takes WITHOUT measuring anything: the class's own MEMORY_ORDER
+# from 2^22 states on (solver._ORDER_MIN_STATES), the env's order (None) below.
+SOLVER_ORDER_TABLE = [
+    ("double_pendulum_swingup", (64, 64, 32, 31), None), ("double_pendulum_swingup", (64, 64, 32, 32), (0, 2, 1, 3)),
+    ("double_cartpole", (8, 8, 8, 16, 16, 31), None), ("double_cartpole", (8, 8, 8, 16, 16, 32), (5, 4, 2, 3, 0, 1)),
+]
+
+_PENDULUM_BEYOND_CLAMP_64 = np.linspace(-3.0, 3.0, 64, dtype=np.float32)      # 11 entries <= -2 and 11 >= 2: exact ties in Q
+_PENDULUM_BEYOND_CLAMP_257 = np.linspace(-4.0, 4.0, 257, dtype=np.float32)    # 65 + 65 of them clamp
+
+# The degenerate specialisations: (id, env, shape, actions or None for the env's own).  21 pendulum torques: the tables
+# of (2, 2025) hold exactly 2048 floats (the last size staged through registers at 256 threads), (2, 2026) 2049 (the
+# first one through the strided loop), (2, 15337) 15 360 (pi_create's limit).  2.2.2.1500 with its 11 actions holds 1517
+# floats and does NOT reach the strided loop; 2.2.2.2100 (2117) is the 4-D case that does.  257 is prime and no grid has 257 states:
+# 258 and 259 stand in for it, 1025 = 256 * 4 + 1.  With the envs' own bounds every node of the 2-bin cartpole and 6-D
+# grids is terminal (x = +-bound): those cases pin that such a grid is copied through, the 2-D and double-pendulum ones sweep.
+EDGE_CASES = [
+    ("all2-2d", "pendulum", (2, 2), None), ("all2-4d", "double_pendulum_swingup", (2, 2, 2, 2), None),
+    ("all2-4d-terminal", "cartpole", (2, 2, 2, 2), None), ("all2-6d", "double_cartpole_swingup", (2,) * 6, None),
+    ("one2-slowest", "pendulum", (2, 3000), None), ("one2-fastest", "mountain_car", (3000, 2), None),
+    ("one2-4d", "double_pendulum_swingup", (2, 2, 2, 1500), None),
+    ("one2-4d-strided", "double_pendulum_swingup", (2, 2, 2, 2100), None),
+    ("tab2048", "pendulum", (2, 2025), None), ("tab2049", "pendulum", (2, 2026), None),
+    ("tab15360", "pendulum", (2, 15337), None),
+    ("n63", "mountain_car", (7, 9), None), ("n255", "pendulum", (15, 17), None), ("n256", "mountain_car", (16, 16), None),
+    ("n258", "pendulum", (6, 43), None), ("n259", "mountain_car", (37, 7), None),
+    ("n513-4d", "cartpole", (3, 3, 3, 19), None), ("n1025", "pendulum", (25, 41), None),
+    ("act1", "pendulum", (33, 29), np.array([0.5], np.float32)), ("act1-4d", "cartpole", (5, 4, 6, 3), np.array([10.0], np.float32)),
+    ("act2", "pendulum", (33, 29), np.array([-2.5, 2.5], np.float32)),
+    ("act64", "pendulum", (33, 29), _PENDULUM_BEYOND_CLAMP_64), ("act257", "pendulum", (21, 13), _PENDULUM_BEYOND_CLAMP_257),
+]
+# case id -> (k, flow, xcd_s) of the degenerate specialisations, by the rules in front of DISPATCH_TABLE (all of them
+# sweep with 256-thread workgroups, one chunk each; every dataflow kernel among them is placed: at most 120 workgroups)
+EDGE_DISPATCH = {
+    "all2-2d": (1, False, None), "all2-4d": (1, False, None), "all2-4d-terminal": (1, False, None), "all2-6d": (1, False, None),
+    "one2-slowest": (6, True, 192), "one2-fastest": (6, True, 192), "one2-4d": (0, True, None), "one2-4d-strided": (0, True, None),
+    "tab2048": (4, False, None), "tab2049": (4, False, None), "tab15360": (0, True, 960),
+    "n63": (1, False, None), "n255": (1, False, None), "n256": (1, False, None), "n258": (1, False, None), "n259": (1, False, None),
+    "n513-4d": (2, False, None), "n1025": (2, False, None),
+    "act1": (1, False, None), "act1-4d": (1, False, None), "act2": (1, False, None), "act64": (1, False, None), "act257": (1, False, None),
+}
+EDGE_ROWS = [dict(name=name, shape=shape, actions=acts, k=EDGE_DISPATCH[cid][0], flow=EDGE_DISPATCH[cid][1],
+                  xcd_s=EDGE_DISPATCH[cid][2], eb=256, ib=256, ecpw=1, icpw=1) for cid, name, shape, acts in EDGE_CASES]
+THRESHOLD_CASES = [("x".join(str(g) for g in row["shape"]) + "-" + row["name"], row["name"], row["shape"], None) for row in DISPATCH_TABLE]
+
+
+def edge_case_params():
+    """pytest parameters (case id, env, shape, actions) of every specialisation both edge modules go through."""
+    import pytest
+    return [pytest.param(*c, id=c[0] if c[0].endswith(c[1]) else f"{c[0]}-{c[1]}") for c in EDGE_CASES + THRESHOLD_CASES]
+
+
+def host_engine(name: str, shape, actions=None):
+    """A handle without a device (pi_create's device -1): dispatch decisions and hipRTC compiles only."""
+    from dynamicprogramming_amd import _native
+    bins = env_bins(name, shape)
+    return _native.Engine(envs.ENVS[name]._D, [len(b) for b in bins], [b.min() for b in bins], [b.max() for b in bins],
+                          bins, edge_actions(name, actions), device=-1)
+
+
+def backup_float64(chk, bins, actions, V, gamma):
+    """Plain float64 statement of the backup on the grid `bins`: Q[a, s] = r + gamma * E, E the multilinear interpolation
+    of V over the 2^D corners of the successor's cell (0 for a `done` successor).  Successor, reward and flag come from
+    the oracle's `step`; position, cell, weights and sums are numpy float64."""
+    D = len(bins)
+    shape = [len(b) for b in bins]
+    lo = np.array([np.float32(b.min()) for b in bins], np.float64)
+    hi = np.array([np.float32(b.max()) for b in bins], np.float64)
+    states = oracle.states_from_bins(bins)
+    V64 = np.asarray(V, np.float64).reshape(shape)
+    Q = np.empty((len(actions), len(states)), np.float64)
+    for a, u in enumerate(actions):
+        nxt, rew, done = chk.step(states, np.float32(u))
+        cell, frac = [], []
+        for d in range(D):
+            t = np.clip((nxt[:, d].astype(np.float64) - lo[d]) / (hi[d] - lo[d]) * (shape[d] - 1), 0.0, shape[d] - 1.0)
+            i = np.minimum(np.floor(t).astype(np.int64), shape[d] - 2)
+            cell.append(i)
+            frac.append(t - i)
+        E = np.zeros(len(states), np.float64)
+        for corner in range(1 << D):
+            w = np.ones(len(states), np.float64)
+            at = []
+            for d in range(D):
+                bit = (corner >> (D - 1 - d)) & 1
+                w = w * (frac[d] if bit else 1.0 - frac[d])
+                at.append(cell[d] + bit)
+            E += w * V64[tuple(at)]
+        Q[a] = rew.astype(np.float64) + float(gamma) * np.where(done, 0.0, E)
+    return Q
