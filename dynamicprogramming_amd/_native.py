@@ -77,6 +77,9 @@ SIGNATURES = {
     "pi_infer_destroy": (None, [_vp]),
     "pi_infer_set_policy": (ctypes.c_int, [_vp, _i32p, ctypes.c_int64, _f32p, ctypes.c_int]),
     "pi_infer_query": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "pi_infer_set_dynamics": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]),
+    "pi_infer_rollout": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp,
+                                        _vp, ctypes.c_int, _vp]),
     "pi_plan_schedule": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_uint64)]),
     "pi_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64]),
@@ -89,7 +92,7 @@ SIGNATURES = {
     "pi_eval_end": (ctypes.c_int, [_vp]),
 }
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 _lib = None
 _load_error: Exception | None = None
 
@@ -585,6 +588,23 @@ class InferenceEngine:
     def query(self, d_points, m, d_actions=0, d_weights=0, d_indices=0, stream=0) -> None:
         _check(lib().pi_infer_query(self._h, d_points, int(m), d_actions or None, d_weights or None,
                                     d_indices or None, stream or None), "pi_infer_query")
+
+    def set_dynamics(self, dynamics_src: str) -> str:
+        """Build the rollout kernel for the env plugin `dynamics_src` on this handle's grid (a compile check on a
+        host-only handle); returns the compiler's log.  Calling it again replaces the plugin."""
+        log = ctypes.create_string_buffer(1 << 16)
+        rc = lib().pi_infer_set_dynamics(self._h, dynamics_src.encode(), log, len(log))
+        text = log.value.decode(errors="replace")
+        if rc != 0:
+            raise NativeError(f"rollout kernel compilation failed:\n{last_error()}")
+        return text
+
+    def rollout(self, d_start, m, n_steps, gamma=1.0, d_final=0, d_return=0, d_length=0, d_terminated=0, d_traj=0,
+                traj_every=0, stream=0) -> None:
+        """m episodes of n_steps closed-loop steps in one launch (pi_infer_rollout; raw device pointers, asynchronous)."""
+        _check(lib().pi_infer_rollout(self._h, d_start or None, int(m), int(n_steps), float(gamma), d_final or None,
+                                      d_return or None, d_length or None, d_terminated or None, d_traj or None,
+                                      int(traj_every), stream or None), "pi_infer_rollout")
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -1,5 +1,5 @@
-// pi_internal.h — shared between pi_api.cpp (handles, hipRTC, launches) and pi_comm.cpp
-// (multi-GPU transports and the sharded sweep driver).  Not part of the C ABI.
+// pi_internal.h — shared between pi_api.cpp (handles, hipRTC, launches), pi_comm.cpp (multi-GPU transports
+// and the sharded sweep driver), pi_infer.cpp and pi_rollout.cpp (inference handle).  Not part of the C ABI.
 #pragma once
 
 #include "pi_mi355.h"
@@ -173,6 +173,26 @@ struct pi_handle {
     pi::Comm* comm = nullptr;            // multi-GPU transport (owned; pi_comm.cpp), null = single rank
     pi::ShardPlan* plan = nullptr;       // exchange plan (owned; pi_comm.cpp)
     pi::P2pPending* p2p_pending = nullptr;   // pi_p2p_describe without its pi_comm_init_p2p yet (owned; pi_p2p.cpp)
+};
+
+// One inference handle (pi_infer.cpp; the rollout entry points on it: pi_rollout.cpp).
+struct pi_infer {
+    int device = -1;
+    int D = 0;
+    int64_t n_corners = 0, n_states = 0;
+    int n_actions = 0;
+    hipModule_t module = nullptr;
+    hipFunction_t f = nullptr;
+    float* d_actions = nullptr;
+    int32_t* d_policy = nullptr;
+    // what pi_infer_create was given, for the second module (pi_infer_set_dynamics): the grid as the generated
+    // defines of the translation unit (PI_D, PI_LO_INIT, ... PI_BITS_INIT) and the code-object cache
+    std::string grid_defines, cache_dir;
+    bool has_cache_dir = false;
+    // second module: grid + pi_math.h + the env plugin + csrc/pi_rollout_kernels.hip
+    hipModule_t module_rollout = nullptr;
+    hipFunction_t f_rollout = nullptr;
+    bool has_dynamics = false;           // pi_infer_set_dynamics went through (host-only handles: it compiled)
 };
 
 namespace pi {

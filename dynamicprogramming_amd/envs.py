@@ -38,6 +38,15 @@ def _lin(lo, hi, n):
     return np.linspace(lo, hi, n, dtype=np.float32)
 
 
+def _wrap_pi(a):
+    """float64 angles -> [-pi, pi), as the reference's runners wrap their start angles."""
+    return (a + np.pi) % (2.0 * np.pi) - np.pi
+
+
+def _f32_states(cols):
+    return np.ascontiguousarray(np.stack(cols, axis=1).astype(np.float32))
+
+
 # ═════════════════════════════ 2-D ═══════════════════════════════════════════════
 
 class PendulumCuda(CudaPolicyIteration2D):
@@ -51,6 +60,12 @@ class PendulumCuda(CudaPolicyIteration2D):
     @staticmethod
     def bins_space(bins: int = DEFAULT_BINS) -> dict:
         return {"theta": _lin(-np.pi, np.pi, bins), "theta_dot": _lin(-8.0, 8.0, bins)}
+
+    @classmethod
+    def start_states(cls, rng, m: int) -> np.ndarray:
+        """(m, 2) float32 starts of the evaluation rollouts: Pendulum-v1's reset (the reference's evaluate() resets
+        the gymnasium env, runners/pendulum_cuda.py:152): theta in [-pi, pi], omega in [-1, 1]."""
+        return _f32_states([rng.uniform(-np.pi, np.pi, m), rng.uniform(-1.0, 1.0, m)])
 
     def _dynamics_cuda_src(self) -> str:
         return _PI_WRAP + r'''
@@ -83,6 +98,11 @@ class MountainCarCuda(CudaPolicyIteration2D):
     @staticmethod
     def bins_space(bins: int = DEFAULT_BINS) -> dict:
         return {"position": _lin(-1.2, 0.6, bins), "velocity": _lin(-0.07, 0.07, bins)}
+
+    @classmethod
+    def start_states(cls, rng, m: int) -> np.ndarray:
+        """(m, 2) float32: MountainCar-v0's reset (runners/mountain_car_cuda.py:122): position in [-0.6, -0.4], at rest."""
+        return _f32_states([rng.uniform(-0.6, -0.4, m), np.zeros(m)])
 
     def _dynamics_cuda_src(self) -> str:
         return r'''
@@ -119,6 +139,12 @@ class ContinuousMountainCarCuda(CudaPolicyIteration2D):
     @staticmethod
     def bins_space(bins: int = DEFAULT_BINS) -> dict:
         return {"position": _lin(-1.2, 0.6, bins), "velocity": _lin(-0.07, 0.07, bins)}
+
+    @classmethod
+    def start_states(cls, rng, m: int) -> np.ndarray:
+        """(m, 2) float32: MountainCarContinuous-v0's reset (runners/continuous_mountain_car_cuda.py:126): position in
+        [-0.6, -0.4], at rest."""
+        return _f32_states([rng.uniform(-0.6, -0.4, m), np.zeros(m)])
 
     def _dynamics_cuda_src(self) -> str:
         return r'''
@@ -180,6 +206,11 @@ class CartPoleCuda(CudaPolicyIteration4D):
         return {"x": _lin(-2.5, 2.5, bins), "x_dot": _lin(-5.0, 5.0, bins),
                 "theta": _lin(-0.25, 0.25, bins), "theta_dot": _lin(-5.0, 5.0, bins)}
 
+    @classmethod
+    def start_states(cls, rng, m: int) -> np.ndarray:
+        """(m, 4) float32: CartPole-v1's reset (runners/cartpole_cuda.py:164): every coordinate in +-0.05."""
+        return np.ascontiguousarray(rng.uniform(-0.05, 0.05, (m, 4)).astype(np.float32))
+
     def _dynamics_cuda_src(self) -> str:
         return _CARTPOLE_CORE + r'''
         __device__ void step_dynamics(float x, float xd, float th, float thd, float F,
@@ -227,6 +258,13 @@ class CartPoleSwingUpCuda(CudaPolicyIteration4D):
     def bins_space(bins: int = DEFAULT_BINS) -> dict:
         return {"x": _lin(-2.5, 2.5, bins), "x_dot": _lin(-5.0, 5.0, bins),
                 "theta": _lin(-np.pi, np.pi, bins), "th_dot": _lin(-10.0, 10.0, bins)}
+
+    @classmethod
+    def start_states(cls, rng, m: int) -> np.ndarray:
+        """(m, 4) float32: pole hanging down, pi +- 0.05 wrapped to [-pi, pi), cart within +-0.1, at rest
+        (runners/cartpole_swingup_cuda.py:300-309)."""
+        z = np.zeros(m)
+        return _f32_states([rng.uniform(-0.1, 0.1, m), z, _wrap_pi(np.pi + rng.uniform(-0.05, 0.05, m)), z])
 
     def _dynamics_cuda_src(self) -> str:
         return _PI_WRAP + _CARTPOLE_CORE + r'''
@@ -282,6 +320,14 @@ class DoublePendulumSwingUpCuda(CudaPolicyIteration4D):
     def bins_space(bins: int = DEFAULT_BINS) -> dict:
         return {"theta1": _lin(-np.pi, np.pi, bins), "th1_dot": _lin(-15.0, 15.0, bins),
                 "theta2": _lin(-np.pi, np.pi, bins), "th2_dot": _lin(-15.0, 15.0, bins)}
+
+    @classmethod
+    def start_states(cls, rng, m: int) -> np.ndarray:
+        """(m, 4) float32: both links hanging down, pi +- 0.05 wrapped to [-pi, pi), at rest
+        (runners/double_pendulum_swingup_cuda.py:416-425)."""
+        z = np.zeros(m)
+        return _f32_states([_wrap_pi(np.pi + rng.uniform(-0.05, 0.05, m)), z,
+                            _wrap_pi(np.pi + rng.uniform(-0.05, 0.05, m)), z])
 
     def _dynamics_cuda_src(self) -> str:
         return _PI_WRAP + r'''
@@ -371,6 +417,14 @@ class OverheadCraneCuda(CudaPolicyIteration4D):
     def bins_space(cls, bins: int = DEFAULT_BINS) -> dict:
         return {"x": _lin(-cls._RAIL, cls._RAIL, bins), "x_dot": _lin(-4.0, 4.0, bins),
                 "theta": _lin(-cls._TH_EDGE, cls._TH_EDGE, bins), "theta_dot": _lin(-4.0, 4.0, bins)}
+
+    @classmethod
+    def start_states(cls, rng, m: int, start_x: float = 2.5) -> np.ndarray:
+        """(m, 4) float32: the trolley at `start_x` (the runner's --start-x) +- 0.1, kept inside +-2.8, the load
+        within +-0.05 rad of hanging straight, at rest (runners/overhead_crane_cuda.py:417-420)."""
+        z = np.zeros(m)
+        return _f32_states([np.clip(float(start_x) + rng.uniform(-0.1, 0.1, m), -2.8, 2.8), z,
+                            rng.uniform(-0.05, 0.05, m), z])
 
     def _dynamics_cuda_src(self) -> str:
         body = r'''
@@ -513,6 +567,11 @@ class DoubleCartPoleCuda(CudaPolicyIteration6D):
                 "theta1": _lin(-e, e, bins), "th1_dot": _lin(-5.0, 5.0, bins),
                 "theta2": _lin(-e, e, bins), "th2_dot": _lin(-5.0, 5.0, bins)}
 
+    @classmethod
+    def start_states(cls, rng, m: int) -> np.ndarray:
+        """(m, 6) float32: every coordinate in +-0.05 (runners/double_cartpole_cuda.py:372)."""
+        return np.ascontiguousarray(rng.uniform(-0.05, 0.05, (m, 6)).astype(np.float32))
+
     def _dynamics_cuda_src(self) -> str:
         return _DOUBLE_CART_CORE + r'''
         #define BAL_XLIM   2.4f
@@ -568,6 +627,14 @@ class DoubleCartPoleSwingUpCuda(CudaPolicyIteration6D):
         return {"x": _lin(-2.5, 2.5, bins), "x_dot": _lin(-8.0, 8.0, bins),
                 "theta1": _lin(-np.pi, np.pi, bins), "th1_dot": _lin(-15.0, 15.0, bins),
                 "theta2": _lin(-np.pi, np.pi, bins), "th2_dot": _lin(-15.0, 15.0, bins)}
+
+    @classmethod
+    def start_states(cls, rng, m: int) -> np.ndarray:
+        """(m, 6) float32: both poles hanging down, pi +- 0.05 wrapped to [-pi, pi), cart within +-0.1, at rest
+        (runners/double_cartpole_swingup_cuda.py:493-504)."""
+        z = np.zeros(m)
+        return _f32_states([rng.uniform(-0.1, 0.1, m), z, _wrap_pi(np.pi + rng.uniform(-0.05, 0.05, m)), z,
+                            _wrap_pi(np.pi + rng.uniform(-0.05, 0.05, m)), z])
 
     def _dynamics_cuda_src(self) -> str:
         return _PI_WRAP + _DOUBLE_CART_CORE + r'''

@@ -943,6 +943,27 @@ class _CudaPolicyIterationBase(abc.ABC):
         self._backend.close()
         logger.success("Device memory released. Results in host memory.")
 
+    # ── closed-loop evaluation (the reference's per-runner evaluate(), e.g. pendulum_cuda.py:135-189) ─────────
+    def rollout(self, start_states, steps, gamma=1.0, record_every=0, device=None):
+        """Roll the trained policy out on the env's own dynamics, every episode of the batch in ONE kernel launch
+        (utils.barycentric.DevicePolicy.rollout; csrc/pi_rollout_kernels.hip): `start_states` (m, D) — numpy, or a
+        float32 tensor on the device — for `steps` steps each.  Returns a RolloutResult (states, returns, lengths,
+        terminated, trajectory).  Works on the host arrays, so after run() as well as on a load()ed instance."""
+        from utils.barycentric import DevicePolicy
+        if getattr(self, "policy", None) is None:
+            raise RuntimeError("rollout needs a trained policy in host memory: call run() or load() first")
+        if device is None:                          # the device the solver trained on; a load()ed instance has none
+            device = getattr(self, "_device_arg", None) or "cuda:0"
+        dp = DevicePolicy(self.policy, self.action_space, self.bounds_low, self.bounds_high, self.grid_shape,
+                          self.strides, self.corner_bits, device=device)
+        try:
+            dp.set_dynamics(self._dynamics_cuda_src())
+            out = dp.rollout(start_states, steps, gamma=gamma, record_every=record_every)
+            dp._torch.cuda.synchronize(dp.device)
+            return out
+        finally:
+            dp.close()
+
     # ── persistence (schema of :392-432) ────────────────────────────────────────────
     def save(self, filepath) -> None:
         filepath = Path(filepath).with_suffix(".npz")

@@ -33,7 +33,7 @@ extern "C" {
 typedef struct pi_handle pi_handle;
 
 /* ABI version of this header (bumped on any signature change). */
-#define PI_MI355_ABI_VERSION 10
+#define PI_MI355_ABI_VERSION 11
 int pi_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -425,6 +425,23 @@ int pi_plan_schedule(pi_handle* h, int block, int64_t first, int64_t count, int6
  *   pi_infer_query      d_points (m, D) float32 on the device; any of the three outputs may be null:
  *                       d_actions_out (m) float32 = sum_c w[c] * action_space[policy[idx[c]]] (ascending c),
  *                       d_weights_out (m, 2^D) float32, d_indices_out (m, 2^D) int32.  Asynchronous.
+ * Closed-loop rollouts on the same handle (the reference's per-runner evaluate(), e.g. pendulum_cuda.py:135-189:
+ * get_optimal_action + one env step per time step on the CPU) as ONE launch for m episodes:
+ *   pi_infer_set_dynamics  the env plugin (the step_dynamics string pi_compile takes), compiled with the handle's grid
+ *                       and csrc/pi_rollout_kernels.hip into a second module (same flags and cache as pi_compile;
+ *                       compiler output in `log`, errors in `log` and pi_last_error).  device = -1: compile check.
+ *                       Calling it again replaces the module (after a device synchronisation)
+ *   pi_infer_rollout    d_start (m, D) float32 on the device, dimensions in the order of step_dynamics' arguments.
+ *                       Every episode runs n_steps steps of: action = what pi_infer_query returns for the state
+ *                       (same bits); step_dynamics; ret = ret + disc * r, disc = disc * gamma (float32, separate
+ *                       multiply and add); state = successor, length = t + 1; a `done` step ends the episode,
+ *                       which keeps its state from then on.  Outputs, any of which may be null: d_final (m, D)
+ *                       float32, d_return (m) float32, d_length (m) int32, d_terminated (m) uint8 (1: ended by
+ *                       `done`).  traj_every > 0: row j of d_traj, (n_steps / traj_every + 1, m, D) float32, is every
+ *                       episode's state after j * traj_every steps (row 0 the start; an ended episode repeats its
+ *                       last state).  d_final and d_traj must be 8-byte aligned (4-D: 16-byte).  Needs
+ *                       pi_infer_set_policy and pi_infer_set_dynamics; m == 0 is a no-op, n_steps == 0 copies the
+ *                       start (length 0, return 0); traj_every > n_steps (n_steps > 0) is an error.  Asynchronous.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pi_infer pi_infer;
 pi_infer* pi_infer_create(int device, int D, const float* lo, const float* hi, const int32_t* grid_shape,
@@ -435,6 +452,10 @@ int pi_infer_set_policy(pi_infer* h, const int32_t* policy, int64_t n_states, co
                         int n_actions);
 int pi_infer_query(pi_infer* h, const float* d_points, int64_t m, float* d_actions_out, float* d_weights_out,
                    int32_t* d_indices_out, void* stream);
+int pi_infer_set_dynamics(pi_infer* h, const char* dynamics_src, char* log, size_t log_len);
+int pi_infer_rollout(pi_infer* h, const float* d_start, int64_t m, int n_steps, float gamma, float* d_final,
+                     float* d_return, int32_t* d_length, uint8_t* d_terminated, float* d_traj, int traj_every,
+                     void* stream);
 
 /* Tuning: the `what` of pi_set_option. */
 enum pi_option_code {

@@ -8,11 +8,17 @@ written for the reference works unchanged:
 
   solver-side, honoured      --bins N, --retrain, --save-path PATH, crane: --target-x X
   rollout-side, accepted     --render, --record PATH, --random [N], --episodes N, --steps N,
-  and ignored (with a note)  --seed N, --no-plot, crane: --start-x X
+  and ignored (with a note)  --seed N, --no-plot, crane: --start-x X    (but see --rollout below)
 
 One flag is an extension (the reference has no counterpart; off by default): --value-iteration trains with
 the fused max-backup sweep of SURVEY.md section 8f.4 instead of policy iteration — the same fixed point
 (measured: identical V and policy on the 80^4 double pendulum) in fewer sweeps.
+
+A second extension flag, --rollout (off by default), runs the closed-loop evaluation that follows training in the
+reference — on the GPU, all episodes in one kernel launch (solver.rollout): --episodes episodes of --steps steps from
+the env's start distribution (envs.<Env>.start_states, seeded by --seed; crane: around --start-x), one line per
+episode; those four flags are then honoured, not ignored.  The 6-D swing-up also writes results/last_trajectory.npz
+(the last 100 states of every episode), the file the reference's scoring script reads.
 
 The ignored group drives the reference's gymnasium / pygame / matplotlib evaluation harness, which is
 outside the scope of this package: training, saving and loading behave as in
@@ -96,7 +102,54 @@ def build_parser(env_name: str, default_save: str) -> argparse.ArgumentParser:
     p.add_argument("--save-path", type=Path, default=Path(default_save))
     p.add_argument("--value-iteration", action="store_true",
                    help="(extension) train with fused value-iteration sweeps instead of policy iteration")
+    p.add_argument("--rollout", action="store_true",
+                   help="(extension) after training / loading, roll the policy out on the GPU: --episodes episodes of "
+                        "--steps steps from the env's start states (--seed; crane: --start-x), one line per episode")
     return p
+
+
+STEADY_WINDOW = 100     # states per episode in results/last_trajectory.npz (the reference's STATS_WINDOW)
+
+
+def evaluate(env_name: str, pi, episodes: int, steps: int, seed: int, start_x: float | None = None,
+             traj_path: Path | None = None):
+    """--rollout: `episodes` closed-loop episodes of at most `steps` steps in one kernel launch (solver.rollout), one
+    line each.  `traj_path`: also dump the last min(100, length + 1) states of every episode, concatenated, as the
+    reference's evaluate() does for its scoring script (double_cartpole_swingup_cuda.py:583-592).  Returns the
+    RolloutResult."""
+    import numpy as np
+    from dynamicprogramming_amd import envs
+    cls = envs.ENVS[env_name]
+    rng = np.random.default_rng(seed)
+    kw = {} if start_x is None else {"start_x": start_x}
+    starts = cls.start_states(rng, episodes, **kw)
+    res = pi.rollout(starts, steps, gamma=1.0, record_every=1 if traj_path is not None else 0)
+    for ep in range(episodes):
+        outcome = "terminated" if res.terminated[ep] else f"{steps} steps"
+        final = "  ".join(f"{v:+.4f}" for v in res.states[ep])
+        print(f"Episode {ep + 1}: {int(res.lengths[ep])} steps | return = {float(res.returns[ep]):.3f} | {outcome} | "
+              f"final state: {final}")
+    if traj_path is not None:
+        windows = []
+        for ep in range(episodes):
+            n = int(res.lengths[ep]) + 1                      # rows 0 .. length of this episode: start + every step
+            windows.append(res.trajectory[max(0, n - STEADY_WINDOW):n, ep, :])
+        traj_path = Path(traj_path)
+        traj_path.parent.mkdir(parents=True, exist_ok=True)
+        np.savez(traj_path, traj=np.concatenate(windows, axis=0).astype(np.float32), n_episodes=episodes,
+                 steps_per_episode=STEADY_WINDOW)
+        print(f"[{env_name}] steady-state windows of {episodes} episodes written to {traj_path}")
+    return res
+
+
+def ignored_flags(args) -> list:
+    """The flags of this command line that nothing here acts on.  --render, --record and --no-plot always; --episodes,
+    --steps, --seed and --start-x unless --rollout runs the evaluation they belong to."""
+    harness = not args.rollout
+    return [f for f, on in (("--render", args.render), ("--record", args.record is not None),
+                            ("--episodes", harness and args.episodes != 5), ("--steps", harness and args.steps != 1000),
+                            ("--seed", harness and args.seed != 42), ("--no-plot", args.no_plot),
+                            ("--start-x", harness and getattr(args, "start_x", 2.5) != 2.5)) if on]
 
 
 def main(env_name: str, default_save: str, argv=None):
@@ -106,10 +159,7 @@ def main(env_name: str, default_save: str, argv=None):
     from dynamicprogramming_amd import envs
     cls = envs.ENVS[env_name]
     args = build_parser(env_name, default_save).parse_args(argv)
-    ignored = [f for f, on in (("--render", args.render), ("--record", args.record is not None),
-                               ("--episodes", args.episodes != 5), ("--steps", args.steps != 1000),
-                               ("--seed", args.seed != 42), ("--no-plot", args.no_plot),
-                               ("--start-x", getattr(args, "start_x", 2.5) != 2.5)) if on]
+    ignored = ignored_flags(args)
     if ignored:
         print(f"[{env_name}] note: {', '.join(ignored)} belong to the rollout / plot harness, which this "
               "package does not include; accepted and ignored")
@@ -122,6 +172,10 @@ def main(env_name: str, default_save: str, argv=None):
         print(f"[+] Loading existing policy from {path}")
         pi = cls.load(path)
         print(f"[{env_name}] {pi.n_states:,} states, {pi.n_actions} actions; use --retrain to recompute")
-        return pi
-    print("[*] Training new policy...")
-    return train(env_name, args.bins, path, value_iteration=args.value_iteration, **kw)
+    else:
+        print("[*] Training new policy...")
+        pi = train(env_name, args.bins, path, value_iteration=args.value_iteration, **kw)
+    if args.rollout:
+        evaluate(env_name, pi, args.episodes, args.steps, args.seed, start_x=getattr(args, "start_x", None),
+                 traj_path=Path("results") / "last_trajectory.npz" if env_name == "double_cartpole_swingup" else None)
+    return pi

@@ -1,0 +1,168 @@
+"""tools/rollout_bench.py — fused closed-loop rollouts (pi_infer_rollout, csrc/pi_rollout_kernels.hip) against the
+step-by-step loop they replace (one pi_infer_query and one pi_probe_step launch per time step plus the host-side
+bookkeeping of ended episodes), on one MI355X.
+
+Configs: C2 (pendulum 200^2), C3 (cartpole swing-up 50^4) and the 25^6 double cart-pole, each with a seeded random
+policy (timing needs no training) and starts drawn uniformly inside the grid; m in {5, 4 096, 262 144} episodes of
+1 000 steps.  Under a random policy the cart-pole episodes of C3 and 25^6 end early (the share that terminated and the
+mean length are in the table): for those rows the honest unit of work is the episode-steps actually taken.
+
+The driver (no arguments) runs every (config, m) in a child process of its own under `timeout -k 10`, one after the
+other, and stops at the first child that fails; then one `rocprofv3 --kernel-trace --stats` run of the fused call
+alone (C3, m = 4 096).  Each child warms both paths up once and reports the better of `--repeat` timings (device
+events around the whole call, a synchronise at the end), fused and loop alternating.  The table goes to --out.
+usage: python tools/rollout_bench.py [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
+"""
+import argparse
+import json
+import subprocess
+import sys
+from itertools import product
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+CONFIGS = {"c2": ("pendulum", 200), "c3": ("cartpole_swingup", 50), "c5": ("double_cartpole", 25)}
+BATCHES = (5, 4096, 262144)
+CHILD_SECONDS = 420
+
+
+def child(args):
+    import numpy as np
+    import torch
+    from dynamicprogramming_amd import _native, envs
+    from utils import barycentric as B
+    env, bins = CONFIGS[args.config]
+    cls = envs.ENVS[env]
+    tabs = [np.asarray(b, np.float32) for b in cls.bins_space(bins).values()]
+    D = len(tabs)
+    shape = np.array([len(t) for t in tabs], np.int32)
+    lo, hi = np.array([t.min() for t in tabs], np.float32), np.array([t.max() for t in tabs], np.float32)
+    strides = np.array([int(np.prod(shape[d + 1:])) for d in range(D)], np.int32)
+    bits = np.array(list(product([0, 1], repeat=D)), dtype=np.int32)
+    acts = np.asarray(cls.ACTIONS, np.float32)
+    rng = np.random.default_rng(0)
+    policy = rng.integers(0, len(acts), size=int(np.prod(shape.astype(np.int64))), dtype=np.int32)
+    m, steps = args.m, args.steps
+    dev = torch.device("cuda:0")
+    starts = torch.from_numpy((lo + (hi - lo) * rng.random((m, D), dtype=np.float32)).astype(np.float32)).to(dev)
+    dp = B.DevicePolicy(policy, acts, lo, hi, shape, strides, bits, device=dev)
+    dp.set_dynamics(envs.dynamics_source(env))
+
+    def fused():
+        return dp.rollout(starts, steps)
+
+    if args.fused_only:                                   # the profiled run: warm-up + one call
+        fused()
+        out = fused()
+        torch.cuda.synchronize()
+        print(json.dumps({"config": args.config, "m": m, "steps": steps, "episode_steps": int(out.lengths.sum().item())}))
+        return
+    eng = _native.Engine(D, shape, lo, hi, tabs, acts, device=0)
+    eng.compile(envs.dynamics_source(env))
+    st = torch.cuda.current_stream(dev).cuda_stream
+
+    def loop():
+        states = starts.clone()
+        nxt = torch.empty_like(states)
+        rew = torch.empty(m, dtype=torch.float32, device=dev)
+        done = torch.empty(m, dtype=torch.uint8, device=dev)
+        ret = torch.zeros(m, dtype=torch.float32, device=dev)
+        length = torch.zeros(m, dtype=torch.int32, device=dev)
+        ended = torch.zeros(m, dtype=torch.bool, device=dev)
+        for t in range(steps):
+            act = dp(states)
+            eng.probe_step(states.data_ptr(), act.data_ptr(), nxt.data_ptr(), rew.data_ptr(), done.data_ptr(), m, st)
+            run = ~ended
+            ret = torch.where(run, ret + rew, ret)
+            states = torch.where(run[:, None], nxt, states)
+            length = torch.where(run, torch.full_like(length, t + 1), length)
+            ended = ended | (run & (done != 0))
+        return B.RolloutResult(states, ret, length, ended, None)
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record()
+        out = fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1), out
+
+    a, b = fused(), loop()                                # warm-up of both paths, and: same results
+    torch.cuda.synchronize()
+    same = bool(torch.equal(a.states.view(torch.int32), b.states.view(torch.int32)) and torch.equal(a.lengths, b.lengths)
+                and torch.equal(a.returns.view(torch.int32), b.returns.view(torch.int32)))
+    t_fused, t_loop = [], []
+    for _ in range(args.repeat):                          # alternating, so that drift hits both alike
+        t_fused.append(timed(fused)[0])
+        t_loop.append(timed(loop)[0])
+    taken = int(a.lengths.sum().item())
+    print(json.dumps({"config": args.config, "env": env, "bins": bins, "D": D, "m": m, "steps": steps, "same_bits": same,
+                      "fused_ms": min(t_fused), "loop_ms": min(t_loop), "fused_ms_all": t_fused, "loop_ms_all": t_loop,
+                      "episode_steps": taken, "terminated_share": float(a.terminated.float().mean().item()),
+                      "launches_loop": 2 * steps}))
+    dp.close()
+    eng.close()
+
+
+def driver(args):
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    rows = []
+    me = [sys.executable, str(Path(__file__).resolve())]
+    common = ["--steps", str(args.steps), "--repeat", str(args.repeat)]
+    for config in CONFIGS:
+        for m in BATCHES:
+            res = subprocess.run(["timeout", "-k", "10", str(CHILD_SECONDS), *me, "--child", "--config", config, "--m", str(m),
+                                  *common], capture_output=True, text=True)
+            if res.returncode != 0:                       # a fault, an abort or a time limit: nothing more runs
+                sys.exit(f"{config} m={m} ended with status {res.returncode}; stopping\n{res.stdout[-2000:]}\n{res.stderr[-2000:]}")
+            rows.append(json.loads(res.stdout.strip().splitlines()[-1]))
+            print(rows[-1], flush=True)
+    lines = [f"fused rollouts vs the step-by-step loop, MI355X, commit {args.commit}",
+             f"{args.steps} steps per episode, seeded random policy, starts uniform in the grid; times in ms: the better of "
+             f"{args.repeat} after one warm-up, device events around the whole call",
+             "episode-steps: steps actually taken (episodes that ended stop); launch-bound time of the loop: "
+             "2 launches per step x ~5 us = the time the loop cannot go below whatever the kernels cost",
+             "",
+             f"{'config':28s} {'m':>7s} {'fused':>10s} {'loop':>10s} {'loop/fused':>10s} {'ep-steps':>12s} {'M ep-steps/s':>12s} "
+             f"{'ended':>6s} {'same bits':>9s}"]
+    for r in rows:
+        lines.append(f"{r['config'] + ' ' + r['env'] + ' ' + str(r['bins']) + '^' + str(r['D']):28s} {r['m']:7d} "
+                     f"{r['fused_ms']:10.3f} {r['loop_ms']:10.3f} {r['loop_ms'] / r['fused_ms']:10.1f} {r['episode_steps']:12d} "
+                     f"{r['episode_steps'] / r['fused_ms'] / 1e3:12.2f} {r['terminated_share']:6.3f} {str(r['same_bits']):>9s}")
+    out.write_text("\n".join(lines) + "\n")
+    # kernel time of the fused call alone, in a run of its own (tracing slows the host)
+    trace_dir = out.parent / "rollout_trace"
+    res = subprocess.run(["timeout", "-k", "10", str(CHILD_SECONDS), "rocprofv3", "--kernel-trace", "--stats", "-d", str(trace_dir),
+                          "--", *me, "--child", "--fused-only", "--config", "c3", "--m", "4096", *common],
+                         capture_output=True, text=True)
+    if res.returncode != 0:
+        sys.exit(f"rocprofv3 run ended with status {res.returncode}\n{res.stdout[-2000:]}\n{res.stderr[-2000:]}")
+    stats = sorted(trace_dir.rglob("*kernel_stats.csv"))
+    with out.open("a") as f:
+        f.write("\nrocprofv3 --kernel-trace --stats, fused call alone (c3, m = 4096; warm-up + one call):\n")
+        for p in stats:
+            for line in p.read_text().splitlines()[:6]:
+                f.write("  " + line + "\n")
+    print(out.read_text())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "r07" / "rollout.txt"))
+    ap.add_argument("--commit", default="unknown")
+    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--child", action="store_true")
+    ap.add_argument("--fused-only", action="store_true")
+    ap.add_argument("--config", choices=list(CONFIGS), default="c3")
+    ap.add_argument("--m", type=int, default=4096)
+    args = ap.parse_args()
+    (child if args.child else driver)(args)
+
+
+if __name__ == "__main__":
+    main()
