@@ -1,50 +1,11 @@
-// pi_api.cpp — host side of libpi_mi355.so: handle management, hipRTC specialisation
-// of the sweep-kernel template for one env plugin, code-object cache, launches.
-// The C ABI is declared (with reference citations) in include/pi_mi355.h; the multi-GPU
-// entry points live in pi_comm.cpp.
+// pi_api.cpp — host side of libpi_mi355.so: error state, handle management (pi_create's dispatch policy), the sweep
+// launchers and the graph cache, the sweep entry points, options and info.
+// The C ABI is declared (with reference citations) in include/pi_mi355.h; pi_internal.h says which file holds the rest.
 
 #include "pi_internal.h"
 
-#include <hip/hiprtc.h>
-
 #include <algorithm>
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <map>
-#include <mutex>
-#include <sstream>
-#include <sys/stat.h>
-#include <unistd.h>
-
-// The device-code template and the deterministic math header are embedded verbatim.
-#ifndef PI_CSRC_DIR
-#error "build with -DPI_CSRC_DIR=\"...\" and -DPI_INCLUDE_DIR=\"...\""
-#endif
-asm(".section .rodata\n"
-    ".global pi_embedded_kernels\n"
-    "pi_embedded_kernels:\n"
-    ".incbin \"" PI_CSRC_DIR "/pi_sweep_kernels.hip\"\n"
-    ".byte 0\n"
-    ".global pi_embedded_onelaunch\n"
-    "pi_embedded_onelaunch:\n"
-    ".incbin \"" PI_CSRC_DIR "/pi_onelaunch_kernels.hip\"\n"
-    ".byte 0\n"
-    ".global pi_embedded_math\n"
-    "pi_embedded_math:\n"
-    ".incbin \"" PI_INCLUDE_DIR "/pi_math.h\"\n"
-    ".byte 0\n"
-    ".global pi_embedded_push\n"
-    "pi_embedded_push:\n"
-    ".incbin \"" PI_CSRC_DIR "/pi_push_kernels.hip\"\n"
-    ".byte 0\n"
-    ".text\n");
-extern "C" const char pi_embedded_kernels[];
-extern "C" const char pi_embedded_onelaunch[];
-extern "C" const char pi_embedded_math[];
-extern "C" const char pi_embedded_push[];
 
 namespace pi {
 
@@ -56,132 +17,12 @@ int fail(const std::string& msg) {
 }
 const std::string& last_error() { return g_error; }
 
-}  // namespace pi
-
-using pi::fail;
-using pi::kSlots;
-using pi::kXcds;
-
-namespace {
-
-const char* const kArch = "gfx950";
-constexpr int kXcdCtlWords = 128 + 256;   // control block of the XCD-local kernel: PI_XCD_CTL_FLAGS + 2 banks x 64 flag granules
-const char* const kCompileFlags[] = {"--offload-arch=gfx950", "-O3", "-ffp-contract=off",
-                                     "-std=c++17"};
-
 int env_int(const char* name, int dflt, int lo, int hi) {
     if (const char* e = std::getenv(name)) {
         const int v = std::atoi(e);
         if (v >= lo && v <= hi) return v;
     }
     return dflt;
-}
-
-uint64_t fnv1a(const std::string& s, uint64_t h) {
-    for (unsigned char c : s) {
-        h ^= c;
-        h *= 1099511628211ull;
-    }
-    return h;
-}
-
-float bits_to_float(uint32_t u) {
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-uint32_t float_to_bits(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    return u;
-}
-
-// ---- exact division by a constant through its reciprocal --------------------------------
-// The interpolation computes (s - lo) / span with span fixed per dimension.  The kernels replace
-// the IEEE division by  t = a * y;  r = fma(-t, span, a);  q = fma(r, y, t)  with y = RN(1/span).
-// That is the IEEE quotient for "almost all" operands (Markstein), but not provably for all, so
-// it is enabled per divisor only after this exhaustive check: every one of the 2^23 float32
-// significands of the dividend (the sequence is invariant under scaling the dividend by a power
-// of two as long as nothing leaves the normal range, which the kernel guards, and under its sign).
-__attribute__((target("fma"))) bool divisor_exact_fma(float span, float y) {
-    for (uint32_t m = 0; m < (1u << 23); ++m) {
-        const float a = bits_to_float(0x3F800000u | m);
-        const float t = a * y;
-        const float r = __builtin_fmaf(-t, span, a);
-        const float q = __builtin_fmaf(r, y, t);
-        if (q != a / span) return false;
-    }
-    return true;
-}
-bool divisor_exact_libm(float span, float y) {
-    for (uint32_t m = 0; m < (1u << 23); ++m) {
-        const float a = bits_to_float(0x3F800000u | m);
-        const float t = a * y;
-        const float r = std::fmaf(-t, span, a);
-        const float q = std::fmaf(r, y, t);
-        if (q != a / span) return false;
-    }
-    return true;
-}
-bool validate_fast_division(float span) {
-    if (!(span >= 0x1p-30f && span <= 0x1p30f)) return false;
-    static std::mutex mu;
-    static std::map<uint32_t, bool> memo;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = memo.find(float_to_bits(span));
-    if (it != memo.end()) return it->second;
-    const float y = 1.0f / span;
-    const bool ok = __builtin_cpu_supports("fma") ? divisor_exact_fma(span, y) : divisor_exact_libm(span, y);
-    memo[float_to_bits(span)] = ok;
-    return ok;
-}
-
-std::string hex_float(float v) {
-    char buf[64];
-    std::snprintf(buf, sizeof buf, "%af", (double)v);
-    return buf;
-}
-template <typename T, typename F>
-std::string brace_list(const std::vector<T>& v, F fmt) {
-    std::string r = "{";
-    for (size_t i = 0; i < v.size(); ++i) r += (i ? "," : "") + fmt(v[i]);
-    return r + "}";
-}
-
-std::string build_source(const pi_handle* h, const char* dynamics_src) {
-    std::ostringstream o;
-    o << "// generated by libpi_mi355 for " << kArch << "\n";
-    o << "#define PI_BLOCK_EVAL " << h->block_eval << "\n";
-    o << "#define PI_BLOCK_IMPROVE " << h->block_improve << "\n";
-    o << "#define PI_RESIDENT_K " << h->resident_k << "\n";
-    o << "#define PI_RESIDENT_BLOCK " << h->resident_block << "\n";
-    if (h->flow) o << "#define PI_FLOW 1\n#define PI_FLOW_BLOCK " << h->flow_block << "\n";
-    if (h->xcd) o << "#define PI_XCD 1\n#define PI_XCD_S " << h->xcd_states << "\n#define PI_XCD_RING " << h->xcd_ring
-                  << "\n#define PI_XCD_HOST_CTL_WORDS " << kXcdCtlWords << "\n";
-    if (h->xcd && std::getenv("PI_MI355_XCD_FIRST_SLEEP")) o << "#define PI_XCD_FIRST_SLEEP " << env_int("PI_MI355_XCD_FIRST_SLEEP", 8, 0, 127) << "\n";
-    if (h->xcd && std::getenv("PI_MI355_XCD_TIMING")) o << "#define PI_XCD_TIMING 1\n";      // cycles per phase into the control block
-    if (h->debug_bounds) o << "#define PI_DEBUG_BOUNDS 1\n";
-    o << "#define PI_D " << h->D << "\n";
-    o << "#define PI_NA " << h->n_actions << "\n";
-    o << "#define PI_GRID_INIT " << brace_list(h->shape, [](int32_t x) { return std::to_string(x); }) << "\n";
-    o << "#define PI_LO_INIT " << brace_list(h->lo, hex_float) << "\n";
-    o << "#define PI_SPAN_INIT " << brace_list(h->span, hex_float) << "\n";
-    o << "#define PI_RCP_INIT " << brace_list(h->rcp, hex_float) << "\n";
-    o << "#define PI_FASTDIV_INIT " << brace_list(h->fastdiv, [](int x) { return std::to_string(x); }) << "\n";
-    o << "#define PI_MEM_OF_INIT " << brace_list(h->mem_of_user, [](int x) { return std::to_string(x); }) << "\n";
-    o << pi_embedded_math << "\n";
-    o << "#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n";
-    o << "// ---- env plugin (user string) ----\n";
-    o << dynamics_src << "\n";
-    o << "// ---- sweep kernels ----\n";
-    o << pi_embedded_kernels << "\n";
-    // the one-launch kernels of launch-bound grids (csrc/pi_onelaunch_kernels.hip): only where the grid qualifies, so
-    // the translation units of the big grids stay ~1 000 lines shorter
-    if (h->resident_k > 0 || h->flow || h->xcd) {
-        o << "// ---- one-launch kernels ----\n";
-        o << pi_embedded_onelaunch << "\n";
-    }
-    return o.str();
 }
 
 // The strip period the sweeps of this handle use (PiSched): strip_mode > 0 as given, 0 none, -1 the library's choice,
@@ -209,79 +50,6 @@ void drop_graphs(pi_handle* h) {
     h->graphs.clear();
 }
 
-int load_module(pi_handle* h, const std::vector<char>& image) {
-    if (h->device < 0) return 0;   // host-only handle: compile check only
-    pi::DeviceGuard guard(h->device);
-    drop_graphs(h);
-    if (h->module) {
-        PI_HIP(hipModuleUnload(h->module));
-        h->module = nullptr;
-    }
-    if (h->module_push) {
-        PI_HIP(hipModuleUnload(h->module_push));
-        h->module_push = nullptr;
-        h->f_eval_push = nullptr;
-        h->f_reach_pairs = nullptr;
-    }
-    PI_HIP(hipModuleLoadData(&h->module, image.data()));
-    PI_HIP(hipModuleGetFunction(&h->f_eval, h->module, "pi_eval_sweep_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_eval_live, h->module, "pi_eval_live_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_policy_list, h->module, "pi_policy_list_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_scan_slots, h->module, "pi_scan_slots_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_mask_list, h->module, "pi_mask_list_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_improve, h->module, "pi_improve_sweep_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_improve_live, h->module, "pi_improve_live_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_value, h->module, "pi_value_sweep_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_finalize, h->module, "pi_finalize_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_reach_planes, h->module, "pi_reach_planes_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_reach_units, h->module, "pi_reach_units_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_probe_step, h->module, "pi_probe_step_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_probe_interp, h->module, "pi_probe_interp_kernel"));
-    PI_HIP(hipModuleGetFunction(&h->f_probe_coords, h->module, "pi_probe_coords_kernel"));
-    h->f_run_resident = nullptr;
-    if (h->resident_k > 0) {
-        PI_HIP(hipModuleGetFunction(&h->f_resident, h->module, "pi_eval_resident_kernel"));
-        PI_HIP(hipModuleGetFunction(&h->f_run_resident, h->module, "pi_run_resident_kernel"));
-    }
-    h->f_flow = h->f_flow_finish = nullptr;
-    if (h->flow) {
-        PI_HIP(hipModuleGetFunction(&h->f_flow, h->module, "pi_eval_flow_kernel"));
-        PI_HIP(hipModuleGetFunction(&h->f_flow_finish, h->module, "pi_flow_finish_kernel"));
-        // the kernel's workgroups wait for each other: all of them have to be resident at once.  The occupancy API may
-        // answer 1-2 more per CU than the hardware admits (SGPR granules: MI355X_MICROARCH.md, "Residency"): margin.
-        int per_cu = 0;
-        const int64_t wgs = (h->n_states + h->flow_block - 1) / h->flow_block;
-        if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->f_flow, h->flow_block, 0) != hipSuccess ||
-            (int64_t)(per_cu * 3 / 4) * h->num_cu < wgs) {
-            (void)hipGetLastError();
-            h->f_flow = nullptr;
-        }
-    }
-    h->f_xcd = h->f_xcd_finish = nullptr;
-    if (h->xcd && h->f_flow) {
-        PI_HIP(hipModuleGetFunction(&h->f_xcd, h->module, "pi_xcd_kernel"));
-        PI_HIP(hipModuleGetFunction(&h->f_xcd_finish, h->module, "pi_xcd_finish_kernel"));
-        // one workgroup per CU of one XCD, all resident at once: the kernel's LDS padding keeps a second one off a CU
-        int regs = 0, lds = 0;
-        const int64_t wgs = (h->n_states + h->xcd_states - 1) / h->xcd_states, cus = h->num_cu / kXcds, per_cu = 1;
-        const bool ok = hipFuncGetAttribute(&regs, HIP_FUNC_ATTRIBUTE_NUM_REGS, h->f_xcd) == hipSuccess &&
-                        hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, h->f_xcd) == hipSuccess &&
-                        wgs <= cus && lds > 80 * 1024 && lds <= 160 * 1024 && regs <= 128;
-        if (std::getenv("PI_MI355_XCD_TRACE"))
-            std::fprintf(stderr, "[pi] xcd kernel: regs %d lds %d wgs %lld cus %lld per_cu %lld ok %d\n", regs, lds, (long long)wgs,
-                         (long long)cus, (long long)per_cu, (int)ok);
-        if (!ok) {
-            (void)hipGetLastError();
-            h->f_xcd = nullptr;
-        }
-    }
-    int v = 0;
-    if (hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_NUM_REGS, h->f_eval) == hipSuccess) h->vgpr_eval = v;
-    if (hipFuncGetAttribute(&v, HIP_FUNC_ATTRIBUTE_NUM_REGS, h->f_improve) == hipSuccess)
-        h->vgpr_improve = v;
-    return 0;
-}
-
 // Workgroups for a range: one per group of `cpw` chunks, rounded up so that every XCD gets the
 // same number (the kernels' chunk schedule deals groups to XCDs in contiguous runs).
 unsigned launch_blocks(int block, int64_t count, int cpw) {
@@ -290,10 +58,6 @@ unsigned launch_blocks(int block, int64_t count, int cpw) {
     const int64_t span = (groups + kXcds - 1) / kXcds;
     return (unsigned)std::max<int64_t>(span * kXcds, kXcds);
 }
-
-}  // namespace
-
-namespace pi {
 
 // The schedule of one sweep launch over `count` units (states of a range, or entries of a state list) starting at unit
 // `first` of `total` units that stand for the handle's whole grid (a list of live states: its length; a state range: n).
@@ -325,213 +89,56 @@ Grid2 plan_launch(const pi_handle* h, int block, int64_t first, int64_t count, i
 
 }  // namespace pi
 
-namespace {
+using namespace pi;
 
-using pi::Sched;
-using pi::plan_launch;
+namespace {
 
 unsigned int* delta_slots(pi_handle* h) { return h->d_slots; }
 unsigned int* changed_slots(pi_handle* h) { return h->d_slots + kSlots; }
 
-}  // namespace
-
-namespace pi {
-
-int check_ready(const pi_handle* h) {
-    if (!h) return fail("null handle");
-    if (h->device < 0) return fail("host-only handle (device = -1) cannot launch kernels");
-    if (!h->module) return fail("pi_compile has not been called on this handle");
+// empty range: zero whichever of the outputs were given, nothing to launch
+int zero_outputs(float* d_delta, uint32_t* d_changed, hipStream_t st) {
+    if (d_delta) PI_HIP(hipMemsetAsync(d_delta, 0, sizeof(float), st));
+    if (d_changed) PI_HIP(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), st));
     return 0;
 }
 
-int check_range(const pi_handle* h, int64_t s_begin, int64_t s_end) {
-    if (s_begin < 0 || s_end < s_begin || s_end > h->n_states)
-        return fail("state range [" + std::to_string(s_begin) + ", " + std::to_string(s_end) +
-                    ") outside [0, " + std::to_string(h->n_states) + ")");
-    return 0;
+// Everything the handle owns on its device (pi_destroy, and pi_create when an allocation fails)
+void free_device_state(pi_handle* h) {
+    drop_graphs(h);
+    if (h->module) (void)hipModuleUnload(h->module);
+    if (h->module_push) (void)hipModuleUnload(h->module_push);
+    for (void* p : {(void*)h->d_tab, (void*)h->d_slots, (void*)h->d_live, (void*)h->d_eval_list, (void*)h->d_eval_cursor,
+                    h->d_flow, h->d_xcd})
+        if (p) (void)hipFree(p);
 }
 
-int finalize(pi_handle* h, float* d_delta, uint32_t* d_changed, hipStream_t st) {
-    if (!d_delta && !d_changed) return 0;
-    unsigned int* ds = d_delta ? delta_slots(h) : nullptr;
-    unsigned int* cs = d_changed ? changed_slots(h) : nullptr;
-    void* args[] = {&ds, &d_delta, &cs, &d_changed};
-    PI_HIP(hipModuleLaunchKernel(h->f_finalize, 1, 1, 1, 64, 1, 1, 0, st, args, nullptr));
-    return 0;
-}
-
-int launch_eval(pi_handle* h, const float* V, float* Vnew, const int32_t* policy, const uint8_t* term,
-                int64_t s_begin, int64_t s_end, float gamma, bool want_delta, hipStream_t st,
-                bool keep_terminals) {
-    if (s_end == s_begin) return 0;
-    long long b = s_begin, e = s_end;
-    const float* tab = h->d_tab;
-    unsigned int* dbits = want_delta ? delta_slots(h) : nullptr;
-    Sched sc;
-    const pi::Grid2 blocks = plan_launch(h, h->block_eval, s_begin, s_end - s_begin, h->n_states, h->cpw_eval, &sc);
-    int keep = keep_terminals ? 1 : 0;
-    void* args[] = {&V, &Vnew, &policy, &term, &tab, &b, &e, &gamma, &dbits, &sc, &keep};
-    PI_HIP(hipModuleLaunchKernel(h->f_eval, blocks.x, blocks.y, 1, h->block_eval, 1, 1, 0, st, args, nullptr));
-    return 0;
-}
-
-bool live_usable(const pi_handle* h, const uint8_t* term, int64_t s_begin, int64_t s_end) {
-    return h->live_count > 0 && term != nullptr && term == h->live_term && s_begin >= h->live_lo && s_end <= h->live_hi;
-}
-
-void live_span(const pi_handle* h, int64_t s_begin, int64_t s_end, int64_t* first, int64_t* count) {
-    const int64_t word0 = h->live_lo >> 6;
-    auto position = [&](int64_t s) {                      // listed live states below s
-        if (s <= h->live_lo) return int64_t(0);
-        if (s >= h->live_hi) return h->live_count;
-        const uint64_t word = h->live_bits[(size_t)((s >> 6) - word0)];
-        const uint64_t below = (s & 63) ? word & ((uint64_t(1) << (s & 63)) - 1) : 0;
-        return h->live_before[(size_t)((s >> 6) - word0)] + (int64_t)__builtin_popcountll(below);
-    };
-    *first = position(s_begin);
-    *count = position(s_end) - *first;
-}
-
-void live_states(const pi_handle* h, int64_t s_begin, int64_t s_end, std::vector<int32_t>& out) {
-    const int64_t a = std::max(s_begin, h->live_lo), b = std::min(s_end, h->live_hi);
-    const int64_t word0 = h->live_lo >> 6;
-    for (int64_t w = a >> 6; w <= (b - 1) >> 6 && a < b; ++w) {
-        uint64_t word = h->live_bits[(size_t)(w - word0)];
-        while (word) {
-            const int bit = __builtin_ctzll(word);
-            word &= word - 1;
-            const int64_t s = (w << 6) + bit;
-            if (s >= a && s < b) out.push_back((int32_t)s);
-        }
+// pi_create, step 3: the tables and the accumulator slots on the device, the number of CUs
+int allocate_device_state(pi_handle* h) {
+    h->num_cu = 256;
+    if (h->device < 0) return 0;
+    pi::DeviceGuard guard(h->device);
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties(&prop, h->device);
+    if (e == hipSuccess && std::string(prop.gcnArchName).rfind(pi::kArch, 0) != 0)
+        return fail(std::string("pi_create: device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_tab, h->tab.size() * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(h->d_tab, h->tab.data(), h->tab.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_slots, 2 * kSlots * sizeof(unsigned int));
+    if (e == hipSuccess) e = hipMemset(h->d_slots, 0, 2 * kSlots * sizeof(unsigned int));
+    if (e != hipSuccess) {
+        free_device_state(h);
+        return fail(std::string("pi_create: ") + hipGetErrorString(e));
     }
-}
-
-// What a list of `entries` states spread over the listed range [live_lo, live_hi) would have over the whole grid
-// (plan_launch's `total`: the strip schedule cuts a list into the same shares as the planes it stands for).
-int64_t live_list_total(const pi_handle* h, int64_t entries) {
-    const int64_t range = h->live_hi - h->live_lo;
-    if (range <= 0 || entries <= 0) return 0;
-    return (int64_t)((double)entries * ((double)h->n_states / (double)range));
-}
-
-// One evaluation sweep over `count` entries of the list of live states from position `first` (pi_prepare_mask): a
-// sweep that need not copy terminal values.
-void drop_eval_list(pi_handle* h) {
-    h->eval_count = -1;
-    h->eval_policy = nullptr;
-    h->eval_holds.clear();
-}
-
-int launch_eval_live(pi_handle* h, const float* V, float* Vnew, const int32_t* policy, int64_t first, int64_t count,
-                     float gamma, bool want_delta, hipStream_t st, const int32_t* list, int64_t list_total) {
-    if (count <= 0) return 0;
-    const int32_t* live = (list ? list : h->d_live) + first;
-    if (!list) list_total = live_list_total(h, h->live_count);
-    long long cnt = count;
-    const float* tab = h->d_tab;
-    unsigned int* dbits = want_delta ? delta_slots(h) : nullptr;
-    // a list the caller passes (the per-evaluation list, the lists of an exchange plan) is some subset of the live
-    // states in ascending order: its periods are the same share of ITS length only when it covers the listed range
-    Sched sc;
-    const pi::Grid2 blocks = plan_launch(h, h->block_eval, first, count, list_total, h->cpw_eval, &sc);
-    void* args[] = {&V, &Vnew, &policy, &live, &tab, &cnt, &gamma, &dbits, &sc};
-    PI_HIP(hipModuleLaunchKernel(h->f_eval_live, blocks.x, blocks.y, 1, h->block_eval, 1, 1, 0, st, args, nullptr));
+    h->num_cu = prop.multiProcessorCount;
     return 0;
 }
 
-// The handle's second module: the same translation unit + csrc/pi_push_kernels.hip, built (hipRTC, same cache) the
-// first time an exchange plan wants the fused swept-first kernel.  Nothing else ever pays for it.
-int ensure_push_module(pi_handle* h) {
-    if (h->f_eval_push) return 0;
-    if (!h->compiled || h->dynamics_src.empty()) return fail("ensure_push_module: pi_compile has not run on this handle");
-    std::vector<char> image;
-    const std::string src = build_source(h, h->dynamics_src.c_str()) + "// ---- fused swept-first kernel ----\n" + pi_embedded_push + "\n";
-    if (compile_image(src, h->has_cache_dir ? h->cache_dir.c_str() : nullptr, nullptr, 0, image, nullptr)) return 1;
-    if (h->device < 0) return 0;            // host-only handle: compile check only
-    DeviceGuard guard(h->device);
-    PI_HIP(hipModuleLoadData(&h->module_push, image.data()));
-    PI_HIP(hipModuleGetFunction(&h->f_eval_push, h->module_push, "pi_eval_push_kernel"));
-    if (h->D >= 3) PI_HIP(hipModuleGetFunction(&h->f_reach_pairs, h->module_push, "pi_reach_pairs_kernel"));
-    return 0;
-}
-
-bool pairs_possible(const pi_handle* h) {
-    return h->D >= 3 && h->mem_of_user[0] == 0 && (int64_t)h->shape[0] * h->shape[h->mem_of_user[1]] <= (int64_t(1) << 17);
-}
-
-int reach_pairs(pi_handle* h, const uint8_t* term, int64_t s_begin, int64_t s_end, uint32_t* d_bitmap, hipStream_t st) {
-    if (!pairs_possible(h)) return fail("reach_pairs: needs 3 or more dimensions, dimension 0 slowest and g_0 * g_v <= 2^17");
-    if (ensure_push_module(h)) return 1;
-    if (s_end <= s_begin) return 0;
-    const float* tab = h->d_tab;
-    long long a = s_begin, b = s_end;
-    int cpw = 4;
-    void* args[] = {&term, &tab, &a, &b, &d_bitmap, &cpw};
-    PI_HIP(hipModuleLaunchKernel(h->f_reach_pairs, launch_blocks(kProbeBlock, s_end - s_begin, cpw), 1, 1, kProbeBlock, 1, 1, 0,
-                                 st, args, nullptr));
-    return 0;
-}
-
-int launch_eval_push(pi_handle* h, const float* V, float* Vnew, const int32_t* policy, const int32_t* list,
-                     const uint8_t* dest, float* const* d_peers, int n_peers, int64_t count, float gamma, bool want_delta,
-                     hipStream_t st) {
-    if (count <= 0) return 0;
-    if (ensure_push_module(h)) return 1;
-    long long cnt = count;
-    const float* tab = h->d_tab;
-    unsigned int* dbits = want_delta ? delta_slots(h) : nullptr;
-    int cpw = h->cpw_eval;
-    void* args[] = {&V, &Vnew, &policy, &list, &dest, &d_peers, &n_peers, &tab, &cnt, &gamma, &dbits, &cpw};
-    PI_HIP(hipModuleLaunchKernel(h->f_eval_push, launch_blocks(h->block_eval, count, cpw), 1, 1, h->block_eval, 1, 1, 0,
-                                 st, args, nullptr));
-    return 0;
-}
-
-}  // namespace pi
-
-using pi::check_range;
-using pi::check_ready;
-
-extern "C" {
-
-int pi_abi_version(void) { return PI_MI355_ABI_VERSION; }
-
-const char* pi_last_error(void) { return pi::last_error().c_str(); }
-
-pi_handle* pi_create(int device, int D, const int32_t* grid_shape, const float* lo,
-                     const float* hi, const float* const* bins, const float* actions,
-                     int n_actions) {
-    pi::fail("");
-    if (D != 2 && D != 4 && D != 6) { fail("D must be 2, 4 or 6"); return nullptr; }
-    if (n_actions < 1) { fail("need at least one action"); return nullptr; }
-    if (!grid_shape || !lo || !hi || !bins || !actions) { fail("null argument"); return nullptr; }
-    std::unique_ptr<pi_handle> h(new pi_handle);
-    h->device = device;
-    h->D = D;
-    h->n_actions = n_actions;
-    h->shape.assign(grid_shape, grid_shape + D);
-    for (int d = 0; d < D; ++d) { h->mem_of_user.push_back(d); h->user_of_mem.push_back(d); }
-    int64_t n = 1;
-    for (int d = 0; d < D; ++d) {
-        if (grid_shape[d] < 2) { fail("every dimension needs at least 2 bins"); return nullptr; }
-        n *= grid_shape[d];
-        if (n >= (int64_t(1) << 31)) { fail("n_states must be < 2^31"); return nullptr; }
-    }
-    h->n_states = n;
-    for (int d = 0; d < D; ++d) {
-        const float span = hi[d] - lo[d];            // float32 subtraction, as the reference's kernels
-        h->lo.push_back(lo[d]);
-        h->span.push_back(span);
-        h->rcp.push_back(1.0f / span);
-        h->fastdiv.push_back(validate_fast_division(span) ? 1 : 0);
-    }
-    if (std::getenv("PI_MI355_IEEE_DIV")) std::fill(h->fastdiv.begin(), h->fastdiv.end(), 0);
-    h->tab.insert(h->tab.end(), actions, actions + n_actions);
-    for (int d = 0; d < D; ++d) h->tab.insert(h->tab.end(), bins[d], bins[d] + grid_shape[d]);
-    if (h->tab.size() * sizeof(float) > 60 * 1024) {
-        fail("bin tables + actions exceed the 60 KiB LDS budget of the sweep kernels");
-        return nullptr;
-    }
+// pi_create, step 2: every launch-geometry and one-launch decision for this grid, with every knob that bears on one.
+// tests/test_edge_dispatch.py pins the outcome (helpers.DISPATCH_TABLE).
+void choose_dispatch(pi_handle* h) {
+    const int D = h->D;
+    const int64_t n = h->n_states;
     // Launch geometry (profiles/r02/block_cpw_sweep.txt): big 4-D grids sweep best with 1024-thread
     // workgroups taking two chunks each (evaluation: the 16 waves' corner rows overlap in one L1)
     // and 512-thread ones taking one (improvement); 6-D grids (64 corners, register-heavy) and
@@ -581,134 +188,7 @@ pi_handle* pi_create(int device, int D, const int32_t* grid_shape, const float* 
     h->xcd = h->flow && xcd_wanted;
     h->xcd_ring = env_int("PI_MI355_XCD_RING", 64, 4, 1024);
     h->xcd_states = (int)(((n + 31) / 32 + 31) / 32 * 32);  // states per workgroup: n over 32 CUs, whole 128-byte lines
-    if (device >= 0) {
-        pi::DeviceGuard guard(device);
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDeviceProperties(&prop, device);
-        if (e == hipSuccess && std::string(prop.gcnArchName).rfind(kArch, 0) != 0) {
-            fail(std::string("pi_create: device is ") + prop.gcnArchName +
-                 ", this library is built for gfx950 only");
-            return nullptr;
-        }
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_tab, h->tab.size() * sizeof(float));
-        if (e == hipSuccess)
-            e = hipMemcpy(h->d_tab, h->tab.data(), h->tab.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc((void**)&h->d_slots, 2 * kSlots * sizeof(unsigned int));
-        if (e == hipSuccess) e = hipMemset(h->d_slots, 0, 2 * kSlots * sizeof(unsigned int));
-        if (e != hipSuccess) {
-            fail(std::string("pi_create: ") + hipGetErrorString(e));
-            if (h->d_tab) (void)hipFree(h->d_tab);
-            if (h->d_slots) (void)hipFree(h->d_slots);
-            return nullptr;
-        }
-        h->num_cu = prop.multiProcessorCount;
-    } else {
-        h->num_cu = 256;
-    }
-    return h.release();
 }
-
-void pi_destroy(pi_handle* h) {
-    if (!h) return;
-    if (h->device >= 0) {
-        pi::DeviceGuard guard(h->device);
-        pi::release_comm(h);
-        drop_graphs(h);
-        if (h->module) (void)hipModuleUnload(h->module);
-        if (h->module_push) (void)hipModuleUnload(h->module_push);
-        if (h->d_tab) (void)hipFree(h->d_tab);
-        if (h->d_slots) (void)hipFree(h->d_slots);
-        if (h->d_live) (void)hipFree(h->d_live);
-        if (h->d_eval_list) (void)hipFree(h->d_eval_list);
-        if (h->d_eval_cursor) (void)hipFree(h->d_eval_cursor);
-        if (h->d_flow) (void)hipFree(h->d_flow);
-        if (h->d_xcd) (void)hipFree(h->d_xcd);
-    }
-    delete h;
-}
-
-size_t pi_kernel_source(pi_handle* h, const char* dynamics_src, char* buf, size_t buf_len) {
-    if (!h || !dynamics_src) return 0;
-    std::string s = build_source(h, dynamics_src);
-    if (buf && buf_len) {
-        size_t k = std::min(buf_len - 1, s.size());
-        std::memcpy(buf, s.data(), k);
-        buf[k] = 0;
-    }
-    return s.size();
-}
-
-}  // extern "C"
-
-namespace pi {
-
-// hipRTC (or the on-disk cache) -> code object image for one translation unit.
-int compile_image(const std::string& src, const char* cache_dir, char* log, size_t log_len,
-                  std::vector<char>& image, bool* cache_hit) {
-    std::string flags;
-    for (const char* f : kCompileFlags) { flags += f; flags += ' '; }
-    int rtc_major = 0, rtc_minor = 0;                     // a new compiler invalidates the cache
-    (void)hiprtcVersion(&rtc_major, &rtc_minor);
-    flags += "hiprtc-" + std::to_string(rtc_major) + "." + std::to_string(rtc_minor);
-    char name[64];
-    std::snprintf(name, sizeof name, "pi_%016llx%016llx.hsaco",
-                  (unsigned long long)fnv1a(src + flags, 14695981039346656037ull),
-                  (unsigned long long)fnv1a(flags + src, 0x9e3779b97f4a7c15ull));
-    std::string path;
-    if (cache_hit) *cache_hit = false;
-    if (cache_dir && cache_dir[0]) {
-        path = std::string(cache_dir) + "/" + name;
-        std::ifstream f(path, std::ios::binary);
-        if (f) {
-            image.assign((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-            if (!image.empty()) {
-                if (cache_hit) *cache_hit = true;
-                return 0;
-            }
-        }
-    }
-    hiprtcProgram prog;
-    if (hiprtcCreateProgram(&prog, src.c_str(), "pi_sweep_kernels.hip", 0, nullptr, nullptr) !=
-        HIPRTC_SUCCESS)
-        return fail("hiprtcCreateProgram failed");
-    const int n_flags = (int)(sizeof kCompileFlags / sizeof kCompileFlags[0]);
-    hiprtcResult rc = hiprtcCompileProgram(prog, n_flags, const_cast<const char**>(kCompileFlags));
-    size_t ls = 0;
-    std::string clog;
-    if (hiprtcGetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) {
-        clog.resize(ls);
-        (void)hiprtcGetProgramLog(prog, &clog[0]);
-    }
-    if (log && log_len) std::snprintf(log, log_len, "%s", clog.c_str());
-    if (rc != HIPRTC_SUCCESS) {
-        (void)hiprtcDestroyProgram(&prog);
-        return fail(std::string("hipRTC compile failed: ") + hiprtcGetErrorString(rc) + "\n" + clog);
-    }
-    size_t cs = 0;
-    if (hiprtcGetCodeSize(prog, &cs) != HIPRTC_SUCCESS || cs == 0) {
-        (void)hiprtcDestroyProgram(&prog);
-        return fail("hiprtcGetCodeSize failed");
-    }
-    image.resize(cs);
-    hiprtcResult rg = hiprtcGetCode(prog, image.data());
-    (void)hiprtcDestroyProgram(&prog);
-    if (rg != HIPRTC_SUCCESS) return fail("hiprtcGetCode failed");
-    if (!path.empty()) {
-        (void)mkdir(cache_dir, 0777);
-        std::string tmp = path + ".tmp" + std::to_string((long long)getpid());
-        std::ofstream f(tmp, std::ios::binary);
-        if (f) {
-            f.write(image.data(), (std::streamsize)image.size());
-            f.close();
-            if (std::rename(tmp.c_str(), path.c_str()) != 0) (void)std::remove(tmp.c_str());
-        }
-    }
-    return 0;
-}
-
-}  // namespace pi
-
-namespace {
 
 // A batch of evaluation sweeps as one hipGraph (kernel nodes built explicitly, so it also works
 // when the caller's stream is the legacy default stream, where stream capture is not allowed).
@@ -721,41 +201,11 @@ int build_eval_graph(pi_handle* h, float* Va, float* Vb, const int32_t* policy, 
     PI_HIP(hipGraphCreate(&graph, 0));
     hipGraphNode_t prev = nullptr;
     int rc = 0;
-    long long b = s_begin, e = s_end;
-    const float* tab = h->d_tab;
-    Sched sc;
-    const pi::Grid2 blocks = plan_launch(h, h->block_eval, s_begin, s_end - s_begin, h->n_states, h->cpw_eval, &sc);
-    for (int i = 0; i < n_sweeps && !rc; ++i) {
-        const float* src = (i & 1) ? Vb : Va;
-        float* dst = (i & 1) ? Va : Vb;
-        unsigned int* dbits = (i == n_sweeps - 1 && d_delta) ? delta_slots(h) : nullptr;
-        int keep = i >= 1 ? 1 : 0;       // sweep 0 copies the terminal values from Va into Vb; from then on both hold them
-        void* args[] = {&src, &dst, &policy, &term, &tab, &b, &e, &gamma, &dbits, &sc, &keep};
-        hipKernelNodeParams p = {};
-        p.func = (void*)h->f_eval;
-        p.gridDim = dim3(blocks.x, blocks.y, 1);
-        p.blockDim = dim3(h->block_eval, 1, 1);
-        p.sharedMemBytes = 0;
-        p.kernelParams = args;
-        p.extra = nullptr;
-        hipGraphNode_t node;
-        if (hipGraphAddKernelNode(&node, graph, prev ? &prev : nullptr, prev ? 1 : 0, &p) != hipSuccess)
-            rc = 1;
-        prev = node;
-    }
-    if (!rc && d_delta) {
-        unsigned int* ds = delta_slots(h);
-        unsigned int* cs = nullptr;
-        uint32_t* dc = nullptr;
-        void* args[] = {&ds, &d_delta, &cs, &dc};
-        hipKernelNodeParams p = {};
-        p.func = (void*)h->f_finalize;
-        p.gridDim = dim3(1, 1, 1);
-        p.blockDim = dim3(64, 1, 1);
-        p.kernelParams = args;
-        hipGraphNode_t node;
-        if (hipGraphAddKernelNode(&node, graph, &prev, 1, &p) != hipSuccess) rc = 1;
-    }
+    // sweep 0 copies the terminal values from Va into Vb; from then on both hold them
+    for (int i = 0; i < n_sweeps && !rc; ++i)
+        rc = pi::launch_eval(h, (i & 1) ? Vb : Va, (i & 1) ? Va : Vb, policy, term, s_begin, s_end, gamma,
+                             i == n_sweeps - 1 && d_delta, pi::LaunchTo(graph, &prev), i >= 1);
+    if (!rc) rc = pi::finalize(h, d_delta, nullptr, pi::LaunchTo(graph, &prev));
     if (!rc && hipGraphInstantiate(out, graph, nullptr, nullptr, 0) != hipSuccess) rc = 1;
     (void)hipGraphDestroy(graph);
     if (rc) {
@@ -767,21 +217,121 @@ int build_eval_graph(pi_handle* h, float* Va, float* Vb, const int32_t* policy, 
 
 }  // namespace
 
+int pi::check_ready(const pi_handle* h) {
+    if (!h) return fail("null handle");
+    if (h->device < 0) return fail("host-only handle (device = -1) cannot launch kernels");
+    if (!h->module) return fail("pi_compile has not been called on this handle");
+    return 0;
+}
+
+int pi::check_range(const pi_handle* h, int64_t s_begin, int64_t s_end) {
+    if (s_begin < 0 || s_end < s_begin || s_end > h->n_states)
+        return fail("state range [" + std::to_string(s_begin) + ", " + std::to_string(s_end) +
+                    ") outside [0, " + std::to_string(h->n_states) + ")");
+    return 0;
+}
+
+// The one place pi_finalize_kernel's arguments are written out (eager, or the last node of an evaluation graph).
+int pi::finalize(pi_handle* h, float* d_delta, uint32_t* d_changed, LaunchTo to) {
+    if (!d_delta && !d_changed) return 0;
+    PI_HIP(launch(h->f_finalize, {1, 1}, 64, to, d_delta ? delta_slots(h) : (unsigned int*)nullptr, d_delta,
+                  d_changed ? changed_slots(h) : (unsigned int*)nullptr, d_changed));
+    return 0;
+}
+
+// The one place pi_eval_sweep_kernel's arguments are written out (eager, or a node of an evaluation graph).
+int pi::launch_eval(pi_handle* h, const float* V, float* Vnew, const int32_t* policy, const uint8_t* term,
+                int64_t s_begin, int64_t s_end, float gamma, bool want_delta, LaunchTo to, bool keep_terminals) {
+    if (s_end == s_begin) return 0;
+    Sched sc;
+    const Grid2 blocks = plan_launch(h, h->block_eval, s_begin, s_end - s_begin, h->n_states, h->cpw_eval, &sc);
+    PI_HIP(launch(h->f_eval, blocks, h->block_eval, to, V, Vnew, policy, term, (const float*)h->d_tab, (long long)s_begin,
+                  (long long)s_end, gamma, want_delta ? delta_slots(h) : (unsigned int*)nullptr, sc, keep_terminals ? 1 : 0));
+    return 0;
+}
+
+// One evaluation sweep over `count` entries of the list of live states from position `first` (pi_prepare_mask): a
+// sweep that need not copy terminal values.
+int pi::launch_eval_live(pi_handle* h, const float* V, float* Vnew, const int32_t* policy, int64_t first, int64_t count,
+                     float gamma, bool want_delta, hipStream_t st, const int32_t* list, int64_t list_total) {
+    if (count <= 0) return 0;
+    const int32_t* live = (list ? list : h->d_live) + first;
+    if (!list) list_total = live_list_total(h, h->live_count);
+    // a list the caller passes (the per-evaluation list, the lists of an exchange plan) is some subset of the live
+    // states in ascending order: its periods are the same share of ITS length only when it covers the listed range
+    Sched sc;
+    const pi::Grid2 blocks = plan_launch(h, h->block_eval, first, count, list_total, h->cpw_eval, &sc);
+    PI_HIP(launch(h->f_eval_live, blocks, h->block_eval, st, V, Vnew, policy, live, (const float*)h->d_tab, (long long)count, gamma,
+                  want_delta ? delta_slots(h) : (unsigned int*)nullptr, sc));
+    return 0;
+}
+
+int pi::launch_eval_push(pi_handle* h, const float* V, float* Vnew, const int32_t* policy, const int32_t* list,
+                     const uint8_t* dest, float* const* d_peers, int n_peers, int64_t count, float gamma, bool want_delta,
+                     hipStream_t st) {
+    if (count <= 0) return 0;
+    if (ensure_push_module(h)) return 1;
+    const int cpw = h->cpw_eval;
+    PI_HIP(launch(h->f_eval_push, {launch_blocks(h->block_eval, count, cpw), 1}, h->block_eval, st, V, Vnew, policy, list, dest,
+                  d_peers, n_peers, (const float*)h->d_tab, (long long)count, gamma,
+                  want_delta ? delta_slots(h) : (unsigned int*)nullptr, cpw));
+    return 0;
+}
+
 extern "C" {
 
-int pi_compile(pi_handle* h, const char* dynamics_src, const char* cache_dir, char* log,
-               size_t log_len) {
+int pi_abi_version(void) { return PI_MI355_ABI_VERSION; }
+
+const char* pi_last_error(void) { return pi::last_error().c_str(); }
+
+pi_handle* pi_create(int device, int D, const int32_t* grid_shape, const float* lo,
+                     const float* hi, const float* const* bins, const float* actions,
+                     int n_actions) {
     pi::fail("");
-    if (log && log_len) log[0] = 0;
-    if (!h || !dynamics_src) return fail("null argument");
-    std::vector<char> image;
-    if (pi::compile_image(build_source(h, dynamics_src), cache_dir, log, log_len, image, &h->cache_hit)) return 1;
-    h->compiled = true;
-    resolve_strip(h);                 // the memory order is final now
-    h->dynamics_src = dynamics_src;
-    h->has_cache_dir = cache_dir != nullptr;
-    h->cache_dir = cache_dir ? cache_dir : "";
-    return load_module(h, image);
+    // step 1: validation and the tables; step 2: choose_dispatch; step 3: allocate_device_state
+    if (D != 2 && D != 4 && D != 6) { fail("D must be 2, 4 or 6"); return nullptr; }
+    if (n_actions < 1) { fail("need at least one action"); return nullptr; }
+    if (!grid_shape || !lo || !hi || !bins || !actions) { fail("null argument"); return nullptr; }
+    std::unique_ptr<pi_handle> h(new pi_handle);
+    h->device = device;
+    h->D = D;
+    h->n_actions = n_actions;
+    h->shape.assign(grid_shape, grid_shape + D);
+    for (int d = 0; d < D; ++d) { h->mem_of_user.push_back(d); h->user_of_mem.push_back(d); }
+    int64_t n = 1;
+    for (int d = 0; d < D; ++d) {
+        if (grid_shape[d] < 2) { fail("every dimension needs at least 2 bins"); return nullptr; }
+        n *= grid_shape[d];
+        if (n >= (int64_t(1) << 31)) { fail("n_states must be < 2^31"); return nullptr; }
+    }
+    h->n_states = n;
+    for (int d = 0; d < D; ++d) {
+        const float span = hi[d] - lo[d];            // float32 subtraction, as the reference's kernels
+        h->lo.push_back(lo[d]);
+        h->span.push_back(span);
+        h->rcp.push_back(1.0f / span);
+        h->fastdiv.push_back(pi::validate_fast_division(span) ? 1 : 0);
+    }
+    if (std::getenv("PI_MI355_IEEE_DIV")) std::fill(h->fastdiv.begin(), h->fastdiv.end(), 0);
+    h->tab.insert(h->tab.end(), actions, actions + n_actions);
+    for (int d = 0; d < D; ++d) h->tab.insert(h->tab.end(), bins[d], bins[d] + grid_shape[d]);
+    if (h->tab.size() * sizeof(float) > 60 * 1024) {
+        fail("bin tables + actions exceed the 60 KiB LDS budget of the sweep kernels");
+        return nullptr;
+    }
+    choose_dispatch(h.get());
+    if (allocate_device_state(h.get())) return nullptr;
+    return h.release();
+}
+
+void pi_destroy(pi_handle* h) {
+    if (!h) return;
+    if (h->device >= 0) {
+        pi::DeviceGuard guard(h->device);
+        pi::release_comm(h);
+        free_device_state(h);
+    }
+    delete h;
 }
 
 int pi_eval_sweep(pi_handle* h, const float* V, float* Vnew, const int32_t* policy,
@@ -792,10 +342,7 @@ int pi_eval_sweep(pi_handle* h, const float* V, float* Vnew, const int32_t* poli
     if (V == Vnew) return fail("V and Vnew must be different buffers (Jacobi sweep)");
     pi::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
-    if (s_end == s_begin) {            // empty shard: residual 0, nothing to launch
-        if (d_delta) PI_HIP(hipMemsetAsync(d_delta, 0, sizeof(float), st));
-        return 0;
-    }
+    if (s_end == s_begin) return zero_outputs(d_delta, nullptr, st);   // empty shard: residual 0, nothing to launch
     if (pi::launch_eval(h, V, Vnew, policy, term, s_begin, s_end, gamma, d_delta != nullptr, st)) return 1;
     return pi::finalize(h, d_delta, nullptr, st);
 }
@@ -810,19 +357,11 @@ int pi_eval_sweeps(pi_handle* h, float* Va, float* Vb, const int32_t* policy,
     if (n_sweeps == 0) return 0;
     pi::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
-    if (s_end == s_begin) {
-        if (d_delta) PI_HIP(hipMemsetAsync(d_delta, 0, sizeof(float), st));
-        return 0;
-    }
+    if (s_end == s_begin) return zero_outputs(d_delta, nullptr, st);
     // Small grids, whole-grid batches: one workgroup keeps V in LDS and runs all the sweeps.
     if (h->f_resident && h->use_resident && n_sweeps >= 2 && s_begin == 0 && s_end == h->n_states) {
-        const float* tab = h->d_tab;
-        double theta = 0.0;
-        int interval = 1;
-        int* sweeps_out = nullptr;
-        float* log = nullptr;
-        void* args[] = {&Va, &Vb, &policy, &term, &tab, &gamma, &n_sweeps, &d_delta, &theta, &interval, &sweeps_out, &log};
-        PI_HIP(hipModuleLaunchKernel(h->f_resident, 1, 1, 1, h->resident_block, 1, 1, 0, st, args, nullptr));
+        PI_HIP(launch(h->f_resident, {1, 1}, h->resident_block, st, Va, Vb, policy, term, (const float*)h->d_tab, gamma, n_sweeps,
+                      d_delta, /*theta*/ 0.0, /*check_interval*/ 1, /*sweeps_out*/ (int*)nullptr, /*residual_log*/ (float*)nullptr));
         return 0;
     }
     // Launch-bound sizes: replay the whole batch as one graph.
@@ -840,17 +379,11 @@ int pi_eval_sweeps(pi_handle* h, float* Va, float* Vb, const int32_t* policy,
             } else {
                 if (h->graphs.size() >= 16) {    // evict the least recently used entry
                     auto lru = std::min_element(h->graphs.begin(), h->graphs.end(),
-                                                [](const pi::GraphEntry& a, const pi::GraphEntry& b) {
-                                                    return a.stamp < b.stamp;
-                                                });
+                                                [](const GraphEntry& a, const GraphEntry& b) { return a.stamp < b.stamp; });
                     (void)hipGraphExecDestroy(lru->exec);
                     h->graphs.erase(lru);
                 }
-                pi::GraphEntry g;
-                g.Va = Va; g.Vb = Vb; g.policy = policy; g.term = term; g.d_delta = d_delta;
-                g.s_begin = s_begin; g.s_end = s_end; g.gamma = gamma; g.n_sweeps = n_sweeps;
-                g.exec = exec;
-                h->graphs.push_back(g);
+                h->graphs.push_back({Va, Vb, policy, term, d_delta, s_begin, s_end, gamma, n_sweeps, exec, 0});
                 hit = &h->graphs.back();
             }
         }
@@ -889,169 +422,6 @@ int pi_eval_sweeps(pi_handle* h, float* Va, float* Vb, const int32_t* policy,
     return pi::finalize(h, d_delta, nullptr, st);
 }
 
-namespace {
-// pi_xcd_kernel + pi_xcd_finish_kernel on `st`: one policy evaluation (max_pi_iter == 0) or the whole run.  Device
-// block (owned by the handle): ring of xcd_ring (PI_XCD_RING, 64) granule versions of V (whole 128-byte lines each) |
-// scratch policy | kXcdCtlWords control words (tickets, status, result, two banks of 64 flag granules: the kernel's
-// PI_XCD_CTL_WORDS, checked against this constant by a static_assert in the generated unit).
-int launch_xcd(pi_handle* h, float* V, int32_t* policy, const uint8_t* term, float gamma, double theta, int max_sweeps,
-               int check_interval, int max_pi_iter, int32_t* d_out, float* d_delta, float* d_residual_log, uint32_t* d_iter_log,
-               hipStream_t st) {
-    const size_t n = (size_t)h->n_states;
-    const unsigned wgs = (unsigned)((h->n_states + h->xcd_states - 1) / h->xcd_states);
-    const size_t ctl_words = kXcdCtlWords;
-    const size_t ring_bytes = (size_t)h->xcd_ring * ((n + 15) & ~size_t(15)) * sizeof(unsigned long long);   // PI_XCD_RING versions
-    const size_t pol_bytes = ((n * sizeof(int32_t)) + 255) & ~size_t(255);
-    const size_t bytes = ring_bytes + pol_bytes + ctl_words * sizeof(unsigned int);
-    if (!h->d_xcd || h->xcd_bytes < bytes) {
-        if (h->d_xcd) {
-            PI_HIP(hipStreamSynchronize(st));
-            PI_HIP(hipFree(h->d_xcd));
-            h->d_xcd = nullptr;
-        }
-        PI_HIP(hipMalloc(&h->d_xcd, bytes));
-        h->xcd_bytes = bytes;
-    }
-    // control words start from zero, and the ring's tags of an earlier launch must not match either
-    unsigned long long* ring = (unsigned long long*)h->d_xcd;
-    int32_t* pol_out = (int32_t*)((char*)h->d_xcd + ring_bytes);
-    unsigned int* ctl = (unsigned int*)((char*)h->d_xcd + ring_bytes + pol_bytes);
-    h->xcd_ctl = ctl;
-    PI_HIP(hipMemsetAsync(h->d_xcd, 0, bytes, st));
-    // placement is checked, not assumed: a quarter of a second is ample for a sweep and short for a wrong guess
-    const char* timeout_env = std::getenv("PI_MI355_XCD_TIMEOUT");
-    const double timeout_s = timeout_env && std::atof(timeout_env) > 0.0 ? std::atof(timeout_env) : 0.25;
-    unsigned long long ticks = std::max<unsigned long long>((unsigned long long)(timeout_s * 1e8), 1ull);   // wall_clock64: 100 MHz
-    const unsigned grid = (unsigned)kXcds * (wgs + std::max(wgs / 4, 2u));        // spare workgroups: the first `wgs` on XCD 0 take part
-    const float* cV = V;
-    const int32_t* cpol = policy;
-    const float* tab = h->d_tab;
-    void* xargs[] = {&cV, &cpol, &term, &tab, &gamma, &max_sweeps, &theta, &check_interval, &max_pi_iter, &d_residual_log,
-                     &d_iter_log, &ring, &pol_out, &ctl, &ticks};
-    PI_HIP(hipModuleLaunchKernel(h->f_xcd, grid, 1, 1, 1024, 1, 1, 0, st, xargs, nullptr));
-    const unsigned long long* cring = ring;
-    const int32_t* cpol_out = pol_out;
-    int whole_run = max_pi_iter > 0 ? 1 : 0;
-    void* gargs[] = {&V, &policy, &cring, &cpol_out, &ctl, &whole_run, &d_out, &d_delta};
-    PI_HIP(hipModuleLaunchKernel(h->f_xcd_finish, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, st, gargs, nullptr));
-    return 0;
-}
-// PI_MI355_XCD_TRACE: what the last launch left in its control words (synchronous; diagnostics only)
-int xcd_trace(pi_handle* h, int done) {
-    if (!std::getenv("PI_MI355_XCD_TRACE")) return 0;
-    unsigned int w[96];
-    PI_HIP(hipMemcpy(w, h->xcd_ctl, sizeof w, hipMemcpyDeviceToHost));
-    std::fprintf(stderr, "[pi] xcd launch: result %d tickets %u status %u sweeps %u rounds %u stable %u\n", done, w[0], w[64], w[80], w[82],
-                 w[83]);
-    if (std::getenv("PI_MI355_XCD_TIMING"))
-        std::fprintf(stderr, "[pi] xcd cycles per sweep (gather | backup + store | barrier share | polls x 1000): first workgroup %u %u %u "
-                     "%u, last %u %u %u %u\n", w[8], w[9], w[10], w[11], w[16], w[17], w[18], w[19]);
-    return 0;
-}
-}  // namespace
-
-int pi_policy_evaluation(pi_handle* h, float* V, const int32_t* policy, const uint8_t* term, float gamma,
-                         double theta, int max_sweeps, int check_interval, int32_t* d_sweeps, float* d_delta,
-                         float* d_residual_log, void* stream) {
-    if (check_ready(h)) return 1;
-    const bool lds = h->f_resident && h->use_resident;
-    if (!lds && !h->f_flow)
-        return fail("pi_policy_evaluation: this grid has no one-launch evaluation kernel "
-                    "(PI_INFO_RESIDENT_STATES_PER_THREAD: LDS-resident, PI_INFO_FLOW_WORKGROUPS: dataflow)");
-    if (!V || !policy || !d_sweeps || !d_residual_log) return fail("null device pointer");
-    if (max_sweeps < 1 || check_interval < 1) return fail("max_sweeps and check_interval must be positive");
-    pi::DeviceGuard guard(h->device);
-    const float* tab = h->d_tab;
-    if (h->f_xcd && !h->xcd_off) {
-        // XCD-local kernel first (also on the bigger ones of the grids one CU holds); V is untouched when it did not go through: the placement-independent kernel below runs
-        // this evaluation then.  Repeated failures (placement, a wait that ran out) switch the form off for the handle.
-        hipStream_t st = (hipStream_t)stream;
-        if (launch_xcd(h, V, const_cast<int32_t*>(policy), term, gamma, theta, max_sweeps, check_interval, 0, d_sweeps, d_delta,
-                       d_residual_log, nullptr, st))
-            return 1;
-        int32_t done = 0;                                          // the caller reads it next anyway: one small copy
-        PI_HIP(hipMemcpyAsync(&done, d_sweeps, sizeof done, hipMemcpyDeviceToHost, st));
-        PI_HIP(hipStreamSynchronize(st));
-        ++h->xcd_used;
-        if (xcd_trace(h, done)) return 1;
-        if (done >= 0) return 0;
-        if (++h->xcd_failed >= 2) h->xcd_off = true;
-    }
-    if (!lds) {
-        // dataflow kernel: ring of 16 granule versions | progress words + status word | one check slot per look
-        hipStream_t st = (hipStream_t)stream;
-        const size_t n = (size_t)h->n_states;
-        unsigned int wgs = (unsigned)((h->n_states + h->flow_block - 1) / h->flow_block);
-        const size_t ring_bytes = 16 * n * sizeof(unsigned long long);
-        const size_t progress_words = ((size_t)wgs + 1 + 31) & ~size_t(31);
-        const size_t looks = ((size_t)max_sweeps / (size_t)check_interval + 2 + 31) & ~size_t(31);
-        const size_t bytes = ring_bytes + (progress_words + looks) * sizeof(unsigned int);
-        if (!h->d_flow || h->flow_bytes < bytes) {                // more sweeps or more frequent looks than last time
-            if (h->d_flow) {
-                PI_HIP(hipStreamSynchronize(st));                 // an earlier evaluation may still be using it
-                PI_HIP(hipFree(h->d_flow));
-                h->d_flow = nullptr;
-            }
-            PI_HIP(hipMalloc(&h->d_flow, bytes));
-            h->flow_bytes = bytes;
-        }
-        // progress / status / check words start from zero, and the ring's tags of an earlier evaluation must not match
-        // either (tags are version + 1 >= 1): everything is zeroed, ~3 us for the 5 MB of a 200 x 200 grid
-        PI_HIP(hipMemsetAsync(h->d_flow, 0, bytes, st));
-        unsigned long long* ring = (unsigned long long*)h->d_flow;
-        unsigned int* progress = (unsigned int*)((char*)h->d_flow + ring_bytes);
-        unsigned int* checks = progress + progress_words;
-        const char* timeout_env = std::getenv("PI_MI355_FLOW_TIMEOUT");
-        const double timeout_s = timeout_env && std::atof(timeout_env) > 0.0 ? std::atof(timeout_env) : 2.0;
-        unsigned long long ticks = std::max<unsigned long long>((unsigned long long)(timeout_s * 1e8), 1ull);   // wall_clock64: 100 MHz
-        void* fargs[] = {&V, &policy, &term, &tab, &gamma, &max_sweeps, &d_delta, &theta, &check_interval, &d_sweeps,
-                         &d_residual_log, &ring, &progress, &checks, &ticks};
-        PI_HIP(hipModuleLaunchKernel(h->f_flow, wgs, 1, 1, h->flow_block, 1, 1, 0, st, fargs, nullptr));
-        // the finish kernel is the only writer of V: the last version out of the ring when no wave gave up, nothing otherwise
-        void* gargs[] = {&progress, &wgs, &d_sweeps, &ring, &V};
-        PI_HIP(hipModuleLaunchKernel(h->f_flow_finish, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, st, gargs, nullptr));
-        return 0;
-    }
-    float* none = nullptr;
-    void* args[] = {&V, &none, &policy, &term, &tab, &gamma, &max_sweeps, &d_delta, &theta, &check_interval,
-                    &d_sweeps, &d_residual_log};
-    PI_HIP(hipModuleLaunchKernel(h->f_resident, 1, 1, 1, h->resident_block, 1, 1, 0, (hipStream_t)stream, args, nullptr));
-    return 0;
-}
-
-int pi_policy_iteration(pi_handle* h, float* V, int32_t* policy, const uint8_t* term, float gamma, double theta,
-                        int max_eval_sweeps, int check_interval, int max_pi_iter, int32_t* d_result, uint32_t* d_iter_log,
-                        void* stream) {
-    if (check_ready(h)) return 1;
-    const bool xcd = h->f_xcd && !h->xcd_off;
-    const bool resident = !xcd && h->f_run_resident && h->use_resident;
-    if (!resident && !xcd) return fail("pi_policy_iteration: this grid has no one-launch run (PI_INFO_WHOLE_RUN_AVAILABLE)");
-    if (!V || !policy || !d_result || !d_iter_log) return fail("null device pointer");
-    if (max_eval_sweeps < 1 || check_interval < 1 || max_pi_iter < 1) return fail("limits and check_interval must be positive");
-    pi::DeviceGuard guard(h->device);
-    pi::drop_eval_list(h);                                   // the policy is about to change
-    if (resident) {
-        // one CU holds V and the policy in LDS: one workgroup, nothing to wait for
-        const float* tab = h->d_tab;
-        void* args[] = {&V, &policy, &term, &tab, &gamma, &max_eval_sweeps, &theta, &check_interval, &max_pi_iter, &d_result,
-                        &d_iter_log};
-        PI_HIP(hipModuleLaunchKernel(h->f_run_resident, 1, 1, 1, h->resident_block, 1, 1, 0, (hipStream_t)stream, args, nullptr));
-        ++h->whole_runs;
-        return 0;
-    }
-    if (launch_xcd(h, V, policy, term, gamma, theta, max_eval_sweeps, check_interval, max_pi_iter, d_result, nullptr, nullptr,
-                   d_iter_log, (hipStream_t)stream))
-        return 1;
-    ++h->whole_runs;
-    if (std::getenv("PI_MI355_XCD_TRACE")) {
-        int32_t done = 0;
-        PI_HIP(hipMemcpyAsync(&done, d_result, sizeof done, hipMemcpyDeviceToHost, (hipStream_t)stream));
-        PI_HIP(hipStreamSynchronize((hipStream_t)stream));
-        return xcd_trace(h, done);
-    }
-    return 0;
-}
-
 int pi_improve_sweep(pi_handle* h, const float* V, int32_t* policy, const uint8_t* term,
                      int64_t s_begin, int64_t s_end, float gamma, uint32_t* d_changed,
                      void* stream) {
@@ -1059,12 +429,8 @@ int pi_improve_sweep(pi_handle* h, const float* V, int32_t* policy, const uint8_
     if (!V || !policy) return fail("null device pointer");
     pi::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
-    if (s_end == s_begin) {
-        if (d_changed) PI_HIP(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), st));
-        return 0;
-    }
+    if (s_end == s_begin) return zero_outputs(nullptr, d_changed, st);
     pi::drop_eval_list(h);                                   // the policy is about to change
-    long long b = s_begin, e = s_end;
     const float* tab = h->d_tab;
     unsigned int* cslots = d_changed ? changed_slots(h) : nullptr;
     Sched sc;
@@ -1073,18 +439,16 @@ int pi_improve_sweep(pi_handle* h, const float* V, int32_t* policy, const uint8_
         int64_t first = 0, cnt = 0;
         pi::live_span(h, s_begin, s_end, &first, &cnt);
         if (cnt > 0) {
-            const int32_t* live = h->d_live + first;
-            long long count = cnt;
             const pi::Grid2 blocks = plan_launch(h, h->block_improve, first, cnt, pi::live_list_total(h, h->live_count),
                                                 h->cpw_improve, &sc);
-            void* largs[] = {&V, &policy, &live, &tab, &count, &gamma, &cslots, &sc};
-            PI_HIP(hipModuleLaunchKernel(h->f_improve_live, blocks.x, blocks.y, 1, h->block_improve, 1, 1, 0, st, largs, nullptr));
+            PI_HIP(launch(h->f_improve_live, blocks, h->block_improve, st, V, policy, (const int32_t*)(h->d_live + first), tab,
+                          (long long)cnt, gamma, cslots, sc));
         }
         return pi::finalize(h, nullptr, d_changed, st);
     }
     const pi::Grid2 blocks = plan_launch(h, h->block_improve, s_begin, s_end - s_begin, h->n_states, h->cpw_improve, &sc);
-    void* args[] = {&V, &policy, &term, &tab, &b, &e, &gamma, &cslots, &sc};
-    PI_HIP(hipModuleLaunchKernel(h->f_improve, blocks.x, blocks.y, 1, h->block_improve, 1, 1, 0, st, args, nullptr));
+    PI_HIP(launch(h->f_improve, blocks, h->block_improve, st, V, policy, term, tab, (long long)s_begin, (long long)s_end, gamma,
+                  cslots, sc));
     return pi::finalize(h, nullptr, d_changed, st);
 }
 
@@ -1097,110 +461,13 @@ int pi_value_sweep(pi_handle* h, const float* V, float* Vnew, int32_t* policy, c
     pi::drop_eval_list(h);                                   // the policy is about to change
     pi::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
-    if (s_end == s_begin) {
-        if (d_delta) PI_HIP(hipMemsetAsync(d_delta, 0, sizeof(float), st));
-        if (d_changed) PI_HIP(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), st));
-        return 0;
-    }
-    long long b = s_begin, e = s_end;
-    const float* tab = h->d_tab;
-    unsigned int* dbits = d_delta ? delta_slots(h) : nullptr;
-    unsigned int* cslots = d_changed ? changed_slots(h) : nullptr;
+    if (s_end == s_begin) return zero_outputs(d_delta, d_changed, st);
     Sched sc;
     const pi::Grid2 blocks = plan_launch(h, h->block_improve, s_begin, s_end - s_begin, h->n_states, h->cpw_improve, &sc);
-    void* args[] = {&V, &Vnew, &policy, &term, &tab, &b, &e, &gamma, &dbits, &cslots, &sc};
-    PI_HIP(hipModuleLaunchKernel(h->f_value, blocks.x, blocks.y, 1, h->block_improve, 1, 1, 0, st, args, nullptr));
+    PI_HIP(launch(h->f_value, blocks, h->block_improve, st, V, Vnew, policy, term, (const float*)h->d_tab, (long long)s_begin,
+                  (long long)s_end, gamma, d_delta ? delta_slots(h) : (unsigned int*)nullptr,
+                  d_changed ? changed_slots(h) : (unsigned int*)nullptr, sc));
     return pi::finalize(h, d_delta, d_changed, st);
-}
-
-int pi_reach_planes(pi_handle* h, const uint8_t* term, int64_t s_begin, int64_t s_end, int dim,
-                    uint32_t* d_bitmap, void* stream) {
-    if (check_ready(h) || check_range(h, s_begin, s_end)) return 1;
-    if (!d_bitmap) return fail("null device pointer");
-    if (dim < 0 || dim >= h->D) return fail("dim outside [0, D)");
-    pi::DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t words = (size_t)(h->shape[dim] + 31) / 32;
-    PI_HIP(hipMemsetAsync(d_bitmap, 0, words * sizeof(uint32_t), st));
-    if (s_end == s_begin) return 0;
-    long long b = s_begin, e = s_end;
-    const float* tab = h->d_tab;
-    int cpw = 4;
-    void* args[] = {&term, &tab, &b, &e, &d_bitmap, &dim, &cpw};
-    PI_HIP(hipModuleLaunchKernel(h->f_reach_planes, launch_blocks(pi::kProbeBlock, s_end - s_begin, cpw), 1, 1, pi::kProbeBlock,
-                                 1, 1, 0, st, args, nullptr));
-    return 0;
-}
-
-// Units of the leading `depth` dimensions (depth 1: planes of dimension 0; depth 2: rows (i0, i1)).
-static int64_t reach_unit_count(const pi_handle* h, int depth) {
-    int64_t u = 1;
-    for (int d = 0; d < depth; ++d) u *= h->shape[d];
-    return u;
-}
-
-int pi_reach_depth_max(pi_handle* h) {
-    if (!h) return -1;
-    return (h->D >= 3 && (int64_t)h->shape[0] * h->shape[1] <= (int64_t(1) << 17)) ? PI_REACH_ROWS : PI_REACH_PLANES;
-}
-
-int pi_reach_units(pi_handle* h, const uint8_t* term, int64_t s_begin, int64_t s_end, int depth,
-                   uint32_t* d_bitmap, void* stream) {
-    if (check_ready(h) || check_range(h, s_begin, s_end)) return 1;
-    if (!d_bitmap) return fail("null device pointer");
-    if (depth < 1 || depth > pi_reach_depth_max(h)) return fail("depth outside [1, pi_reach_depth_max]");
-    pi::DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t words = (size_t)(reach_unit_count(h, depth) + 31) / 32;
-    PI_HIP(hipMemsetAsync(d_bitmap, 0, words * sizeof(uint32_t), st));
-    if (s_end == s_begin) return 0;
-    long long b = s_begin, e = s_end;
-    const float* tab = h->d_tab;
-    int cpw = 4;
-    void* args[] = {&term, &tab, &b, &e, &d_bitmap, &depth, &cpw};
-    PI_HIP(hipModuleLaunchKernel(h->f_reach_units, launch_blocks(pi::kProbeBlock, s_end - s_begin, cpw), 1, 1,
-                                 pi::kProbeBlock, 1, 1, 0, st, args, nullptr));
-    return 0;
-}
-
-int pi_probe_step(pi_handle* h, const float* states, const float* acts, float* next,
-                  float* reward, uint8_t* done, int64_t m, void* stream) {
-    if (check_ready(h)) return 1;
-    if (m <= 0) return 0;
-    pi::DeviceGuard guard(h->device);
-    long long mm = m;
-    void* args[] = {&states, &acts, &next, &reward, &done, &mm};
-    PI_HIP(hipModuleLaunchKernel(h->f_probe_step, (unsigned)((m + pi::kProbeBlock - 1) / pi::kProbeBlock), 1, 1,
-                                 pi::kProbeBlock, 1, 1, 0, (hipStream_t)stream, args, nullptr));
-    return 0;
-}
-
-int pi_probe_interp(pi_handle* h, const float* pts, int32_t* idxs, float* wgts, int64_t m,
-                    void* stream) {
-    if (check_ready(h)) return 1;
-    if (m <= 0) return 0;
-    pi::DeviceGuard guard(h->device);
-    long long mm = m;
-    void* args[] = {&pts, &idxs, &wgts, &mm};
-    PI_HIP(hipModuleLaunchKernel(h->f_probe_interp, (unsigned)((m + pi::kProbeBlock - 1) / pi::kProbeBlock), 1, 1,
-                                 pi::kProbeBlock, 1, 1, 0, (hipStream_t)stream, args, nullptr));
-    return 0;
-}
-
-int pi_probe_coords(pi_handle* h, int64_t s_begin, int64_t s_end, float* out, int chunks_per_workgroup,
-                    void* stream) {
-    if (check_ready(h) || check_range(h, s_begin, s_end)) return 1;
-    if (!out) return fail("null device pointer");
-    if (chunks_per_workgroup < 1) return fail("chunks_per_workgroup < 1");
-    if (s_end == s_begin) return 0;
-    pi::DeviceGuard guard(h->device);
-    long long b = s_begin, e = s_end;
-    const float* tab = h->d_tab;
-    Sched sc;                    // the sweeps' own schedule (strips included): the probe shows every state is visited once
-    const pi::Grid2 blocks = plan_launch(h, pi::kProbeBlock, s_begin, s_end - s_begin, h->n_states, chunks_per_workgroup, &sc);
-    void* args[] = {&tab, &b, &e, &out, &sc};
-    PI_HIP(hipModuleLaunchKernel(h->f_probe_coords, blocks.x, blocks.y, 1, pi::kProbeBlock, 1, 1, 0, (hipStream_t)stream, args, nullptr));
-    return 0;
 }
 
 int pi_plan_schedule(pi_handle* h, int block, int64_t first, int64_t count, int64_t total, int chunks_per_workgroup,
@@ -1304,146 +571,6 @@ int pi_set_option(pi_handle* h, int what, int64_t value) {
     }
 }
 
-int pi_prepare_mask(pi_handle* h, const uint8_t* d_term, void* stream) {
-    if (pi::check_ready(h)) return 1;
-    return pi_prepare_mask_range(h, d_term, 0, h->n_states, stream);
-}
-
-int pi_prepare_mask_range(pi_handle* h, const uint8_t* d_term, int64_t s_begin, int64_t s_end, void* stream) {
-    if (pi::check_ready(h)) return 1;
-    if (s_begin < 0 || s_end < s_begin || s_end > h->n_states) return fail("bad state range");
-    pi::DeviceGuard guard(h->device);
-    if (h->d_live) { (void)hipFree(h->d_live); h->d_live = nullptr; }
-    if (h->d_eval_list) { (void)hipFree(h->d_eval_list); h->d_eval_list = nullptr; }
-    if (h->d_eval_cursor) { (void)hipFree(h->d_eval_cursor); h->d_eval_cursor = nullptr; }
-    pi::drop_eval_list(h);
-    h->live_term = nullptr;
-    h->live_count = 0;
-    h->live_bits.clear();
-    h->live_bits.shrink_to_fit();
-    h->live_before.clear();
-    h->live_before.shrink_to_fit();
-    h->live_lo = h->live_hi = 0;
-    if (!d_term || s_end == s_begin) return 0;
-    // Only [s_begin, s_end) is listed: a rank of a sharded run lists its shard (the only states its launches visit),
-    // not the grid — 1 / world of the device list, of the host index and of the host pass (at 25^6 on 8 ranks:
-    // 80 MB instead of 630 MB of list per rank).
-    const int64_t n = s_end - s_begin;
-    if (h->n_states < env_int("PI_MI355_LIVE_MIN", 1 << 20, 1, 1 << 30) || !env_int("PI_MI355_LIVE", 1, 0, 1)) return 0;
-    // Built on the device (pi_mask_list_kernel: bitmap + per-block counts, scan, ordered write); the host keeps the
-    // bitmap only — 1 bit per state, 30 MB at 25^6 — and derives the live states in front of every 64-state block from it,
-    // which is what positions of sub-ranges (live_span) and the sharded planner (live_states) need.
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t w0 = s_begin & ~int64_t(63);
-    const size_t nwords = (size_t)((s_end - w0 + 63) / 64);
-    const long long nblocks = (long long)((nwords * 64 + pi::kProbeBlock - 1) / pi::kProbeBlock);
-    unsigned long long* d_bits = nullptr;
-    unsigned long long* d_slots = nullptr;
-    PI_HIP(hipMalloc((void**)&d_bits, nwords * sizeof(unsigned long long)));
-    if (hipMalloc((void**)&d_slots, (size_t)(nblocks + 1) * sizeof(unsigned long long)) != hipSuccess) {
-        (void)hipFree(d_bits);
-        return fail("pi_prepare_mask: out of device memory");
-    }
-    auto cleanup = [&]() { (void)hipFree(d_bits); (void)hipFree(d_slots); };
-    long long b = s_begin, e = s_end, base = w0;
-    int32_t* out = nullptr;
-    auto pass = [&](int which) -> hipError_t {
-        void* args[] = {&d_term, &b, &e, &base, &d_bits, &d_slots, &out, &which};
-        return hipModuleLaunchKernel(h->f_mask_list, (unsigned)nblocks, 1, 1, pi::kProbeBlock, 1, 1, 0, st, args, nullptr);
-    };
-    hipError_t err = pass(0);
-    if (err == hipSuccess) {
-        long long nb = nblocks;
-        void* sargs[] = {&d_slots, &nb};
-        err = hipModuleLaunchKernel(h->f_scan_slots, 1, 1, 1, 1024, 1, 1, 0, st, sargs, nullptr);
-    }
-    unsigned long long packed = 0;
-    if (err == hipSuccess) err = hipMemcpyAsync(&packed, d_slots + nblocks, sizeof packed, hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    if (err != hipSuccess) { cleanup(); return fail(std::string("pi_prepare_mask: ") + hipGetErrorString(err)); }
-    const int64_t n_live = (int64_t)(packed & 0xFFFFFFFFull), waves_with_a_live_lane = (int64_t)(packed >> 32);
-    // idle lanes the state-order sweep carries through its gathers, as a share of the listed range
-    const double idle = (double)(waves_with_a_live_lane * 64 - n_live) / (double)n;
-    if (n_live == 0 || (idle < 0.03 && !h->live_force)) { cleanup(); return 0; }   // nothing to win: keep sweeping in state order
-    if (hipMalloc((void**)&h->d_live, (size_t)n_live * sizeof(int32_t)) != hipSuccess) { cleanup(); return fail("pi_prepare_mask: out of device memory"); }
-    out = h->d_live;
-    std::vector<uint64_t> bits(nwords);
-    err = pass(1);
-    if (err == hipSuccess) err = hipMemcpyAsync(bits.data(), d_bits, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
-    if (err == hipSuccess) err = hipStreamSynchronize(st);
-    cleanup();
-    if (err != hipSuccess) {
-        (void)hipFree(h->d_live);
-        h->d_live = nullptr;
-        return fail(std::string("pi_prepare_mask: ") + hipGetErrorString(err));
-    }
-    std::vector<int64_t> before_block(nwords + 1, 0);
-    for (size_t k = 0; k < nwords; ++k) before_block[k + 1] = before_block[k] + (int64_t)__builtin_popcountll(bits[k]);
-    if (before_block[nwords] != n_live) {
-        (void)hipFree(h->d_live);
-        h->d_live = nullptr;
-        return fail("pi_prepare_mask: the bitmap and the list disagree");
-    }
-    h->live_term = d_term;
-    h->live_lo = s_begin;
-    h->live_hi = s_end;
-    h->live_count = n_live;
-    h->live_bits = std::move(bits);
-    h->live_before = std::move(before_block);
-    return 0;
-}
-
-int64_t pi_live_list(pi_handle* h, int32_t* d_out, int64_t capacity, void* stream) {
-    if (pi::check_ready(h)) return -1;
-    if (h->live_count <= 0 || !h->d_live) return 0;
-    if (!d_out) return h->live_count;
-    if (capacity < h->live_count) { fail("pi_live_list: capacity below the list's length"); return -1; }
-    pi::DeviceGuard guard(h->device);
-    if (hipMemcpyAsync(d_out, h->d_live, (size_t)h->live_count * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                       (hipStream_t)stream) != hipSuccess) { fail("pi_live_list: copy failed"); return -1; }
-    return h->live_count;
-}
-
-int pi_eval_begin(pi_handle* h, const int32_t* policy, const uint8_t* term, void* stream) {
-    if (pi::check_ready(h)) return 1;
-    if (!policy) return fail("null device pointer");
-    pi::drop_eval_list(h);
-    if (!pi::live_usable(h, term, 0, h->n_states) || !env_int("PI_MI355_EVAL_LIST", 1, 0, 1)) return 0;   // nothing to shorten
-    pi::DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const long long nblocks = (h->live_count + pi::kProbeBlock - 1) / pi::kProbeBlock;
-    if (!h->d_eval_list) PI_HIP(hipMalloc((void**)&h->d_eval_list, (size_t)h->live_count * sizeof(int32_t)));
-    if (!h->d_eval_cursor) PI_HIP(hipMalloc((void**)&h->d_eval_cursor, (size_t)(nblocks + 1) * sizeof(unsigned long long)));
-    const int32_t* live = h->d_live;
-    long long count = h->live_count;
-    const float* tab = h->d_tab;
-    int32_t* out = h->d_eval_list;
-    unsigned long long* slots = h->d_eval_cursor;
-    for (int pass = 0; pass < 2; ++pass) {                    // count per block, scan, write in order
-        void* args[] = {&live, &count, &policy, &tab, &slots, &out, &pass};
-        PI_HIP(hipModuleLaunchKernel(h->f_policy_list, (unsigned)nblocks, 1, 1, pi::kProbeBlock, 1, 1, 0, st, args, nullptr));
-        if (pass == 0) {
-            long long nb = nblocks;
-            void* sargs[] = {&slots, &nb};
-            PI_HIP(hipModuleLaunchKernel(h->f_scan_slots, 1, 1, 1, 1024, 1, 1, 0, st, sargs, nullptr));
-        }
-    }
-    unsigned long long kept = 0;
-    PI_HIP(hipMemcpyAsync(&kept, slots + nblocks, sizeof kept, hipMemcpyDeviceToHost, st));
-    PI_HIP(hipStreamSynchronize(st));
-    // worth a second list only when it is noticeably shorter
-    if ((double)kept > 0.97 * (double)h->live_count) return 0;
-    h->eval_count = (int64_t)kept;
-    h->eval_policy = policy;
-    return 0;
-}
-
-int pi_eval_end(pi_handle* h) {
-    if (!h) return fail("null handle");
-    pi::drop_eval_list(h);
-    return 0;
-}
-
 int pi_debug_report(pi_handle* h, uint32_t* out4) {
     if (pi::check_ready(h)) return 1;
     if (!out4) return fail("null argument");
@@ -1501,3 +628,4 @@ int64_t pi_info(pi_handle* h, int what) {
 }
 
 }  // extern "C"
+

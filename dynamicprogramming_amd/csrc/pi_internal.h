@@ -1,5 +1,12 @@
-// pi_internal.h — shared between pi_api.cpp (handles, hipRTC, launches), pi_comm.cpp (multi-GPU transports
-// and the sharded sweep driver), pi_infer.cpp and pi_rollout.cpp (inference handle).  Not part of the C ABI.
+// pi_internal.h — shared between the host sources of libpi_mi355.so.  Not part of the C ABI.  What lives where:
+//   pi_api.cpp        error state, pi_create / pi_destroy and the dispatch policy, the sweep launchers and the graph cache,
+//                     the sweep entry points, pi_set_option, pi_info
+//   pi_probe.cpp      the reach and probe entry points
+//   pi_compile.cpp    embedded device sources, reciprocal-division check, build_source, hipRTC + code-object cache, modules
+//   pi_onelaunch.cpp  the one-launch families (dataflow, XCD-local, LDS-resident runs) and their scratch blocks
+//   pi_live.cpp       the live-state list of pi_prepare_mask and the per-evaluation list of pi_eval_begin
+//   pi_comm.cpp       multi-GPU transports and the sharded sweep driver;  pi_p2p.cpp  the peer-to-peer transport
+//   pi_infer.cpp, pi_rollout.cpp   the inference handle and its rollouts
 #pragma once
 
 #include "pi_mi355.h"
@@ -26,6 +33,44 @@ const std::string& last_error();
 constexpr int kProbeBlock = 256; // threads per workgroup of the probe kernels' host launches
 constexpr int kXcds = 8;         // PI_NXCD
 constexpr int kSlots = 256;      // PI_NSLOT
+constexpr int kXcdCtlWords = 128 + 256;   // control block of the XCD-local kernel: PI_XCD_CTL_FLAGS + 2 banks x 64 flag granules
+constexpr const char* kArch = "gfx950";
+
+// Where a kernel launch goes: onto a stream, or into a graph under construction as the node behind *prev.
+struct LaunchTo {
+    hipStream_t st = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphNode_t* prev = nullptr;
+    LaunchTo(hipStream_t s) : st(s) {}
+    LaunchTo(hipGraph_t g, hipGraphNode_t* p) : graph(g), prev(p) {}
+};
+struct Grid2 { unsigned x, y; };
+// One kernel launch.  The arguments are taken BY VALUE and passed by address: the deduced type of every one of them must
+// be the kernel's parameter type (an int64_t where the kernel takes an int is read wrong, silently).
+template <typename... A>
+hipError_t launch(hipFunction_t f, Grid2 grid, unsigned block, LaunchTo to, A... a) {
+    void* args[] = {(void*)&a...};
+    if (!to.graph) return hipModuleLaunchKernel(f, grid.x, grid.y, 1, block, 1, 1, 0, to.st, args, nullptr);
+    hipKernelNodeParams p = {};
+    p.func = (void*)f;
+    p.gridDim = dim3(grid.x, grid.y, 1);
+    p.blockDim = dim3(block, 1, 1);
+    p.kernelParams = args;
+    hipGraphNode_t node;
+    const hipError_t e = hipGraphAddKernelNode(&node, to.graph, *to.prev ? to.prev : nullptr, *to.prev ? 1 : 0, &p);
+    if (e == hipSuccess) *to.prev = node;
+    return e;
+}
+
+int env_int(const char* name, int dflt, int lo, int hi);   // integer knob from the environment, dflt when unset or outside [lo, hi]
+// PI_*_INIT lists of the generated translation units: "{a,b,c}", floats as hexadecimal literals (%af)
+std::string hex_float(float v);
+template <typename T, typename F>
+std::string brace_list(const T* v, size_t count, F fmt) {
+    std::string r = "{";
+    for (size_t i = 0; i < count; ++i) r += (i ? "," : "") + fmt(v[i]);
+    return r + "}";
+}
 
 // Makes `device` current for the lifetime of the guard and restores the caller's device after.
 struct DeviceGuard {
@@ -88,6 +133,12 @@ struct GraphEntry {               // one captured batch of evaluation sweeps
 };
 
 }  // namespace pi
+
+// The device sources and the math header, embedded verbatim (pi_compile.cpp)
+extern "C" const char pi_embedded_kernels[];
+extern "C" const char pi_embedded_onelaunch[];
+extern "C" const char pi_embedded_math[];
+extern "C" const char pi_embedded_push[];
 
 struct pi_handle {
     int device = -1;
@@ -205,9 +256,9 @@ int check_range(const pi_handle* h, int64_t s_begin, int64_t s_end);
 // keep_terminals: Vnew already holds the terminal states' values (every sweep of a ping-pong batch but the
 // first), so the sweep neither copies them nor streams old values for them.
 int launch_eval(pi_handle* h, const float* V, float* Vnew, const int32_t* policy, const uint8_t* term,
-                int64_t s_begin, int64_t s_end, float gamma, bool want_delta, hipStream_t st,
+                int64_t s_begin, int64_t s_end, float gamma, bool want_delta, LaunchTo to,
                 bool keep_terminals = false);
-int finalize(pi_handle* h, float* d_delta, uint32_t* d_changed, hipStream_t st);
+int finalize(pi_handle* h, float* d_delta, uint32_t* d_changed, LaunchTo to);
 // The live-state list of pi_prepare_mask.  live_usable: a list is in use, `term` is the mask it was built from and
 // [s_begin, s_end) lies inside the range it covers.
 // live_span: the run of list entries whose states lie in [s_begin, s_end).  launch_eval_live: one evaluation sweep
@@ -224,11 +275,11 @@ struct Sched {
     int cpw;
     unsigned int period, phase;
 };
-struct Grid2 { unsigned x, y; };
 Grid2 plan_launch(const pi_handle* h, int block, int64_t first, int64_t count, int64_t total, int cpw, Sched* sc);
 // pi_eval_push_kernel over `count` entries of `list` with their destination masks: V'(s) goes to Vnew[s] and to
 // peers[j][s] for every bit j of dest[k] (ensure_push_module builds the kernel the first time)
-int ensure_push_module(pi_handle* h);
+int ensure_push_module(pi_handle* h);                                      // pi_compile.cpp
+unsigned launch_blocks(int block, int64_t count, int cpw);                 // slab schedule: workgroups for `count` units
 int launch_eval_push(pi_handle* h, const float* V, float* Vnew, const int32_t* policy, const int32_t* list,
                      const uint8_t* dest, float* const* d_peers, int n_peers, int64_t count, float gamma, bool want_delta,
                      hipStream_t st);
@@ -240,6 +291,9 @@ void drop_eval_list(pi_handle* h);     // the policy may have changed: forget th
 void release_comm(pi_handle* h);      // pi_comm.cpp: tears down the transport and the exchange plan
 void drop_p2p_pending(pi_handle* h);  // pi_p2p.cpp
 double comm_timeout_seconds();        // PI_MI355_COMM_TIMEOUT (default 120): how long a rank waits for a peer
+void drop_graphs(pi_handle* h);       // the cached graphs hold launch geometry and kernel handles: forget them
+void resolve_strip(pi_handle* h);     // strip_mode -> strip_states (the library's choice needs the final memory order)
+bool validate_fast_division(float span);   // pi_compile.cpp: is the reciprocal division exact for this divisor?
 // hipRTC (gfx950, -O3 -ffp-contract=off) or the on-disk code-object cache -> image of one translation unit
 int compile_image(const std::string& src, const char* cache_dir, char* log, size_t log_len,
                   std::vector<char>& image, bool* cache_hit);

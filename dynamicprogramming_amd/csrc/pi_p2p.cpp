@@ -166,8 +166,9 @@ struct P2pComm : pi::Comm {
             }
         return -1;
     }
-    int launch(hipFunction_t f, unsigned grid, unsigned block, void** args, hipStream_t st) {
-        PI_HIP(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, 0, st, args, nullptr));
+    // pi_p2p_sigwait_kernel: raise the counters of `sig`, then wait for those of `wait`
+    int sigwait(const Flags& sig, const Flags& wait, hipStream_t st) {
+        PI_HIP(pi::launch(f_sigwait, {1, 1}, 64, st, sig, wait, ticks, error_word()));
         return 0;
     }
 
@@ -225,7 +226,6 @@ struct P2pComm : pi::Comm {
             auto& v = o.is_send ? receivers : senders;
             if (std::find(v.begin(), v.end(), o.peer) == v.end()) v.push_back(o.peer);
         }
-        uint32_t* err = error_word();
         Flags none = {};
         // 1. one wave: my receives of this group are posted — tell every sender its target region is free — and wait
         //    until the receivers of my sends have said the same (the copy kernel then starts only when its targets are
@@ -242,10 +242,7 @@ struct P2pComm : pi::Comm {
             done.ptr[done.n] = flag(peer_page[p], kOffData, rank);
             done.value[done.n++] = k;
         }
-        {
-            void* args[] = {&posted, &acks, &ticks, &err};
-            if (launch(f_sigwait, 1, 64, args, st)) return 1;
-        }
+        if (sigwait(posted, acks, st)) return 1;
         // 2. my sends: one kernel stores every segment into the peers' buffers and raises their data counters
         if (!receivers.empty()) {
             std::vector<Seg> segs;
@@ -270,8 +267,7 @@ struct P2pComm : pi::Comm {
             int n_segs = (int)segs.size() - 1;
             uint32_t* counter = flag(page, kOffCounter, 0);
             const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((units + 1023) / 1024, 1024));
-            void* args[] = {&d_segs, &n_segs, &vec4, &none, &done, &ticks, &err, &counter};
-            if (launch(f_push, grid, 256, args, st)) return 1;
+            PI_HIP(pi::launch(f_push, {grid, 1}, 256, st, (const Seg*)d_segs, n_segs, vec4, none, done, ticks, error_word(), counter));
         }
         // 3. wait for the data of my receives
         if (!senders.empty()) {
@@ -280,8 +276,7 @@ struct P2pComm : pi::Comm {
                 data.ptr[data.n] = flag(page, kOffData, p);
                 data.value[data.n++] = recv_n[p];
             }
-            void* args[] = {&none, &data, &ticks, &err};
-            if (launch(f_sigwait, 1, 64, args, st)) return 1;
+            if (sigwait(none, data, st)) return 1;
         }
         ops.clear();
         return 0;
@@ -336,16 +331,12 @@ struct P2pComm : pi::Comm {
             }
             carry = {};
         }
-        uint32_t* err = error_word();
         if (carry.n > 0) {                                   // did not fit: wait for it on its own, first
-            Flags none = {};
-            void* wargs[] = {&none, &carry, &ticks, &err};
-            if (launch(f_sigwait, 1, 64, wargs, st)) return 1;
+            if (sigwait(Flags{}, carry, st)) return 1;
             carry = {};
         }
         if (posted.n == 0 && acks.n == 0) return 0;
-        void* args[] = {&posted, &acks, &ticks, &err};
-        return launch(f_sigwait, 1, 64, args, st);
+        return sigwait(posted, acks, st);
     }
     // The next call on this stream is the push_begin of another fused sweep: let IT wait for this sweep's data.
     int push_wait_deferred(hipStream_t) override {
@@ -357,18 +348,12 @@ struct P2pComm : pi::Comm {
     int push_signal(hipStream_t st) override {
         if (alive()) return 1;
         if (pending_done.n == 0) return 0;
-        Flags none = {};
-        uint32_t* err = error_word();
-        void* args[] = {&pending_done, &none, &ticks, &err};
-        return launch(f_sigwait, 1, 64, args, st);
+        return sigwait(pending_done, Flags{}, st);
     }
     int push_wait(hipStream_t st) override {
         if (alive()) return 1;
         if (pending_data.n == 0) return 0;
-        Flags none = {};
-        uint32_t* err = error_word();
-        void* args[] = {&none, &pending_data, &ticks, &err};
-        return launch(f_sigwait, 1, 64, args, st);
+        return sigwait(Flags{}, pending_data, st);
     }
     // Has a wait of this rank timed out?  Blocks on `st` (called where the host synchronises anyway).
     int health(hipStream_t st) {
@@ -415,9 +400,7 @@ struct P2pComm : pi::Comm {
         r.world = world;
         r.epoch = e;
         r.op = op;
-        uint32_t* err = error_word();
-        void* args[] = {&d, &r, &ticks, &err};
-        if (launch(f_reduce, 1, 64, args, st)) return 1;
+        PI_HIP(pi::launch(f_reduce, {1, 1}, 64, st, d, r, ticks, error_word()));
         return health(st);
     }
     // values >= 0 (residuals): their bit patterns order like unsigned integers

@@ -18,7 +18,6 @@ asm(".section .rodata\n"
     ".byte 0\n"
     ".text\n");
 extern "C" const char pi_embedded_rollout[];
-extern "C" const char pi_embedded_math[];          // pi_api.cpp
 
 using pi::fail;
 
@@ -82,11 +81,9 @@ int pi_infer_rollout(pi_infer* h, const float* d_start, int64_t m, int n_steps, 
     const int64_t blocks = (m + 255) / 256;
     if (blocks > INT32_MAX) return fail("m is too large for one launch");
     pi::DeviceGuard guard(h->device);
-    long long mm = m;
-    float* traj = traj_every > 0 ? d_traj : nullptr;
-    void* args[] = {&d_start, &mm, &n_steps, &gamma, &h->d_policy, &h->d_actions, &d_final, &d_return, &d_length,
-                    &d_terminated, &traj, &traj_every};
-    PI_HIP(hipModuleLaunchKernel(h->f_rollout, (unsigned)blocks, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, args, nullptr));
+    PI_HIP(pi::launch(h->f_rollout, {(unsigned)blocks, 1}, 256, (hipStream_t)stream, d_start, (long long)m, n_steps, gamma,
+                      h->d_policy, h->d_actions, d_final, d_return, d_length, d_terminated,
+                      traj_every > 0 ? d_traj : (float*)nullptr, traj_every));
     return 0;
 }
 

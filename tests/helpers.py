@@ -302,7 +302,7 @@ def table_floats(name: str, shape, actions=None) -> int:
 
 
 # What pi_create must decide at every threshold of its dispatch, WRITTEN OUT from the design (the comments on
-# the launch geometry and the one-launch kernels in csrc/pi_api.cpp's pi_create), not computed by the code under test: a
+# the launch geometry and the one-launch kernels in csrc/pi_api.cpp's choose_dispatch), not computed by the code under test: a
 # threshold that moves has to be moved here as well, on purpose.  Per row: env, shape, then
 #   k        states per thread of the LDS-resident kernels (Info.RESIDENT_STATES_PER_THREAD; 0: not resident).  Limits
 #            12 288 (2-D, 1024 threads), 4 096 (4-D, 512 threads), 1 024 (6-D, 512 threads); k = ceil(n / threads)

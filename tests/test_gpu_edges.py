@@ -5,7 +5,7 @@ degenerate grids against float64 numpy).
 
 The kernels are specialised at run time on grid shape, action count, workgroup size, chunks per workgroup and schedule,
 and pi_create picks the kernel family by comparing the state count with fixed numbers.  The shapes below sit ON those
-numbers and one step beyond.  When a constant of csrc/pi_api.cpp moves, update `helpers.DISPATCH_TABLE` and this list:
+numbers and one step beyond.  When a constant of choose_dispatch (csrc/pi_api.cpp) moves, update `helpers.DISPATCH_TABLE` and this list:
 
   threshold                                   shapes (env)
   table floats 8 * 256 = 2048 (staging)       2 x 2025 = 2048, 2 x 2026 = 2049; strided branch also: 2 x 3000, 3000 x 2,

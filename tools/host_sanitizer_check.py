@@ -15,6 +15,9 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
+# the host sources of libpi_mi355.so (HOST_SRC in csrc/Makefile)
+HOST_SOURCES = ("pi_api.cpp", "pi_probe.cpp", "pi_compile.cpp", "pi_onelaunch.cpp", "pi_live.cpp", "pi_comm.cpp", "pi_p2p.cpp", "pi_infer.cpp",
+                "pi_rollout.cpp")
 
 
 def host_runtime_is_clean_under_address_and_ub_sanitizers(tmp_path: Path) -> str:
@@ -30,7 +33,7 @@ def host_runtime_is_clean_under_address_and_ub_sanitizers(tmp_path: Path) -> str
     cmd = [G.HIPCC, "-x", "c++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
            "-ffp-contract=off", "-std=c++17", "-Wall", "-Wextra", f"-I{ROOT / 'include'}", "-I/opt/rocm/include",
            "-D__HIP_PLATFORM_AMD__", f'-DPI_CSRC_DIR="{csrc}"', f'-DPI_INCLUDE_DIR="{ROOT / "include"}"',
-           str(csrc / "pi_api.cpp"), str(csrc / "pi_comm.cpp"), str(csrc / "pi_infer.cpp"), str(csrc / "pi_p2p.cpp"),
+           *(str(csrc / f) for f in HOST_SOURCES),
            str(ROOT / "tools" / "native" / "host_asan_driver.cpp"), "-o", str(exe),
            "-L/opt/rocm/lib", "-lhiprtc", "-lamdhip64", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]
     build = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
