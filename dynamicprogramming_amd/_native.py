@@ -80,6 +80,9 @@ SIGNATURES = {
     "pi_infer_set_dynamics": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]),
     "pi_infer_rollout": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp,
                                         _vp, ctypes.c_int, _vp]),
+    "pi_infer_set_partner": (ctypes.c_int, [_vp, _vp, ctypes.c_char_p, ctypes.c_size_t]),
+    "pi_infer_rollout_hybrid": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, _f32p, _f32p,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "pi_plan_schedule": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_uint64)]),
     "pi_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64]),
@@ -92,7 +95,7 @@ SIGNATURES = {
     "pi_eval_end": (ctypes.c_int, [_vp]),
 }
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 _lib = None
 _load_error: Exception | None = None
 
@@ -605,6 +608,32 @@ class InferenceEngine:
         _check(lib().pi_infer_rollout(self._h, d_start or None, int(m), int(n_steps), float(gamma), d_final or None,
                                       d_return or None, d_length or None, d_terminated or None, d_traj or None,
                                       int(traj_every), stream or None), "pi_infer_rollout")
+
+    def set_partner(self, partner: "InferenceEngine") -> str:
+        """Build this handle's hybrid module: its grid + `partner`'s grid + the plugin of the last set_dynamics + the hybrid
+        rollout kernel (a compile check on host-only handles); returns the compiler's log."""
+        log = ctypes.create_string_buffer(1 << 16)
+        rc = lib().pi_infer_set_partner(self._h, partner._h, log, len(log))
+        text = log.value.decode(errors="replace")
+        if rc != 0:
+            raise NativeError(f"hybrid rollout kernel compilation failed:\n{last_error()}")
+        return text
+
+    def rollout_hybrid(self, partner: "InferenceEngine", d_start, m, n_steps, enter, leave, gamma=1.0, d_final=0,
+                       d_return=0, d_length=0, d_terminated=0, d_secondary_steps=0, d_last_mode=0, d_traj=0, traj_every=0,
+                       stream=0) -> None:
+        """m episodes of n_steps closed-loop steps that switch between this handle's policy and `partner`'s, in one launch
+        (pi_infer_rollout_hybrid; raw device pointers, `enter` / `leave` host arrays of D thresholds; asynchronous)."""
+        box = [None if v is None else np.ascontiguousarray(v, dtype=np.float32) for v in (enter, leave)]
+        for v in box:
+            if v is not None and v.shape != (self.D,):
+                raise ValueError(f"enter and leave must hold {self.D} thresholds each")
+        ent, lea = (None if v is None else v.ctypes.data_as(_f32p) for v in box)
+        _check(lib().pi_infer_rollout_hybrid(self._h, partner._h if partner is not None else None, d_start or None, int(m),
+                                             int(n_steps), float(gamma), ent, lea, d_final or None, d_return or None,
+                                             d_length or None, d_terminated or None, d_secondary_steps or None,
+                                             d_last_mode or None, d_traj or None, int(traj_every), stream or None),
+               "pi_infer_rollout_hybrid")
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -1,0 +1,141 @@
+// pi_hybrid.cpp — closed-loop rollouts that switch between two inference handles (include/pi_mi355.h, "Inference"
+// block): pi_infer_set_partner builds the primary handle's third module — its grid, the partner's grid, pi_math.h,
+// the plugin pi_infer_set_dynamics was given, csrc/pi_rollout_kernels.hip (the shared interpolation) and
+// csrc/pi_hybrid_kernels.hip in one translation unit — and pi_infer_rollout_hybrid runs whole episodes of a batch of
+// start states in one launch.
+
+#include "pi_internal.h"
+
+#include <cmath>
+#include <sstream>
+
+#ifndef PI_CSRC_DIR
+#error "build with -DPI_CSRC_DIR=\"...\""
+#endif
+asm(".section .rodata\n"
+    ".global pi_embedded_hybrid\n"
+    "pi_embedded_hybrid:\n"
+    ".incbin \"" PI_CSRC_DIR "/pi_hybrid_kernels.hip\"\n"
+    ".byte 0\n"
+    ".text\n");
+extern "C" const char pi_embedded_hybrid[];
+
+using pi::fail;
+
+namespace {
+
+struct HybridBox {                     // PiHybridBox of pi_hybrid_kernels.hip
+    float enter[6], leave[6];
+};
+
+// the partner's grid as the SECOND set of defines: PI_D -> PI2_D, PI_LO_INIT -> PI2_LO_INIT, ...
+std::string second_defines(const std::string& defines) {
+    std::string out;
+    const std::string from = "#define PI_", to = "#define PI2_";
+    size_t at = 0;
+    for (size_t hit; (hit = defines.find(from, at)) != std::string::npos; at = hit + from.size()) {
+        out.append(defines, at, hit - at);
+        out += to;
+    }
+    out.append(defines, at, std::string::npos);
+    return out;
+}
+
+// what both entry points refuse about the pair
+int check_pair(const char* who, const pi_infer* h, const pi_infer* partner) {
+    const std::string w = std::string(who) + ": ";
+    if (h->device != partner->device)
+        return fail(w + "the handles are on different devices (" + std::to_string(h->device) + " and " +
+                    std::to_string(partner->device) + ")");
+    if (h->D != partner->D)
+        return fail(w + "the handles differ in D (" + std::to_string(h->D) + " and " + std::to_string(partner->D) + ")");
+    if (h->corner_bits != partner->corner_bits)
+        return fail(w + "the handles differ in their corner_bits tables (the kernel walks one corner order for both grids)");
+    return 0;
+}
+
+}  // namespace
+
+int pi::drop_hybrid(pi_infer* h) {
+    if (h->module_hybrid) {                         // launches already enqueued have to finish first
+        pi::DeviceGuard guard(h->device);
+        PI_HIP(hipDeviceSynchronize());
+        PI_HIP(hipModuleUnload(h->module_hybrid));
+    }
+    h->module_hybrid = nullptr;
+    h->f_hybrid = nullptr;
+    h->has_partner = false;
+    h->partner_defines.clear();
+    return 0;
+}
+
+extern "C" {
+
+int pi_infer_set_partner(pi_infer* h, pi_infer* partner, char* log, size_t log_len) {
+    pi::fail("");
+    if (log && log_len) log[0] = 0;
+    if (!h || !partner) return fail("null handle");
+    if (check_pair("pi_infer_set_partner", h, partner)) return 1;
+    if (!h->has_dynamics) return fail("pi_infer_set_partner: pi_infer_set_dynamics was never called on the primary handle");
+    std::ostringstream src;
+    src << "#define PI_HYBRID 1\n";
+    src << h->grid_defines;
+    src << "// ---- secondary grid ----\n" << second_defines(partner->grid_defines);
+    src << pi_embedded_math << "\n";
+    src << "#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n";
+    src << "// ---- env plugin (user string) ----\n";
+    src << h->dynamics_src << "\n";
+    src << "// ---- rollout helpers ----\n";
+    src << pi_embedded_rollout << "\n";
+    src << "// ---- hybrid rollout kernel ----\n";
+    src << pi_embedded_hybrid << "\n";
+    std::vector<char> image;
+    if (pi::compile_image(src.str(), h->has_cache_dir ? h->cache_dir.c_str() : nullptr, log, log_len, image, nullptr)) return 1;
+    if (pi::drop_hybrid(h)) return 1;
+    if (h->device >= 0) {
+        pi::DeviceGuard guard(h->device);
+        PI_HIP(hipModuleLoadData(&h->module_hybrid, image.data()));
+        PI_HIP(hipModuleGetFunction(&h->f_hybrid, h->module_hybrid, "pi_hybrid_rollout_kernel"));
+    }
+    h->partner_defines = partner->grid_defines;
+    h->has_partner = true;
+    return 0;
+}
+
+int pi_infer_rollout_hybrid(pi_infer* h, pi_infer* partner, const float* d_start, int64_t m, int n_steps, float gamma,
+                            const float* enter, const float* leave, float* d_final, float* d_return, int32_t* d_length,
+                            uint8_t* d_terminated, int32_t* d_secondary_steps, uint8_t* d_last_mode, float* d_traj,
+                            int traj_every, void* stream) {
+    if (!h || !partner) return fail("null handle");
+    if (h->device < 0 || partner->device < 0) return fail("host-only handle (device = -1) cannot launch kernels");
+    if (check_pair("pi_infer_rollout_hybrid", h, partner)) return 1;
+    if (!h->d_policy) return fail("pi_infer_rollout_hybrid: pi_infer_set_policy was never called on the primary handle");
+    if (!partner->d_policy) return fail("pi_infer_rollout_hybrid: pi_infer_set_policy was never called on the partner");
+    if (!h->has_dynamics) return fail("pi_infer_rollout_hybrid: pi_infer_set_dynamics was never called on the primary handle");
+    if (!h->has_partner || !h->f_hybrid)
+        return fail("pi_infer_rollout_hybrid: no hybrid module: call pi_infer_set_partner (again after every pi_infer_set_dynamics)");
+    if (partner->grid_defines != h->partner_defines)
+        return fail("pi_infer_rollout_hybrid: the hybrid module was built for another partner grid: call pi_infer_set_partner "
+                    "with this partner");
+    if (!enter || !leave) return fail("null argument (enter / leave)");
+    HybridBox box = {};
+    for (int d = 0; d < h->D; ++d) {
+        if (std::isnan(enter[d]) || std::isnan(leave[d]))
+            return fail("pi_infer_rollout_hybrid: threshold " + std::to_string(d) + " is NaN");
+        if (enter[d] > leave[d])
+            return fail("pi_infer_rollout_hybrid: enter[" + std::to_string(d) + "] > leave[" + std::to_string(d) +
+                        "]: the box to enter must lie inside the box to leave");
+        box.enter[d] = enter[d];
+        box.leave[d] = leave[d];
+    }
+    int64_t blocks = 0;
+    if (const int rc = pi::check_rollout_args(h->D, d_start, m, n_steps, d_final, d_traj, traj_every, &blocks)) return rc == 2 ? 0 : 1;
+    pi::DeviceGuard guard(h->device);
+    PI_HIP(pi::launch(h->f_hybrid, {(unsigned)blocks, 1}, 256, (hipStream_t)stream, d_start, (long long)m, n_steps, gamma,
+                      (const int32_t*)h->d_policy, (const float*)h->d_actions, (const int32_t*)partner->d_policy,
+                      (const float*)partner->d_actions, box, d_final, d_return, d_length, d_terminated, d_secondary_steps,
+                      d_last_mode, traj_every > 0 ? d_traj : (float*)nullptr, traj_every));
+    return 0;
+}
+
+}  // extern "C"

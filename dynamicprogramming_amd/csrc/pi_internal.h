@@ -6,7 +6,7 @@
 //   pi_onelaunch.cpp  the one-launch families (dataflow, XCD-local, LDS-resident runs) and their scratch blocks
 //   pi_live.cpp       the live-state list of pi_prepare_mask and the per-evaluation list of pi_eval_begin
 //   pi_comm.cpp       multi-GPU transports and the sharded sweep driver;  pi_p2p.cpp  the peer-to-peer transport
-//   pi_infer.cpp, pi_rollout.cpp   the inference handle and its rollouts
+//   pi_infer.cpp, pi_rollout.cpp   the inference handle and its rollouts;  pi_hybrid.cpp  rollouts that switch between two handles
 #pragma once
 
 #include "pi_mi355.h"
@@ -139,6 +139,7 @@ extern "C" const char pi_embedded_kernels[];
 extern "C" const char pi_embedded_onelaunch[];
 extern "C" const char pi_embedded_math[];
 extern "C" const char pi_embedded_push[];
+extern "C" const char pi_embedded_rollout[];      // pi_rollout.cpp
 
 struct pi_handle {
     int device = -1;
@@ -244,6 +245,14 @@ struct pi_infer {
     hipModule_t module_rollout = nullptr;
     hipFunction_t f_rollout = nullptr;
     bool has_dynamics = false;           // pi_infer_set_dynamics went through (host-only handles: it compiled)
+    std::string dynamics_src;            // the plugin of that call, for the third module
+    std::vector<int32_t> corner_bits;    // what pi_infer_create was given: both handles of a hybrid rollout share it
+    // third module (pi_infer_set_partner, pi_hybrid.cpp): this grid + a partner's grid + pi_math.h + the env plugin +
+    // csrc/pi_rollout_kernels.hip + csrc/pi_hybrid_kernels.hip; partner_defines: the partner grid it was built for
+    hipModule_t module_hybrid = nullptr;
+    hipFunction_t f_hybrid = nullptr;
+    bool has_partner = false;            // pi_infer_set_partner went through (host-only handles: it compiled)
+    std::string partner_defines;
 };
 
 namespace pi {
@@ -297,5 +306,10 @@ bool validate_fast_division(float span);   // pi_compile.cpp: is the reciprocal 
 // hipRTC (gfx950, -O3 -ffp-contract=off) or the on-disk code-object cache -> image of one translation unit
 int compile_image(const std::string& src, const char* cache_dir, char* log, size_t log_len,
                   std::vector<char>& image, bool* cache_hit);
+// pi_rollout.cpp: the argument rules pi_infer_rollout and pi_infer_rollout_hybrid share (m, n_steps, traj_every, the
+// 63-bit size, d_start, alignment).  0: launch `*blocks` workgroups; 1: refused (pi::fail was called); 2: m == 0, nothing to do
+int check_rollout_args(int D, const float* d_start, int64_t m, int n_steps, const float* d_final, const float* d_traj,
+                       int traj_every, int64_t* blocks);
+int drop_hybrid(pi_infer* h);           // pi_hybrid.cpp: unloads the third module (after a device synchronisation)
 
 }  // namespace pi

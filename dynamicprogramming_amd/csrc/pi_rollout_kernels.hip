@@ -38,19 +38,33 @@ struct PiRolloutGrid {
 };
 __device__ constexpr PiRolloutGrid PI_RG = {PI_LO_INIT, PI_HI_INIT, PI_SHAPE_INIT, PI_STRIDES_INIT, PI_BITS_INIT};
 
-// the action of pi_infer_kernel at the point s
-__device__ __forceinline__ float pi_rollout_action(const float (&s)[PI_D], const int* __restrict__ policy,
+// The grid an interpolation runs on, as the operands of its arithmetic.  PiGridFixed is the module's own grid: every
+// operand a compile-time constant.  (pi_hybrid_kernels.hip adds a second kind, whose operands a lane picks from two
+// grids.)  step(d) is the float64 cell width, (double)(hi - lo) / (double)(shape - 1).
+struct PiGridFixed {
+    __device__ __forceinline__ float lo(int d) const { return PI_RG.lo[d]; }
+    __device__ __forceinline__ float hi(int d) const { return PI_RG.hi[d]; }
+    __device__ __forceinline__ int shape(int d) const { return PI_RG.shape[d]; }
+    __device__ __forceinline__ int stride(int d) const { return PI_RG.stride[d]; }
+    __device__ __forceinline__ double step(int d) const {
+        return (double)(PI_RG.hi[d] - PI_RG.lo[d]) / (double)(PI_RG.shape[d] - 1);
+    }
+};
+
+// the action of pi_infer_kernel at the point s on the grid g (corners in the order of PI_RG.bits)
+template <typename G>
+__device__ __forceinline__ float pi_rollout_action(const G& g, const float (&s)[PI_D], const int* __restrict__ policy,
                                                    const float* __restrict__ actions) {
     int base[PI_D];
     double t[PI_D];
 #pragma unroll
     for (int d = 0; d < PI_D; ++d) {
-        const float l = PI_RG.lo[d], h = PI_RG.hi[d];
-        const double step = (double)(h - l) / (double)(PI_RG.shape[d] - 1);
+        const float l = g.lo(d), h = g.hi(d);
+        const double step = g.step(d);
         const float p = fmaxf(l, fminf(s[d], h));
         const double cell = (double)(p - l) / step;
         int i = (int)cell;
-        if (i >= PI_RG.shape[d] - 1) i = PI_RG.shape[d] - 2;
+        if (i >= g.shape(d) - 1) i = g.shape(d) - 2;
         base[d] = i;
         t[d] = (double)(float)(((double)p - ((double)l + (double)i * step)) / step);
     }
@@ -63,7 +77,7 @@ __device__ __forceinline__ float pi_rollout_action(const float (&s)[PI_D], const
 #pragma unroll
         for (int d = 0; d < PI_D; ++d) {
             w *= PI_RG.bits[c][d] ? t[d] : (1.0 - t[d]);
-            f += (base[d] + PI_RG.bits[c][d]) * PI_RG.stride[d];
+            f += (base[d] + PI_RG.bits[c][d]) * g.stride(d);
         }
         wf[c] = (float)w;
         a_idx[c] = f;
@@ -106,6 +120,7 @@ __device__ __forceinline__ void pi_rollout_store_state(float* __restrict__ row, 
 #endif
 }
 
+#ifndef PI_HYBRID                                     // the hybrid module holds pi_hybrid_rollout_kernel instead
 extern "C" __global__ void __launch_bounds__(PI_RO_BLOCK)
 pi_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, float gamma,
                   const int* __restrict__ policy, const float* __restrict__ actions,
@@ -131,7 +146,7 @@ pi_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, flo
     bool terminated = false, running = exists;
     for (int t = 0; t < n_steps && __any(running); ++t) {
         if (running) {
-            const float a = pi_rollout_action(s, policy, actions);
+            const float a = pi_rollout_action(PiGridFixed(), s, policy, actions);
             float n[PI_D], r;
             bool done;
             pi_rollout_dynamics(s, a, n, &r, &done);
@@ -162,3 +177,4 @@ pi_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, flo
     if (out_length != nullptr) out_length[k] = length;
     if (out_terminated != nullptr) out_terminated[k] = terminated ? 1 : 0;
 }
+#endif  // PI_HYBRID

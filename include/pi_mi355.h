@@ -33,7 +33,7 @@ extern "C" {
 typedef struct pi_handle pi_handle;
 
 /* ABI version of this header (bumped on any signature change). */
-#define PI_MI355_ABI_VERSION 11
+#define PI_MI355_ABI_VERSION 12
 int pi_abi_version(void);
 
 /* Last error message of the calling thread ("" if none). */
@@ -442,6 +442,32 @@ int pi_plan_schedule(pi_handle* h, int block, int64_t first, int64_t count, int6
  *                       last state).  d_final and d_traj must be 8-byte aligned (4-D: 16-byte).  Needs
  *                       pi_infer_set_policy and pi_infer_set_dynamics; m == 0 is a no-op, n_steps == 0 copies the
  *                       start (length 0, return 0); traj_every > n_steps (n_steps > 0) is an error.  Asynchronous.
+ * Rollouts that switch between TWO policies (the reference's runners/hybrid_double_cartpole.py: _use_balance :62-69
+ * and the body of evaluate's loop :112-125, two get_optimal_action tables and one _step_python per step on the CPU)
+ * as ONE launch for m episodes.  Two handles of the same D, device and corner_bits table: the PRIMARY h (mode 0) and
+ * the SECONDARY `partner` (mode 1), each with its own bounds, shape, strides, policy and ACTION table; the env plugin
+ * is h's.  The switch is a box with hysteresis, two float32 vectors of D thresholds, `enter` and `leave`.  Every
+ * episode starts in mode 0; per step t of an episode still running, in this order:
+ *   1. mode: if it is 1 it stays 1 unless fabsf(s[d]) > leave[d] for some d; if it is 0 it becomes 1 iff
+ *      fabsf(s[d]) < enter[d] for every d.  float32, strict comparisons; +inf in both vectors = the dimension takes
+ *      no part.  Applied before the first step too: an episode that starts inside the box acts on the secondary policy
+ *   2. action: the interpolated action of the mode's policy on ITS grid, the bits pi_infer_query returns on that
+ *      handle for the state (the point clamped to that grid's bounds, as in the reference)
+ *   3. secondary_steps += 1 when the mode is 1
+ *   4. step_dynamics, ret = ret + disc * r, disc = disc * gamma, state = successor, length = t + 1, `done` freezes
+ *      the episode: exactly as in pi_infer_rollout.
+ * The reference's rule is enter = (inf, inf, 0.32, 4.0, 0.32, 4.0), leave = (inf, inf, 0.38, 5.0, 0.38, 5.0), its
+ * balance_steps = secondary_steps.
+ *   pi_infer_set_partner   builds h's THIRD module: h's grid + partner's grid + the plugin last given to
+ *                       pi_infer_set_dynamics(h) + csrc/pi_hybrid_kernels.hip.  Same cache, flags and log convention
+ *                       as pi_infer_set_dynamics; device = -1 handles: compile check.  pi_infer_set_dynamics on h
+ *                       drops the module again (the next hybrid rollout then fails, naming pi_infer_set_partner)
+ *   pi_infer_rollout_hybrid  arguments and outputs of pi_infer_rollout, plus: enter, leave HOST arrays of D floats
+ *                       (no NaN, enter[d] <= leave[d]); d_secondary_steps (m) int32; d_last_mode (m) uint8, the mode of
+ *                       the last step taken (0 when length is 0); either may be null.  Policy and action tables of
+ *                       both handles are read at launch: a later pi_infer_set_policy on either is picked up.  The
+ *                       partner must have the grid the module was built for.  m == 0 is a no-op, n_steps == 0 copies
+ *                       the start (lengths, returns, secondary_steps, last_mode 0).  Asynchronous.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pi_infer pi_infer;
 pi_infer* pi_infer_create(int device, int D, const float* lo, const float* hi, const int32_t* grid_shape,
@@ -456,6 +482,11 @@ int pi_infer_set_dynamics(pi_infer* h, const char* dynamics_src, char* log, size
 int pi_infer_rollout(pi_infer* h, const float* d_start, int64_t m, int n_steps, float gamma, float* d_final,
                      float* d_return, int32_t* d_length, uint8_t* d_terminated, float* d_traj, int traj_every,
                      void* stream);
+int pi_infer_set_partner(pi_infer* h, pi_infer* partner, char* log, size_t log_len);
+int pi_infer_rollout_hybrid(pi_infer* h, pi_infer* partner, const float* d_start, int64_t m, int n_steps, float gamma,
+                            const float* enter, const float* leave, float* d_final, float* d_return, int32_t* d_length,
+                            uint8_t* d_terminated, int32_t* d_secondary_steps, uint8_t* d_last_mode, float* d_traj,
+                            int traj_every, void* stream);
 
 /* Tuning: the `what` of pi_set_option. */
 enum pi_option_code {

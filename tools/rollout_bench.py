@@ -11,7 +11,12 @@ The driver (no arguments) runs every (config, m) in a child process of its own u
 other, and stops at the first child that fails; then one `rocprofv3 --kernel-trace --stats` run of the fused call
 alone (C3, m = 4 096).  Each child warms both paths up once and reports the better of `--repeat` timings (device
 events around the whole call, a synchronise at the end), fused and loop alternating.  The table goes to --out.
-usage: python tools/rollout_bench.py [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
+--hybrid: the two-policy rollout instead (pi_infer_rollout_hybrid, csrc/pi_hybrid_kernels.hip): the 25^6 double cart-pole
+swing-up grid with the 25^6 balance grid as its partner, seeded random policies, the reference's switch box, starts
+uniform in the swing-up grid; per m the fused hybrid call, the loop it replaces (a query on each handle and one plugin
+step per time step, the mode rule and the bookkeeping as torch ops) and the single-policy fused rollout of the same
+batch.  The table is appended to --out.
+usage: python tools/rollout_bench.py [--hybrid] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
 """
 import argparse
 import json
@@ -107,6 +112,120 @@ def child(args):
     eng.close()
 
 
+def hybrid_child(args):
+    import numpy as np
+    import torch
+    from dynamicprogramming_amd import _native, envs
+    from utils import barycentric as B
+    sys.path.insert(0, str(ROOT / "runners"))
+    from hybrid_double_cartpole import ENTER, LEAVE
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(0)
+    bits = np.array(list(product([0, 1], repeat=6)), dtype=np.int32)
+    pols, tabs0 = [], None
+    for env in ("double_cartpole_swingup", "double_cartpole"):
+        cls = envs.ENVS[env]
+        tabs = [np.asarray(b, np.float32) for b in cls.bins_space(25).values()]
+        tabs0 = tabs0 or tabs
+        shape = np.array([len(t) for t in tabs], np.int32)
+        lo, hi = np.array([t.min() for t in tabs], np.float32), np.array([t.max() for t in tabs], np.float32)
+        strides = np.array([int(np.prod(shape[d + 1:])) for d in range(6)], np.int32)
+        acts = np.asarray(cls.ACTIONS, np.float32)
+        policy = rng.integers(0, len(acts), size=int(np.prod(shape.astype(np.int64))), dtype=np.int32)
+        pols.append(B.DevicePolicy(policy, acts, lo, hi, shape, strides, bits, device=dev))
+    dp, dp2 = pols
+    dyn = envs.dynamics_source("double_cartpole_swingup")
+    dp.set_dynamics(dyn)
+    hp = B.HybridPolicy(dp, dp2, ENTER, LEAVE)
+    m, steps = args.m, args.steps
+    lo, hi = np.array([t.min() for t in tabs0], np.float32), np.array([t.max() for t in tabs0], np.float32)
+    starts = torch.from_numpy((lo + (hi - lo) * rng.random((m, 6), dtype=np.float32)).astype(np.float32)).to(dev)
+    eng = _native.Engine(6, [len(t) for t in tabs0], lo, hi, tabs0, np.asarray(envs.ENVS["double_cartpole_swingup"].ACTIONS, np.float32), device=0)
+    eng.compile(dyn)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ent, lea = torch.tensor(ENTER, dtype=torch.float32, device=dev), torch.tensor(LEAVE, dtype=torch.float32, device=dev)
+
+    def loop():
+        states = starts.clone()
+        nxt = torch.empty_like(states)
+        rew = torch.empty(m, dtype=torch.float32, device=dev)
+        done = torch.empty(m, dtype=torch.uint8, device=dev)
+        ret = torch.zeros(m, dtype=torch.float32, device=dev)
+        length = torch.zeros(m, dtype=torch.int32, device=dev)
+        second = torch.zeros(m, dtype=torch.int32, device=dev)
+        ended = torch.zeros(m, dtype=torch.bool, device=dev)
+        mode = torch.zeros(m, dtype=torch.bool, device=dev)
+        for t in range(steps):
+            run = ~ended
+            mag = states.abs()
+            mode = torch.where(run, torch.where(mode, ~(mag > lea).any(dim=1), (mag < ent).all(dim=1)), mode)
+            act = torch.where(mode, dp2(states), dp(states))
+            second = second + (run & mode).to(torch.int32)
+            eng.probe_step(states.data_ptr(), act.data_ptr(), nxt.data_ptr(), rew.data_ptr(), done.data_ptr(), m, st)
+            ret = torch.where(run, ret + rew, ret)
+            states = torch.where(run[:, None], nxt, states)
+            length = torch.where(run, torch.full_like(length, t + 1), length)
+            ended = ended | (run & (done != 0))
+        return B.HybridRolloutResult(states, ret, length, ended, None, second, mode.to(torch.uint8))
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record()
+        out = fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1), out
+
+    def fused():
+        return hp.rollout(starts, steps)
+
+    def single():
+        return dp.rollout(starts, steps)
+    a, b = fused(), loop()                                # warm-up of all paths, and: same results
+    single()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(a.states.view(torch.int32), b.states.view(torch.int32)) and torch.equal(a.lengths, b.lengths)
+                and torch.equal(a.returns.view(torch.int32), b.returns.view(torch.int32))
+                and torch.equal(a.secondary_steps, b.secondary_steps) and torch.equal(a.last_mode, b.last_mode))
+    t_fused, t_loop, t_single = [], [], []
+    for _ in range(args.repeat):
+        t_fused.append(timed(fused)[0])
+        t_loop.append(timed(loop)[0])
+        t_single.append(timed(single)[0])
+    print(json.dumps({"m": m, "steps": steps, "same_bits": same, "fused_ms": min(t_fused), "loop_ms": min(t_loop),
+                      "single_ms": min(t_single), "episode_steps": int(a.lengths.sum().item()),
+                      "secondary_steps": int(a.secondary_steps.sum().item()),
+                      "terminated_share": float(a.terminated.float().mean().item()), "launches_loop": 3 * steps}))
+    dp.close()
+    dp2.close()
+    eng.close()
+
+
+def hybrid_driver(args):
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    me = [sys.executable, str(Path(__file__).resolve())]
+    rows = []
+    for m in BATCHES:
+        res = subprocess.run(["timeout", "-k", "10", str(CHILD_SECONDS), *me, "--child", "--hybrid", "--m", str(m), "--steps",
+                              str(args.steps), "--repeat", str(args.repeat)], capture_output=True, text=True)
+        if res.returncode != 0:                           # a fault, an abort or a time limit: nothing more runs
+            sys.exit(f"hybrid m={m} ended with status {res.returncode}; stopping\n{res.stdout[-2000:]}\n{res.stderr[-2000:]}")
+        rows.append(json.loads(res.stdout.strip().splitlines()[-1]))
+        print(rows[-1], flush=True)
+    lines = ["", f"hybrid rollouts (25^6 swing-up + 25^6 balance, the reference's switch box), MI355X, commit {args.commit}",
+             f"{'m':>7s} {'fused':>10s} {'loop':>10s} {'loop/fused':>10s} {'single':>10s} {'ep-steps':>12s} {'mode-1 steps':>12s} "
+             f"{'ended':>6s} {'same bits':>9s}"]
+    for r in rows:
+        lines.append(f"{r['m']:7d} {r['fused_ms']:10.3f} {r['loop_ms']:10.3f} {r['loop_ms'] / r['fused_ms']:10.1f} "
+                     f"{r['single_ms']:10.3f} {r['episode_steps']:12d} {r['secondary_steps']:12d} {r['terminated_share']:6.3f} "
+                     f"{str(r['same_bits']):>9s}")
+    with out.open("a") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def driver(args):
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
@@ -158,10 +277,14 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--fused-only", action="store_true")
+    ap.add_argument("--hybrid", action="store_true")
     ap.add_argument("--config", choices=list(CONFIGS), default="c3")
     ap.add_argument("--m", type=int, default=4096)
     args = ap.parse_args()
-    (child if args.child else driver)(args)
+    if args.hybrid:
+        (hybrid_child if args.child else hybrid_driver)(args)
+    else:
+        (child if args.child else driver)(args)
 
 
 if __name__ == "__main__":

@@ -28,6 +28,10 @@ import numpy as np
 # float32 = sum_t gamma^t r_t, lengths (m) int32 = steps taken, terminated (m) bool = ended by the env's `done`,
 # trajectory (rows, m, D) float32 or None.
 RolloutResult = namedtuple("RolloutResult", "states returns lengths terminated trajectory")
+# ... and a rollout that switches between two policies (``HybridPolicy.rollout``, ``hybrid_rollout``): the same fields plus
+# secondary_steps (m) int32 = steps taken on the secondary policy, last_mode (m) uint8 = the mode (0 primary, 1 secondary)
+# of the last step taken, 0 for an episode of length 0.
+HybridRolloutResult = namedtuple("HybridRolloutResult", RolloutResult._fields + ("secondary_steps", "last_mode"))
 
 
 class DevicePolicy:
@@ -90,15 +94,12 @@ class DevicePolicy:
         through; returns the compiler's log.  Calling it again replaces the plugin."""
         log = self._engine.set_dynamics(dynamics_src)
         self._has_dynamics = True
+        self._dynamics_serial = getattr(self, "_dynamics_serial", 0) + 1      # HybridPolicy rebuilds its module after this
         return log
 
-    def rollout(self, states, steps, gamma=1.0, record_every=0):
-        """Closed-loop episodes from ``states`` (m, D) in ONE kernel launch: per step the interpolated action (what
-        calling this object returns for the state, same bits) and the plugin's ``step_dynamics``; an episode whose
-        step reports `done` keeps the state it reached.  ``returns`` accumulates ``ret + disc * r`` in float32,
-        ``disc`` running through ``gamma``.  ``record_every = k > 0``: ``trajectory[j]`` holds all states after
-        ``j * k`` steps (row 0 the start, ended episodes repeat their last state), ``steps // k + 1`` rows.
-        A float32 tensor on this device in -> torch tensors on the device out; a numpy array in -> numpy out."""
+    def _rollout_buffers(self, states, steps, record_every):
+        """Checked arguments and the output tensors every rollout fills: (on_device, d_start, m, steps, every, final,
+        returns, lengths, terminated (uint8), trajectory or None)."""
         torch = self._torch
         if not self._has_policy:
             raise RuntimeError("this DevicePolicy was built without a policy table")
@@ -120,6 +121,16 @@ class DevicePolicy:
         length = torch.empty(m, dtype=torch.int32, device=self.device)
         term = torch.empty(m, dtype=torch.uint8, device=self.device)
         traj = torch.empty((steps // every + 1, m, self.D), dtype=torch.float32, device=self.device) if every else None
+        return on_device, d_start, m, steps, every, final, ret, length, term, traj
+
+    def rollout(self, states, steps, gamma=1.0, record_every=0):
+        """Closed-loop episodes from ``states`` (m, D) in ONE kernel launch: per step the interpolated action (what
+        calling this object returns for the state, same bits) and the plugin's ``step_dynamics``; an episode whose
+        step reports `done` keeps the state it reached.  ``returns`` accumulates ``ret + disc * r`` in float32,
+        ``disc`` running through ``gamma``.  ``record_every = k > 0``: ``trajectory[j]`` holds all states after
+        ``j * k`` steps (row 0 the start, ended episodes repeat their last state), ``steps // k + 1`` rows.
+        A float32 tensor on this device in -> torch tensors on the device out; a numpy array in -> numpy out."""
+        on_device, d_start, m, steps, every, final, ret, length, term, traj = self._rollout_buffers(states, steps, record_every)
         self._engine.rollout(d_start.data_ptr(), m, steps, gamma, d_final=final.data_ptr(), d_return=ret.data_ptr(),
                              d_length=length.data_ptr(), d_terminated=term.data_ptr(),
                              d_traj=traj.data_ptr() if every else 0, traj_every=every, stream=self._stream())
@@ -131,6 +142,51 @@ class DevicePolicy:
 
     def close(self) -> None:
         self._engine.close()
+
+
+class HybridPolicy:
+    """Two trained policies on the GPU and the rule that switches between them: ``HybridPolicy(primary, secondary,
+    enter, leave)`` — two ``DevicePolicy`` objects of the same D on the same device, each on its own grid with its own
+    action table, and two vectors of D float32 thresholds.  Every episode starts on the primary policy (mode 0); per
+    step it moves to the secondary (mode 1) iff ``|s[d]| < enter[d]`` in every dimension and back iff ``|s[d]| >
+    leave[d]`` in some dimension (float32, strict; ``inf`` in both: the dimension takes no part) — the reference's
+    runners/hybrid_double_cartpole.py with ``enter = (inf, inf, 0.32, 4, 0.32, 4)``, ``leave = (inf, inf, 0.38, 5, 0.38,
+    5)``.  The env plugin is the primary's: ``primary.set_dynamics(...)`` first."""
+
+    def __init__(self, primary: DevicePolicy, secondary: DevicePolicy, enter, leave):
+        if primary.D != secondary.D or primary.device != secondary.device:
+            raise ValueError("both policies of a HybridPolicy need the same D and the same device")
+        self.primary, self.secondary = primary, secondary
+        self.enter = np.ascontiguousarray(enter, dtype=np.float32)
+        self.leave = np.ascontiguousarray(leave, dtype=np.float32)
+        if self.enter.shape != (primary.D,) or self.leave.shape != (primary.D,):
+            raise ValueError(f"enter and leave must hold {primary.D} thresholds each")
+        self._built_for = None                     # the primary's set_dynamics call the hybrid module was built after
+
+    def rollout(self, states, steps, gamma=1.0, record_every=0):
+        """Closed-loop episodes from ``states`` (m, D) in ONE kernel launch, in/out conventions of ``DevicePolicy.rollout``;
+        returns a ``HybridRolloutResult``.  The hybrid kernel is built on first use and again after a new
+        ``primary.set_dynamics``."""
+        a, b = self.primary, self.secondary
+        if not b._has_policy:
+            raise RuntimeError("the secondary DevicePolicy was built without a policy table")
+        on_device, d_start, m, steps, every, final, ret, length, term, traj = a._rollout_buffers(states, steps, record_every)
+        if self._built_for != a._dynamics_serial:
+            a._engine.set_partner(b._engine)
+            self._built_for = a._dynamics_serial
+        torch = a._torch
+        second = torch.empty(m, dtype=torch.int32, device=a.device)
+        mode = torch.empty(m, dtype=torch.uint8, device=a.device)
+        a._engine.rollout_hybrid(b._engine, d_start.data_ptr(), m, steps, self.enter, self.leave, gamma,
+                                 d_final=final.data_ptr(), d_return=ret.data_ptr(), d_length=length.data_ptr(),
+                                 d_terminated=term.data_ptr(), d_secondary_steps=second.data_ptr(),
+                                 d_last_mode=mode.data_ptr(), d_traj=traj.data_ptr() if every else 0, traj_every=every,
+                                 stream=a._stream())
+        term = term != 0
+        if on_device:
+            return HybridRolloutResult(final, ret, length, term, traj, second, mode)
+        return HybridRolloutResult(final.cpu().numpy(), ret.cpu().numpy(), length.cpu().numpy(), term.cpu().numpy(),
+                                   traj.cpu().numpy() if every else None, second.cpu().numpy(), mode.cpu().numpy())
 
 
 def get_barycentric_weights_and_indices(points, bounds_low, bounds_high, grid_shape, strides,
@@ -188,21 +244,26 @@ def get_optimal_action(state, policy, action_space, bounds_low, bounds_high, gri
     return lambdas @ np.asarray(action_space)[np.asarray(policy)[flat]]
 
 
-def rollout(step, states, steps, policy, action_space, bounds_low, bounds_high, grid_shape, strides, corner_bits,
-            gamma=1.0, record_every=0):
-    """Closed-loop episodes on the CPU (numpy): the twin of ``DevicePolicy.rollout``, same definition.
-    ``step(states (k, D) float32, actions (k,) float32) -> (next (k, D), reward (k,), done (k,))`` is any batched
-    env step; it is only handed the episodes still running.  Per step: weights and indices from
-    ``get_barycentric_weights_and_indices``, the action summed in float32 over ascending corners (multiply, then
-    add), ``ret = ret + disc * r`` and ``disc = disc * gamma`` in float32, state = successor, length = t + 1; `done`
-    freezes the episode at the state it reached.  Returns a ``RolloutResult`` of numpy arrays."""
+def _interpolated_actions(points, policy, action_space, bounds_low, bounds_high, grid_shape, strides, corner_bits):
+    """The rollouts' action: weights and indices from ``get_barycentric_weights_and_indices``, summed in float32 over
+    ascending corners (multiply, then add)."""
+    pol = np.asarray(policy)
+    acts = np.asarray(action_space, dtype=np.float32)
+    w, idx = get_barycentric_weights_and_indices(points, bounds_low, bounds_high, grid_shape, strides, corner_bits)
+    a = np.zeros(len(points), np.float32)
+    for c in range(w.shape[1]):
+        a = a + w[:, c] * acts[pol[idx[:, c]]]
+    return a
+
+
+def _closed_loop(step, states, steps, gamma, record_every, act):
+    """The loop ``rollout`` and ``hybrid_rollout`` share.  ``act(live, states (k, D)) -> actions (k,) float32`` is asked
+    for the episodes still running (``live``: their indices).  Returns the fields of a ``RolloutResult``."""
     steps, every = int(steps), int(record_every)
     if steps < 0 or every < 0 or (steps > 0 and every > steps):
         raise ValueError("rollout needs steps >= 0 and 0 <= record_every <= steps")
     s = np.array(np.atleast_2d(states), dtype=np.float32)
     m = len(s)
-    pol = np.asarray(policy)
-    acts = np.asarray(action_space, dtype=np.float32)
     ret = np.zeros(m, np.float32)
     length = np.zeros(m, np.int32)
     terminated = np.zeros(m, bool)
@@ -214,11 +275,7 @@ def rollout(step, states, steps, policy, action_space, bounds_low, bounds_high, 
         if len(live) == 0 and not every:
             break
         if len(live):
-            w, idx = get_barycentric_weights_and_indices(s[live], bounds_low, bounds_high, grid_shape, strides,
-                                                         corner_bits)
-            a = np.zeros(len(live), np.float32)
-            for c in range(w.shape[1]):
-                a = a + w[:, c] * acts[pol[idx[:, c]]]
+            a = act(live, s[live])
             nxt, rew, done = step(s[live], a)
             ret[live] = ret[live] + disc * np.asarray(rew, np.float32)
             s[live] = np.asarray(nxt, np.float32)
@@ -229,4 +286,49 @@ def rollout(step, states, steps, policy, action_space, bounds_low, bounds_high, 
         disc = np.float32(disc * g)
         if every and (t + 1) % every == 0:
             rows.append(s.copy())
-    return RolloutResult(s, ret, length, terminated, np.stack(rows) if every else None)
+    return s, ret, length, terminated, np.stack(rows) if every else None
+
+
+def rollout(step, states, steps, policy, action_space, bounds_low, bounds_high, grid_shape, strides, corner_bits,
+            gamma=1.0, record_every=0):
+    """Closed-loop episodes on the CPU (numpy): the twin of ``DevicePolicy.rollout``, same definition.
+    ``step(states (k, D) float32, actions (k,) float32) -> (next (k, D), reward (k,), done (k,))`` is any batched
+    env step; it is only handed the episodes still running.  Per step: weights and indices from
+    ``get_barycentric_weights_and_indices``, the action summed in float32 over ascending corners (multiply, then
+    add), ``ret = ret + disc * r`` and ``disc = disc * gamma`` in float32, state = successor, length = t + 1; `done`
+    freezes the episode at the state it reached.  Returns a ``RolloutResult`` of numpy arrays."""
+    tables = (policy, action_space, bounds_low, bounds_high, grid_shape, strides, corner_bits)
+    return RolloutResult(*_closed_loop(step, states, steps, gamma, record_every,
+                                       lambda live, pts: _interpolated_actions(pts, *tables)))
+
+
+def switch_mode(mode, states, enter, leave):
+    """One application of the hybrid rule: ``mode`` (k,) bool (True: secondary) and ``states`` (k, D) -> the new modes.
+    A secondary episode stays unless ``|s[d]| > leave[d]`` for some d; a primary one moves over iff ``|s[d]| < enter[d]``
+    for every d.  float32, strict comparisons."""
+    mag = np.abs(np.asarray(states, dtype=np.float32))
+    inside = (mag < np.asarray(enter, dtype=np.float32)).all(axis=1)
+    outside = (mag > np.asarray(leave, dtype=np.float32)).any(axis=1)
+    return np.where(np.asarray(mode, bool), ~outside, inside)
+
+
+def hybrid_rollout(step, states, steps, primary, secondary, enter, leave, gamma=1.0, record_every=0):
+    """Closed-loop episodes that switch between two policies, on the CPU (numpy): the twin of ``HybridPolicy.rollout``.
+    ``primary`` and ``secondary`` are the tuples of tables ``rollout`` takes — ``(policy, action_space, bounds_low,
+    bounds_high, grid_shape, strides, corner_bits)`` — and ``step`` its batched env step.  Every episode starts in
+    mode 0; per step ``switch_mode`` first, then the action of the mode's policy on its own grid, ``secondary_steps``
+    counts the steps in mode 1, and the step's bookkeeping is ``rollout``'s.  Returns a ``HybridRolloutResult``."""
+    m = len(np.atleast_2d(states))
+    mode = np.zeros(m, bool)
+    second = np.zeros(m, np.int32)
+
+    def act(live, pts):
+        now = switch_mode(mode[live], pts, enter, leave)
+        mode[live] = now
+        second[live] += now
+        a = np.empty(len(live), np.float32)
+        for which, tables in ((~now, primary), (now, secondary)):
+            if which.any():
+                a[which] = _interpolated_actions(pts[which], *tables)
+        return a
+    return HybridRolloutResult(*_closed_loop(step, states, steps, gamma, record_every, act), second, mode.astype(np.uint8))
