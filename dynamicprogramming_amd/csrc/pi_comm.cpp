@@ -30,6 +30,7 @@
 #include <deque>
 #include <map>
 #include <mutex>
+#include <numeric>
 
 using pi::fail;
 
@@ -46,29 +47,32 @@ struct ShardPlan {
     bool broken = false;            // a sharded sweep failed half-way: streams were drained; new communicator + plan needed
     hipStream_t comm_stream = nullptr;
     hipEvent_t ev_ready = nullptr, ev_done = nullptr;
-    // Row-exact split (grids without terminal states): exactly the rows peers wait for, as an ascending state list
-    // swept by pi_eval_live_kernel in ONE launch, and the rest of the shard as a second list — instead of a few
-    // coarse contiguous ranges that also hold rows nobody waits for (C4 at 8 ranks: 80-100 % of the shard).
-    bool row_exact = false;
-    std::vector<std::pair<int64_t, int64_t>> first_exact, inner_exact;
+    // What an overlapped halo plan sweeps first, beyond the coarse ranges above (every such plan has those).  The Push
+    // kinds belong to the fused exchange of transports that can_push(): entry k of what is swept first goes to the peers
+    // named by the bits of its destination mask — bit j = push_peers[j] — stored by pi_eval_push_kernel itself.
+    enum class SweptFirst {
+        Ranges,         // nothing more; the exchange on the second stream
+        Lists,          // no terminal states: d_first / d_inner split the shard (plan_row_lists)
+        PushLists,      // the same with d_first_dest: fused, every sweep (plan_state_lists, plan_row_lists)
+        // terminal states (plan_live_masks): fused from a batch's second sweep on, while the handle's live-state list is live_list
+        PushLiveLists,  // d_first / d_inner / d_first_dest split the shard's LIVE states
+        PushLiveSpans,  // d_live_dest: one byte per entry of the shard's live span, for the live spans of send_ranges
+    };
+    SweptFirst swept_first = SweptFirst::Ranges;
+    bool row_lists() const { return swept_first == SweptFirst::Lists || swept_first == SweptFirst::PushLists; }
+    bool live_push() const { return swept_first == SweptFirst::PushLiveLists || swept_first == SweptFirst::PushLiveSpans; }
+    bool fused() const { return swept_first == SweptFirst::PushLists || live_push(); }
+    bool has_lists() const { return row_lists() || swept_first == SweptFirst::PushLiveLists; }
+    bool overlapped() const { return halo && comm_stream != nullptr; }
+    std::vector<std::pair<int64_t, int64_t>> first_exact, inner_exact;      // row-exact lists as ranges, for pi_plan_ranges
     int32_t *d_first = nullptr, *d_inner = nullptr;
     int64_t n_first = 0, n_inner = 0;
-    // Fused exchange (transports that can_push()): entry k of the swept-first list goes to the peers named by the bits
-    // of d_first_dest[k] — bit j = push_peers[j] — stored by the swept-first kernel itself (pi_eval_push_kernel).
     std::vector<int> push_peers, push_senders;
-    uint8_t* d_first_dest = nullptr;
-    bool push_ok = false;
-    // The same for the coarse-range plan of a grid WITH terminal states whose later sweeps of a batch run over the
-    // live-state list (pi_prepare_mask_range): one byte per entry of the shard's live span.  Valid for the list it was
-    // built from (live_list / live_count).
-    uint8_t* d_live_dest = nullptr;
-    int64_t live_dest_base = 0;
+    uint8_t *d_first_dest = nullptr, *d_live_dest = nullptr;
     const int32_t* live_list = nullptr;
-    int64_t live_list_count = 0;
-    bool live_push_ok = false;
-    bool live_exact = false;            // d_first / d_inner / d_first_dest hold the split of the shard's LIVE states
+    int64_t live_list_count = 0, live_dest_base = 0;
     bool pair_exact = false;            // destination masks cut down to the pairs (i_0, i_v) each peer reads
-    int64_t fused_send_elems = -1;      // (state, receiver) pairs one fused sweep delivers; -1: not a fused plan
+    int64_t fused_send_elems = -1;      // (state, receiver) pairs one fused sweep delivers; -1: not counted for this plan
     ~ShardPlan() {
         if (d_live_dest) (void)hipFree(d_live_dest);
         if (d_first_dest) (void)hipFree(d_first_dest);
@@ -130,7 +134,7 @@ struct RcclComm : pi::Comm {
     ~RcclComm() override {
         if (comm) (void)ncclCommDestroy(comm);
     }
-    const char* kind() const override { return "rccl"; }
+    int transport() const override { return PI_TRANSPORT_RCCL; }
     int abort_with(const std::string& why) {
         if (in_group) { (void)ncclGroupEnd(); in_group = false; }
         if (comm) { (void)ncclCommAbort(comm); comm = nullptr; }
@@ -175,16 +179,13 @@ struct RcclComm : pi::Comm {
                                 comm, st), "ncclAllGather")) return 1;
         return poll_async();
     }
-    int allreduce_max_f32(float* d, hipStream_t st) override {
+    int allreduce_scalar(void* d, ncclDataType_t type, ncclRedOp_t op, const char* what, hipStream_t st) {
         if (alive()) return 1;
-        if (check(ncclAllReduce(d, d, 1, ncclFloat, ncclMax, comm, st), "ncclAllReduce(max)")) return 1;
+        if (check(ncclAllReduce(d, d, 1, type, op, comm, st), what)) return 1;
         return poll_async();
     }
-    int allreduce_sum_u32(uint32_t* d, hipStream_t st) override {
-        if (alive()) return 1;
-        if (check(ncclAllReduce(d, d, 1, ncclUint32, ncclSum, comm, st), "ncclAllReduce(sum)")) return 1;
-        return poll_async();
-    }
+    int allreduce_max_f32(float* d, hipStream_t st) override { return allreduce_scalar(d, ncclFloat, ncclMax, "ncclAllReduce(max)", st); }
+    int allreduce_sum_u32(uint32_t* d, hipStream_t st) override { return allreduce_scalar(d, ncclUint32, ncclSum, "ncclAllReduce(sum)", st); }
 };
 
 // ---- in-process transport (test transport: N handles, N host threads, one process) -------
@@ -233,7 +234,7 @@ struct LocalComm : pi::Comm {
         std::lock_guard<std::mutex> lk(g_groups_mu);
         if (grp && ++grp->left == grp->world) g_groups.erase(name);
     }
-    const char* kind() const override { return "local"; }
+    int transport() const override { return PI_TRANSPORT_IN_PROCESS; }
     // Every host wait of this transport is bounded: a peer that failed (or never arrives) turns into
     // an error on all members after PI_MI355_COMM_TIMEOUT seconds instead of a hang.
     template <typename Pred>
@@ -339,28 +340,19 @@ struct LocalComm : pi::Comm {
         *out = grp->red_result;
         return 0;
     }
-    int allreduce_max_f32(float* d, hipStream_t st) override {
-        float v;
+    template <typename T> int allreduce_scalar(T* d, bool is_max, hipStream_t st) {
+        T v;
         PI_HIP(hipMemcpyAsync(&v, d, sizeof v, hipMemcpyDeviceToHost, st));
         PI_HIP(hipStreamSynchronize(st));
         double r;
-        if (reduce_host((double)v, true, &r)) return 1;
-        v = (float)r;
+        if (reduce_host((double)v, is_max, &r)) return 1;
+        v = (T)r;
         PI_HIP(hipMemcpyAsync(d, &v, sizeof v, hipMemcpyHostToDevice, st));
         PI_HIP(hipStreamSynchronize(st));
         return 0;
     }
-    int allreduce_sum_u32(uint32_t* d, hipStream_t st) override {
-        uint32_t v;
-        PI_HIP(hipMemcpyAsync(&v, d, sizeof v, hipMemcpyDeviceToHost, st));
-        PI_HIP(hipStreamSynchronize(st));
-        double r;
-        if (reduce_host((double)v, false, &r)) return 1;
-        v = (uint32_t)r;
-        PI_HIP(hipMemcpyAsync(d, &v, sizeof v, hipMemcpyHostToDevice, st));
-        PI_HIP(hipStreamSynchronize(st));
-        return 0;
-    }
+    int allreduce_max_f32(float* d, hipStream_t st) override { return allreduce_scalar(d, true, st); }
+    int allreduce_sum_u32(uint32_t* d, hipStream_t st) override { return allreduce_scalar(d, false, st); }
 };
 
 int need_comm(pi_handle* h) {
@@ -435,6 +427,332 @@ int gather_reach(pi::Comm* c, int64_t units, Probe probe, hipStream_t st, std::v
     return 0;
 }
 
+// ---- the steps of pi_exchange_plan, in the order it takes them -----------------------------------------------------------
+using Ranges = std::vector<std::pair<int64_t, int64_t>>;
+using SweptFirst = pi::ShardPlan::SweptFirst;
+// Units the reach is measured in: rows (i0, i1) where the grid has them (2-4x fewer values to
+// exchange than whole planes of dimension 0), planes otherwise; PI_MI355_REACH_DEPTH overrides.
+int reach_depth(pi_handle* h) {
+    int depth = pi_reach_depth_max(h);
+    if (const char* e = std::getenv("PI_MI355_REACH_DEPTH")) depth = std::max(1, std::min(depth, std::atoi(e)));
+    return depth;
+}
+// Reach bitmap of this shard -> all ranks -> who sends what to whom -> halo or all-gather (`mode`; PI_PLAN_NONE: halo
+// unless a rank would receive > 60 % of an all-gather).  A halo plan keeps the segments that involve this rank.  Collective.
+int plan_halo_segments(pi_handle* h, const uint8_t* term, int mode, hipStream_t st, pi::ShardPlan* plan) {
+    pi::Comm* c = h->comm;
+    int64_t g0 = 1;
+    for (int d = 0; d < plan->depth; ++d) g0 *= h->shape[d];
+    const int64_t n = h->n_states, stride0 = n / g0;
+    std::vector<uint8_t> reach;
+    auto probe = [&](uint32_t* d_bits) { return pi_reach_units(h, term, plan->s_begin, plan->s_end, plan->depth, d_bits, st); };
+    if (gather_reach(c, g0, probe, st, reach, "exchange plan")) return 1;
+    const int64_t count = pi_plan_segments(c->world, g0, stride0, n, plan->per, reach.data(), nullptr, 0);
+    std::vector<int64_t> segs((size_t)count * 4);
+    pi_plan_segments(c->world, g0, stride0, n, plan->per, reach.data(), segs.data(), count);
+    std::vector<int64_t> recv(c->world, 0);
+    for (int64_t i = 0; i < count; ++i) recv[segs[4 * i + 1]] += segs[4 * i + 3] - segs[4 * i + 2];
+    const int64_t worst = *std::max_element(recv.begin(), recv.end()), full = plan->per * (c->world - 1);
+    plan->halo = mode == PI_PLAN_HALO || (double)worst <= 0.6 * (double)full;
+    if (!plan->halo) return 0;
+    for (int64_t i = 0; i < count; ++i) {
+        pi::ShardPlan::Seg s = {(int)segs[4 * i], (int)segs[4 * i + 1], segs[4 * i + 2], segs[4 * i + 3]};
+        if (s.src == c->rank) { plan->segs.push_back(s); plan->send_elems += s.b - s.a; }
+        else if (s.dst == c->rank) { plan->segs.push_back(s); plan->recv_elems += s.b - s.a; }
+    }
+    return 0;
+}
+
+// Sorted ranges, those at most `gap` apart merged | what ascending ranges leave of [lo, hi).
+Ranges merge_ranges(const Ranges& sorted, int64_t gap) {
+    Ranges out;
+    for (const auto& r : sorted) {
+        if (!out.empty() && r.first <= out.back().second + gap) out.back().second = std::max(out.back().second, r.second);
+        else out.push_back(r);
+    }
+    return out;
+}
+Ranges ranges_between(const Ranges& ranges, int64_t lo, int64_t hi) {
+    Ranges out;
+    for (const auto& r : ranges) {
+        if (r.first > lo) out.push_back({lo, r.first});
+        lo = std::max(lo, r.second);
+    }
+    if (lo < hi) out.push_back({lo, hi});
+    return out;
+}
+// The coarse launch ranges of the shard [s_begin, s_end): `cuts` (what travels, sorted) merged into what is swept first,
+// and the rest.  What is swept first may be coarser than what is sent: pieces less than two planes of dimension 0 (at
+// least 2^16 states) apart become ONE launch, so a shard is still swept in about three launches (low boundary planes, high
+// boundary planes, interior) although the segments that travel are single rows.  The gap is bounded by an eighth of the
+// shard: with shards of ~10 planes (C4 at 8 ranks) two planes would merge every send range into the whole shard and leave
+// nothing to sweep while the halo travels (profiles/r02/halo_granularity.txt: "1 / 0").
+void coarse_ranges(const Ranges& cuts, int64_t s_begin, int64_t s_end, int64_t n, int64_t shape0, Ranges* first, Ranges* interior) {
+    const int64_t gap = std::min(std::max<int64_t>(int64_t(1) << 16, 2 * (n / shape0)), std::max<int64_t>((s_end - s_begin) / 8, 1));
+    *first = merge_ranges(cuts, gap);
+    // a sliver between the shard's edge and its first / last send range joins that range
+    if (!first->empty()) {
+        if (first->front().first - s_begin < gap) first->front().first = s_begin;
+        if (s_end - first->back().second < gap) first->back().second = s_end;
+    }
+    *interior = ranges_between(*first, s_begin, s_end);
+}
+// Does the plan get what a transport that can deliver from inside the sweep (can_push) adds to it?  Wanted here: the
+// transport can, PI_MI355_P2P_FUSED is not 0 and the second module builds.  Every rank must take the fused steps or none: a
+// rank whose second module did not build (a failed hipRTC compile, a corrupt cache entry) would otherwise leave its peers
+// waiting in the pair probe until the communicator's time limit.  One scalar sum, collective where can_push().
+int agree_on_fused(pi_handle* h, hipStream_t st, bool* fused) {
+    pi::Comm* c = h->comm;
+    *fused = false;
+    if (!c->can_push()) return 0;
+    const char* env = std::getenv("PI_MI355_P2P_FUSED");
+    const uint32_t mine = !(env && std::atoi(env) == 0) && pi::ensure_push_module(h) == 0 ? 1u : 0u;
+    uint32_t* d_votes = nullptr;
+    PI_HIP(hipMalloc((void**)&d_votes, sizeof(uint32_t)));
+    uint32_t all = 0;
+    hipError_t e = hipMemcpyAsync(d_votes, &mine, sizeof mine, hipMemcpyHostToDevice, st);
+    int rc = e == hipSuccess ? c->allreduce_sum_u32(d_votes, st) : 1;
+    if (!rc && hipMemcpyAsync(&all, d_votes, sizeof all, hipMemcpyDeviceToHost, st) != hipSuccess) rc = 1;
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = 1;
+    (void)hipFree(d_votes);
+    if (rc) return fail("exchange plan: the ranks could not agree on the fused exchange");
+    *fused = all == (uint32_t)c->world;
+    return 0;
+}
+// Pair refinement.  With the velocity that moves coordinate 0 somewhere else than in memory dimension 1 (the fast
+// single-GPU orders put it along the lanes) the rows (i0, i1) of the segments are all reachable and the segments are whole
+// bands of planes; the fused exchange delivers per STATE, so its destination masks are cut down to the pairs (i_0, i_v)
+// every peer really reads (pi_reach_pairs_kernel) — the triangle again, in any memory order.  The segments stay as they are:
+// the unfused exchanges (a batch's first sweep on grids with terminal states, value iteration, all-gathers) travel whole.
+struct PairReach {
+    std::vector<uint8_t> need;                  // [rank * units + i_0 * gv + i_v]; empty: not measured, every state is wanted
+    int64_t units = 0, gv = 1, stv = 1, st0 = 1;
+    bool measured() const { return !need.empty(); }
+    bool wanted_by(int dst, int64_t q) const {   // does rank dst read state q at all (pair level)?
+        return need.empty() || need[(size_t)dst * (size_t)units + (size_t)((q / st0) * gv + (q / stv) % gv)] != 0;
+    }
+};
+// Measured where it can be and PI_MI355_PAIR_REACH is not 0.  Collective: every rank measures or none (same grid, same
+// order, same transport, same environment).
+int gather_pair_reach(pi_handle* h, const uint8_t* term, const pi::ShardPlan& plan, hipStream_t st, PairReach* pr) {
+    const char* e = std::getenv("PI_MI355_PAIR_REACH");
+    const int v = h->D >= 2 ? h->mem_of_user[1] : 0;
+    if (!pi::pairs_possible(h) || v == 1 || (e && std::atoi(e) == 0)) return 0;
+    pr->st0 = h->n_states / h->shape[0];
+    pr->gv = h->shape[v];
+    for (int d = v + 1; d < h->D; ++d) pr->stv *= h->shape[d];
+    pr->units = (int64_t)h->shape[0] * pr->gv;
+    return gather_reach(h->comm, pr->units, [&](uint32_t* d_bits) { return pi::reach_pairs(h, term, plan.s_begin, plan.s_end, d_bits, st); },
+                        st, pr->need, "exchange plan (pairs)");
+}
+// One walk over the plan's segments for the fused exchange: the senders of incoming ones are noted (push_senders); for every
+// outgoing one the receiver gets its bit in the destination masks — the j-th distinct receiver bit j (push_peers), at most 8
+// (more: keep the copy kernel) — and visit(segment, bit) marks what it delivers, or refuses.  Returns whether everything
+// fitted; if not, the plan names no receivers and no senders.
+template <typename Visit> bool mark_deliveries(pi::ShardPlan* plan, int rank, Visit visit) {
+    auto index_in = [](std::vector<int>& v, int x) {           // position of x in v, appended if it is new
+        auto it = std::find(v.begin(), v.end(), x);
+        return (size_t)((it == v.end() ? v.insert(it, x) : it) - v.begin());
+    };
+    for (const auto& sg : plan->segs) {
+        if (sg.dst == rank) { index_in(plan->push_senders, sg.src); continue; }
+        const size_t j = index_in(plan->push_peers, sg.dst);
+        if (j >= 8 || !visit(sg, (uint8_t)(1u << j))) {
+            plan->push_peers.clear(); plan->push_senders.clear();
+            return false;
+        }
+    }
+    return true;
+}
+int64_t count_deliveries(const std::vector<uint8_t>& dest) {     // (state, receiver) pairs
+    return std::accumulate(dest.begin(), dest.end(), int64_t(0), [](int64_t n, uint8_t m) { return n + __builtin_popcount(m); });
+}
+template <typename T> int copy_up(const std::vector<T>& v, T** d, hipStream_t st) {   // asynchronous: synchronise `st` while v is alive
+    PI_HIP(hipMalloc((void**)d, std::max<size_t>(v.size(), 1) * sizeof(T)));
+    PI_HIP(hipMemcpyAsync(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    return 0;
+}
+// Ends an upload, failed (rc) or not: copies queued so far still read the host vectors, so the stream is drained either way.
+int finish_upload(int rc, hipStream_t st) {
+    const hipError_t e = hipStreamSynchronize(st);
+    if (!rc) PI_HIP(e);
+    return rc;
+}
+// The swept-first list, the interior list and — fused plans; null otherwise — the destination mask of every swept-first entry
+// go to the device and the plan becomes `kind`.  count: the plan reports what one sweep delivers (PI_COMM_INFO_FUSED_VALUES).
+int upload_lists(pi::ShardPlan* plan, SweptFirst kind, const std::vector<int32_t>& first, const std::vector<int32_t>& inner,
+                 std::vector<uint8_t>* dest, bool count, hipStream_t st) {
+    plan->n_first = (int64_t)first.size();
+    plan->n_inner = (int64_t)inner.size();
+    int rc = copy_up(first, &plan->d_first, st) || copy_up(inner, &plan->d_inner, st);
+    if (!rc && dest) {
+        drop_deliveries_for_tests(*dest);
+        rc = copy_up(*dest, &plan->d_first_dest, st);
+        if (count) plan->fused_send_elems = count_deliveries(*dest);
+    }
+    if (finish_upload(rc, st)) return 1;
+    plan->swept_first = kind;
+    return 0;
+}
+
+// State-exact lists (grids without terminal states, pair reach measured): swept first = the states of this shard some
+// peer reads, each with the mask of those peers; the rest is the interior.  Only the fused exchange can deliver them.
+// Leaves the plan as it is when more than 8 peers read from this shard or the split is trivial.
+int plan_state_lists(pi_handle* h, const PairReach& pairs, hipStream_t st, pi::ShardPlan* plan) {
+    const int64_t len = plan->s_end - plan->s_begin;
+    std::vector<uint8_t> mark((size_t)len, 0);
+    if (!mark_deliveries(plan, h->comm->rank, [&](const pi::ShardPlan::Seg& sg, uint8_t bit) {
+            for (int64_t q = sg.a; q < sg.b; ++q)
+                if (pairs.wanted_by(sg.dst, q)) mark[(size_t)(q - plan->s_begin)] |= bit;
+            return true;
+        }))
+        return 0;
+    std::vector<int32_t> first, inner;
+    std::vector<uint8_t> dest;
+    for (int64_t q = plan->s_begin; q < plan->s_end; ++q) {
+        const uint8_t m = mark[(size_t)(q - plan->s_begin)];
+        if (m) { first.push_back((int32_t)q); dest.push_back(m); }
+        else inner.push_back((int32_t)q);
+    }
+    if (first.empty() || (int64_t)first.size() == len) { plan->push_peers.clear(); plan->push_senders.clear(); return 0; }
+    return upload_lists(plan, SweptFirst::PushLists, first, inner, &dest, true, st);
+}
+
+// Row-exact lists (grids without terminal states: the list kernel visits listed states only and copies nothing): the union
+// of the rows that travel (`cuts`), nothing merged across gaps.  Taken when it moves at least a quarter of the coarse
+// swept-first states into the interior or PI_MI355_ROW_EXACT = 1 (`want`).  `fused`: who reads which listed row, a byte per entry.
+int plan_row_lists(pi_handle* h, const Ranges& cuts, int want, bool fused, hipStream_t st, pi::ShardPlan* plan) {
+    const Ranges exact = merge_ranges(cuts, 0);
+    int64_t exact_states = 0, coarse_states = 0;
+    for (const auto& r : exact) exact_states += r.second - r.first;
+    for (const auto& r : plan->send_ranges) coarse_states += r.second - r.first;
+    const bool possible = !exact.empty() && exact_states < plan->s_end - plan->s_begin;
+    const bool pays = exact.size() > plan->send_ranges.size() && 4 * exact_states <= 3 * coarse_states;
+    if (!possible || !(want == 1 || pays)) return 0;
+    plan->first_exact = exact;
+    plan->inner_exact = ranges_between(exact, plan->s_begin, plan->s_end);
+    std::vector<int32_t> first, inner;
+    std::vector<int64_t> start;                                 // position of every range of `exact` in the list
+    first.reserve((size_t)exact_states);
+    inner.reserve((size_t)(plan->s_end - plan->s_begin - exact_states));
+    for (const auto& r : exact) {
+        start.push_back((int64_t)first.size());
+        for (int64_t q = r.first; q < r.second; ++q) first.push_back((int32_t)q);
+    }
+    for (const auto& r : plan->inner_exact)
+        for (int64_t q = r.first; q < r.second; ++q) inner.push_back((int32_t)q);
+    std::vector<uint8_t> dest(first.size(), 0);
+    fused = fused && mark_deliveries(plan, h->comm->rank, [&](const pi::ShardPlan::Seg& sg, uint8_t bit) {
+        // the range of `exact` that holds [a, b): the last one that starts at or before a
+        const size_t i = (size_t)(std::upper_bound(exact.begin(), exact.end(), std::make_pair(sg.a, INT64_MAX)) - exact.begin()) - 1;
+        if (i >= exact.size() || sg.a < exact[i].first || sg.b > exact[i].second) return false;
+        for (int64_t q = sg.a; q < sg.b; ++q) dest[(size_t)(start[i] + (q - exact[i].first))] |= bit;
+        return true;
+    });
+    // fused_send_elems is NOT counted for this plan: PI_COMM_INFO_FUSED_VALUES has always answered -1 for it (recorded runs hold that)
+    return upload_lists(plan, fused ? SweptFirst::PushLists : SweptFirst::Lists, first, inner, fused ? &dest : nullptr, false, st);
+}
+
+// Live-state masks (grids WITH terminal states whose shard keeps a live-state list): later sweeps of a batch visit the
+// shard's live states only — who reads which of them.  Where some are read by nobody the plan gets state-exact lists for
+// these sweeps too: swept first = the live states some peer reads (with their masks), interior = the shard's other live states
+// — instead of the coarse ranges, which in the orders that keep the coupling velocity off memory dimension 1 are bands of planes.
+int plan_live_masks(pi_handle* h, const PairReach& pairs, hipStream_t st, pi::ShardPlan* plan) {
+    int64_t base = 0, total = 0;
+    pi::live_span(h, plan->s_begin, plan->s_end, &base, &total);
+    if (total <= 0) return 0;
+    std::vector<uint8_t> dest((size_t)total, 0);
+    std::vector<int32_t> states;
+    if (!mark_deliveries(plan, h->comm->rank, [&](const pi::ShardPlan::Seg& sg, uint8_t bit) {
+            int64_t first = 0, count = 0;
+            pi::live_span(h, sg.a, sg.b, &first, &count);
+            states.clear();
+            if (pairs.measured()) pi::live_states(h, sg.a, sg.b, states);      // the listed states of [a, b), ascending
+            for (int64_t k = 0; k < count; ++k)
+                if (!pairs.measured() || pairs.wanted_by(sg.dst, states[(size_t)k])) dest[(size_t)(first - base + k)] |= bit;
+            return true;
+        }))
+        return 0;
+    plan->live_list = h->d_live;
+    plan->live_list_count = h->live_count;
+    plan->fused_send_elems = count_deliveries(dest);
+    std::vector<int32_t> every, first, inner;
+    std::vector<uint8_t> dfirst;
+    pi::live_states(h, plan->s_begin, plan->s_end, every);
+    if ((int64_t)every.size() == total) {
+        for (int64_t k = 0; k < total; ++k) {
+            if (dest[(size_t)k]) { first.push_back(every[(size_t)k]); dfirst.push_back(dest[(size_t)k]); }
+            else inner.push_back(every[(size_t)k]);
+        }
+    }
+    if (!first.empty() && !inner.empty()) return upload_lists(plan, SweptFirst::PushLiveLists, first, inner, &dfirst, false, st);
+    if (finish_upload(copy_up(dest, &plan->d_live_dest, st), st)) return 1;
+    plan->live_dest_base = base;
+    plan->swept_first = SweptFirst::PushLiveSpans;
+    return 0;
+}
+
+// ---- one sharded evaluation sweep: what peers wait for, the hand-over, the interior ------------------------------------
+struct ShardSweep {
+    const float* src; float* dst;   // the buffers of this sweep: dst = V'(src)
+    const int32_t* policy; const uint8_t* term;
+    float gamma;
+    bool want;          // this sweep leaves its residual in the accumulator slots
+    int k;              // index in its batch
+    bool live, fused;   // the handle holds a live-state list for `term` that covers the shard | the swept-first kernel delivers
+    hipStream_t st;
+};
+// Does sweep k of a batch go through the fused exchange?  Lists with masks: every sweep.  Live-state masks: the later sweeps,
+// over the list they were built from (terminal states' values never change: every rank holds them since the first sweep).
+bool fused_sweep(const pi_handle* h, const uint8_t* term, int k, bool live) {
+    const pi::ShardPlan* p = h->plan;
+    if (!p->overlapped()) return false;
+    if (p->swept_first == SweptFirst::PushLists) return term == nullptr;
+    return p->live_push() && k >= 1 && live && p->live_list == h->d_live && p->live_list_count == h->live_count;
+}
+// Is the sweep split into the plan's two state lists (otherwise: into its coarse ranges)?  Live lists hold no terminal state,
+// and a batch's first sweep (k = 0, never fused) has to copy the terminal values: it takes the coarse ranges like any unfused sweep.
+bool swept_by_lists(const pi::ShardPlan* p, const ShardSweep& s) {
+    return p->row_lists() ? s.term == nullptr : s.fused && p->swept_first == SweptFirst::PushLiveLists;
+}
+// One launch range of one sweep: the later sweeps of a batch (k >= 1) visit only the range's live states when
+// the handle holds a list for this mask (pi_prepare_mask) — the first one copies the terminal values.
+int sweep_range(pi_handle* h, const ShardSweep& s, int64_t a, int64_t b) {
+    if (s.k >= 1 && s.live) {
+        int64_t first = 0, count = 0;
+        pi::live_span(h, a, b, &first, &count);
+        return pi::launch_eval_live(h, s.src, s.dst, s.policy, first, count, s.gamma, s.want, s.st);
+    }
+    return pi::launch_eval(h, s.src, s.dst, s.policy, s.term, a, b, s.gamma, s.want, s.st, s.k >= 1);
+}
+// What peers wait for (no overlap: the whole shard).  `table`: the peers' addresses of s.dst for the push kernel, fused sweeps only.
+int sweep_first_part(pi_handle* h, const ShardSweep& s, float* const* table) {
+    const pi::ShardPlan* p = h->plan;
+    if (!p->overlapped()) return sweep_range(h, s, p->s_begin, p->s_end);
+    const int n_peers = (int)p->push_peers.size();
+    if (swept_by_lists(p, s))
+        return s.fused ? pi::launch_eval_push(h, s.src, s.dst, s.policy, p->d_first, p->d_first_dest, table, n_peers, p->n_first,
+                                              s.gamma, s.want, s.st)
+                       : pi::launch_eval_live(h, s.src, s.dst, s.policy, 0, p->n_first, s.gamma, s.want, s.st, p->d_first);
+    for (const auto& r : p->send_ranges) {
+        int64_t first = 0, count = 0;                       // fused: the live states of the range, with their masks
+        if (s.fused) pi::live_span(h, r.first, r.second, &first, &count);
+        if (s.fused ? pi::launch_eval_push(h, s.src, s.dst, s.policy, h->d_live + first, p->d_live_dest + (first - p->live_dest_base),
+                                           table, n_peers, count, s.gamma, s.want, s.st)
+                    : sweep_range(h, s, r.first, r.second)) return 1;
+    }
+    return 0;
+}
+// The rest of the shard, swept while the first part travels.
+int sweep_interior_part(pi_handle* h, const ShardSweep& s) {
+    const pi::ShardPlan* p = h->plan;
+    if (!p->overlapped()) return 0;
+    if (swept_by_lists(p, s)) return pi::launch_eval_live(h, s.src, s.dst, s.policy, 0, p->n_inner, s.gamma, s.want, s.st, p->d_inner);
+    for (const auto& r : p->interior)
+        if (sweep_range(h, s, r.first, r.second)) return 1;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -498,23 +816,20 @@ int pi_comm_destroy(pi_handle* h) {
 
 int pi_comm_info(pi_handle* h, int what) {
     if (!h || !h->comm) return -1;
+    const pi::ShardPlan* p = h->plan;
+    auto clip = [](int64_t v) { return (int)std::min<int64_t>(v, INT32_MAX); };
     switch (what) {
         case PI_COMM_INFO_RANK: return h->comm->rank;
         case PI_COMM_INFO_WORLD: return h->comm->world;
-        case PI_COMM_INFO_TRANSPORT:
-            return std::strcmp(h->comm->kind(), "rccl") == 0  ? PI_TRANSPORT_RCCL
-                 : std::strcmp(h->comm->kind(), "p2p") == 0 ? PI_TRANSPORT_P2P
-                                                            : PI_TRANSPORT_IN_PROCESS;
-        case PI_COMM_INFO_PLAN: return h->plan ? (h->plan->halo ? PI_PLAN_HALO : PI_PLAN_ALLGATHER) : PI_PLAN_NONE;
-        case PI_COMM_INFO_REACH_UNITS: return h->plan ? h->plan->depth : 0;
-        case PI_COMM_INFO_ROW_EXACT: return h->plan && h->plan->row_exact ? 1 : 0;
-        case PI_COMM_INFO_FUSED: return h->plan && ((h->plan->row_exact && h->plan->push_ok) || h->plan->live_push_ok) ? 1 : 0;
-        case PI_COMM_INFO_PAIR_EXACT: return h->plan && h->plan->pair_exact ? 1 : 0;
-        case PI_COMM_INFO_FUSED_VALUES: return h->plan ? (int)std::min<int64_t>(h->plan->fused_send_elems, INT32_MAX) : -1;
-        case PI_COMM_INFO_FIRST_ENTRIES:
-            return h->plan && (h->plan->row_exact || h->plan->live_exact) ? (int)std::min<int64_t>(h->plan->n_first, INT32_MAX) : -1;
-        case PI_COMM_INFO_INTERIOR_ENTRIES:
-            return h->plan && (h->plan->row_exact || h->plan->live_exact) ? (int)std::min<int64_t>(h->plan->n_inner, INT32_MAX) : -1;
+        case PI_COMM_INFO_TRANSPORT: return h->comm->transport();
+        case PI_COMM_INFO_PLAN: return p ? (p->halo ? PI_PLAN_HALO : PI_PLAN_ALLGATHER) : PI_PLAN_NONE;
+        case PI_COMM_INFO_REACH_UNITS: return p ? p->depth : 0;
+        case PI_COMM_INFO_ROW_EXACT: return p && p->row_lists() ? 1 : 0;
+        case PI_COMM_INFO_FUSED: return p && p->fused() ? 1 : 0;
+        case PI_COMM_INFO_PAIR_EXACT: return p && p->pair_exact ? 1 : 0;
+        case PI_COMM_INFO_FUSED_VALUES: return p ? clip(p->fused_send_elems) : -1;
+        case PI_COMM_INFO_FIRST_ENTRIES: return p && p->has_lists() ? clip(p->n_first) : -1;
+        case PI_COMM_INFO_INTERIOR_ENTRIES: return p && p->has_lists() ? clip(p->n_inner) : -1;
         default: return -1;
     }
 }
@@ -585,305 +900,44 @@ int64_t pi_plan_segments(int world, int64_t g0, int64_t stride0, int64_t n_state
 // PI_PLAN_HALO.  `overlap` = 0 disables the send-first / interior-while-travelling split.
 // info[0] = mode chosen (PI_PLAN_ALLGATHER | PI_PLAN_HALO), info[1] = elements this rank receives per sweep,
 // info[2] = elements it sends, info[3] = number of send ranges, info[4] = interior ranges.
-int pi_exchange_plan(pi_handle* h, const uint8_t* term, int64_t per, int mode, int overlap,
-                     int64_t* info, void* stream) {
+int pi_exchange_plan(pi_handle* h, const uint8_t* term, int64_t per, int mode, int overlap, int64_t* info, void* stream) {
     if (need_comm(h)) return 1;
     if (per < 1) return fail("bad argument");
     pi::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
     pi::Comm* c = h->comm;
-    // Units the reach is measured in: rows (i0, i1) where the grid has them (2-4x fewer values to
-    // exchange than whole planes of dimension 0), planes otherwise; PI_MI355_REACH_DEPTH overrides.
-    int depth = pi_reach_depth_max(h);
-    if (const char* e = std::getenv("PI_MI355_REACH_DEPTH")) depth = std::max(1, std::min(depth, std::atoi(e)));
-    int64_t g0 = 1;
-    for (int d = 0; d < depth; ++d) g0 *= h->shape[d];
-    const int64_t n = h->n_states, stride0 = n / g0;
+    const int64_t n = h->n_states;
     if (per * c->world < n) return fail("per * world < n_states");
     std::unique_ptr<pi::ShardPlan> plan(new pi::ShardPlan);
     plan->per = per;
-    plan->depth = depth;
+    plan->depth = reach_depth(h);
     plan->s_begin = std::min((int64_t)c->rank * per, n);
     plan->s_end = std::min(plan->s_begin + per, n);
-    if (mode != PI_PLAN_ALLGATHER) {
-        // reach bitmap of this shard -> all ranks
-        std::vector<uint8_t> reach;
-        if (gather_reach(c, g0, [&](uint32_t* d_bits) { return pi_reach_units(h, term, plan->s_begin, plan->s_end, depth, d_bits, stream); },
-                         st, reach, "exchange plan"))
-            return 1;
-        const int64_t count = pi_plan_segments(c->world, g0, stride0, n, per, reach.data(), nullptr, 0);
-        std::vector<int64_t> segs((size_t)count * 4);
-        pi_plan_segments(c->world, g0, stride0, n, per, reach.data(), segs.data(), count);
-        std::vector<int64_t> recv(c->world, 0);
-        for (int64_t i = 0; i < count; ++i) recv[segs[4 * i + 1]] += segs[4 * i + 3] - segs[4 * i + 2];
-        const int64_t full = per * (c->world - 1);
-        const int64_t worst = *std::max_element(recv.begin(), recv.end());
-        plan->halo = mode == PI_PLAN_HALO || (double)worst <= 0.6 * (double)full;
-        if (plan->halo) {
-            for (int64_t i = 0; i < count; ++i) {
-                pi::ShardPlan::Seg s = {(int)segs[4 * i], (int)segs[4 * i + 1], segs[4 * i + 2], segs[4 * i + 3]};
-                if (s.src == c->rank) { plan->segs.push_back(s); plan->send_elems += s.b - s.a; }
-                else if (s.dst == c->rank) { plan->segs.push_back(s); plan->recv_elems += s.b - s.a; }
-            }
-        }
-    }
+    if (mode != PI_PLAN_ALLGATHER && plan_halo_segments(h, term, mode, st, plan.get())) return 1;
     if (plan->halo && overlap) {
         // sub-ranges of this shard that peers wait for (swept first), and the rest
-        std::vector<std::pair<int64_t, int64_t>> cuts;
+        Ranges cuts;
         for (const auto& s : plan->segs)
             if (s.src == c->rank) cuts.push_back({s.a, s.b});
         std::sort(cuts.begin(), cuts.end());
-        // What is swept first may be coarser than what is sent: pieces less than two planes of
-        // dimension 0 (at least 2^16 states) apart become ONE launch, so a shard is still swept
-        // in about three launches (low boundary planes, high boundary planes, interior) although
-        // the segments that travel are single rows.
-        // The gap is bounded by an eighth of the shard: with shards of ~10 planes (C4 at 8 ranks) two
-        // planes would merge every send range into the whole shard and leave nothing to sweep while
-        // the halo travels (profiles/r02/halo_granularity.txt: "1 / 0").
-        const int64_t gap = std::min(std::max<int64_t>(int64_t(1) << 16, 2 * (n / h->shape[0])),
-                                     std::max<int64_t>((plan->s_end - plan->s_begin) / 8, 1));
-        for (const auto& r : cuts) {
-            if (!plan->send_ranges.empty() && r.first <= plan->send_ranges.back().second + gap)
-                plan->send_ranges.back().second = std::max(plan->send_ranges.back().second, r.second);
-            else
-                plan->send_ranges.push_back(r);
-        }
-        // a sliver between the shard's edge and its first / last send range joins that range
-        if (!plan->send_ranges.empty()) {
-            if (plan->send_ranges.front().first - plan->s_begin < gap) plan->send_ranges.front().first = plan->s_begin;
-            if (plan->s_end - plan->send_ranges.back().second < gap) plan->send_ranges.back().second = plan->s_end;
-        }
-        int64_t pos = plan->s_begin;
-        for (const auto& r : plan->send_ranges) {
-            if (r.first > pos) plan->interior.push_back({pos, r.first});
-            pos = std::max(pos, r.second);
-        }
-        if (pos < plan->s_end) plan->interior.push_back({pos, plan->s_end});
-        // ---- what a transport that can deliver from inside the sweep (can_push) adds to the plan --------------------
-        const char* fused_env = std::getenv("PI_MI355_P2P_FUSED");
-        bool fused_wanted = c->can_push() && !(fused_env && std::atoi(fused_env) == 0) && pi::ensure_push_module(h) == 0;
-        if (c->can_push()) {
-            // every rank must take the fused branches below or none: a rank whose second module did not build (a failed
-            // hipRTC compile, a corrupt cache entry) would otherwise leave its peers waiting in the pair probe until the
-            // communicator's time limit.  One scalar sum: fused only if it is wanted everywhere.
-            uint32_t* d_votes = nullptr;
-            PI_HIP(hipMalloc((void**)&d_votes, sizeof(uint32_t)));
-            const uint32_t mine = fused_wanted ? 1u : 0u;
-            uint32_t all = 0;
-            hipError_t e = hipMemcpyAsync(d_votes, &mine, sizeof mine, hipMemcpyHostToDevice, st);
-            int rc = e == hipSuccess ? c->allreduce_sum_u32(d_votes, st) : 1;
-            if (!rc && hipMemcpyAsync(&all, d_votes, sizeof all, hipMemcpyDeviceToHost, st) != hipSuccess) rc = 1;
-            if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = 1;
-            (void)hipFree(d_votes);
-            if (rc) return fail("exchange plan: the ranks could not agree on the fused exchange");
-            fused_wanted = all == (uint32_t)c->world;
-        }
-        // Pair refinement.  With the velocity that moves coordinate 0 somewhere else than in memory dimension 1 (the fast
-        // single-GPU orders put it along the lanes) the rows (i0, i1) above are all reachable and the segments are whole
-        // bands of planes; the fused exchange delivers per STATE, so the destination masks below are cut down to the
-        // pairs (i_0, i_v) every peer really reads (pi_reach_pairs_kernel) — the triangle again, in any memory order.
-        // The segments stay as they are: the unfused exchanges (a batch's first sweep on grids with terminal states,
-        // value iteration, all-gathers) travel whole.  Collective: every rank takes this branch or none (same grid,
-        // same order, same transport, same environment).
-        std::vector<uint8_t> need2;
-        int64_t units = 0, gv = 1, stv = 1;
-        const int64_t st0 = n / h->shape[0];
-        {
-            const char* e = std::getenv("PI_MI355_PAIR_REACH");
-            const int v = h->D >= 2 ? h->mem_of_user[1] : 0;
-            if (fused_wanted && pi::pairs_possible(h) && v != 1 && !(e && std::atoi(e) == 0)) {
-                gv = h->shape[v];
-                for (int d = v + 1; d < h->D; ++d) stv *= h->shape[d];
-                units = (int64_t)h->shape[0] * gv;
-                if (gather_reach(c, units, [&](uint32_t* d_bits) { return pi::reach_pairs(h, term, plan->s_begin, plan->s_end, d_bits, st); },
-                                 st, need2, "exchange plan (pairs)"))
-                    return 1;
-                plan->pair_exact = true;
-            }
-        }
-        auto wanted_by = [&](int dst, int64_t q) {           // does rank dst read state q at all (pair level)?
-            return need2.empty() || need2[(size_t)dst * (size_t)units + (size_t)((q / st0) * gv + (q / stv) % gv)] != 0;
-        };
-        // bit of a receiver in the destination masks: the j-th distinct one, at most 8 (more: keep the copy kernel)
-        auto peer_bit = [&](int dst, uint8_t* bit) {
-            auto it = std::find(plan->push_peers.begin(), plan->push_peers.end(), dst);
-            if (it == plan->push_peers.end()) {
-                if (plan->push_peers.size() == 8) return false;
-                plan->push_peers.push_back(dst);
-                it = plan->push_peers.end() - 1;
-            }
-            *bit = (uint8_t)(1u << (it - plan->push_peers.begin()));
-            return true;
-        };
-        auto note_sender = [&](int src) {
-            if (std::find(plan->push_senders.begin(), plan->push_senders.end(), src) == plan->push_senders.end())
-                plan->push_senders.push_back(src);
-        };
-        auto upload_lists = [&](const std::vector<int32_t>& first, const std::vector<int32_t>& inner) -> int {
-            plan->n_first = (int64_t)first.size();
-            plan->n_inner = (int64_t)inner.size();
-            PI_HIP(hipMalloc((void**)&plan->d_first, std::max<size_t>(first.size(), 1) * sizeof(int32_t)));
-            PI_HIP(hipMalloc((void**)&plan->d_inner, std::max<size_t>(inner.size(), 1) * sizeof(int32_t)));
-            PI_HIP(hipMemcpyAsync(plan->d_first, first.data(), first.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            PI_HIP(hipMemcpyAsync(plan->d_inner, inner.data(), inner.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            PI_HIP(hipStreamSynchronize(st));
-            plan->row_exact = true;
-            return 0;
-        };
+        coarse_ranges(cuts, plan->s_begin, plan->s_end, n, h->shape[0], &plan->send_ranges, &plan->interior);
+        // the collectives of the fused exchange, in this order on every rank
+        bool fused = false;
+        PairReach pairs;
+        if (agree_on_fused(h, st, &fused)) return 1;
+        if (fused && gather_pair_reach(h, term, *plan, st, &pairs)) return 1;
+        plan->pair_exact = pairs.measured();
+        // What is swept first, beyond the coarse ranges — the first of these that yields something:
+        //   state-exact lists   no terminal states, pair reach measured, this shard sends something; always fused
+        //   row-exact lists     no terminal states, where they pay or PI_MI355_ROW_EXACT = 1 (= 0: neither kind of list)
+        //   live-state masks    the shard keeps a live-state list for this mask; fused exchange only
         int want = -1;
         if (const char* e = std::getenv("PI_MI355_ROW_EXACT")) want = std::atoi(e) != 0 ? 1 : 0;
-        if (plan->pair_exact && term == nullptr && !cuts.empty() && want != 0) {
-            // State-exact lists (grids without terminal states): swept first = the states of this shard some peer reads,
-            // each with the mask of those peers; the rest is the interior.  Only the fused exchange can deliver them.
-            const int64_t len = plan->s_end - plan->s_begin;
-            std::vector<uint8_t> mark((size_t)len, 0);
-            bool fits = true;
-            for (const auto& sg : plan->segs) {
-                if (sg.dst == c->rank) { note_sender(sg.src); continue; }
-                uint8_t bit = 0;
-                if (!peer_bit(sg.dst, &bit)) { fits = false; break; }
-                for (int64_t q = sg.a; q < sg.b; ++q)
-                    if (wanted_by(sg.dst, q)) mark[(size_t)(q - plan->s_begin)] |= bit;
-            }
-            if (fits) {
-                std::vector<int32_t> first, inner;
-                std::vector<uint8_t> dest;
-                for (int64_t q = plan->s_begin; q < plan->s_end; ++q) {
-                    const uint8_t m = mark[(size_t)(q - plan->s_begin)];
-                    if (m) { first.push_back((int32_t)q); dest.push_back(m); }
-                    else inner.push_back((int32_t)q);
-                }
-                if (!first.empty() && (int64_t)first.size() < len) {
-                    if (upload_lists(first, inner)) return 1;
-                    drop_deliveries_for_tests(dest);
-                    PI_HIP(hipMalloc((void**)&plan->d_first_dest, dest.size()));
-                    PI_HIP(hipMemcpy(plan->d_first_dest, dest.data(), dest.size(), hipMemcpyHostToDevice));
-                    plan->push_ok = true;
-                    plan->fused_send_elems = 0;
-                    for (uint8_t m : dest) plan->fused_send_elems += __builtin_popcount(m);
-                }
-            }
-            if (!plan->push_ok) { plan->push_peers.clear(); plan->push_senders.clear(); }
-        }
-        // Row-exact alternative: the union of the rows that travel, nothing merged across gaps.  Taken when the grid
-        // has no terminal states (the list kernel visits listed states only and copies nothing) and it moves at least a
-        // quarter of the coarse swept-first states into the interior; PI_MI355_ROW_EXACT=0 / 1 forces it off / on.
-        if (!plan->row_exact) {
-            std::vector<std::pair<int64_t, int64_t>> exact;
-            for (const auto& r : cuts) {
-                if (!exact.empty() && r.first <= exact.back().second)
-                    exact.back().second = std::max(exact.back().second, r.second);
-                else
-                    exact.push_back(r);
-            }
-            int64_t exact_states = 0, coarse_states = 0;
-            for (const auto& r : exact) exact_states += r.second - r.first;
-            for (const auto& r : plan->send_ranges) coarse_states += r.second - r.first;
-            const bool possible = term == nullptr && !exact.empty() && exact_states < plan->s_end - plan->s_begin;
-            const bool pays = exact.size() > plan->send_ranges.size() && 4 * exact_states <= 3 * coarse_states;
-            if (possible && (want == 1 || (want < 0 && pays))) {
-                std::vector<int32_t> first, inner;
-                first.reserve((size_t)exact_states);
-                inner.reserve((size_t)(plan->s_end - plan->s_begin - exact_states));
-                int64_t at = plan->s_begin;
-                for (const auto& r : exact) {
-                    if (r.first > at) plan->inner_exact.push_back({at, r.first});
-                    for (int64_t q = at; q < r.first; ++q) inner.push_back((int32_t)q);
-                    for (int64_t q = r.first; q < r.second; ++q) first.push_back((int32_t)q);
-                    at = r.second;
-                }
-                if (at < plan->s_end) plan->inner_exact.push_back({at, plan->s_end});
-                for (int64_t q = at; q < plan->s_end; ++q) inner.push_back((int32_t)q);
-                plan->first_exact = exact;
-                if (upload_lists(first, inner)) return 1;
-                // who reads which listed row: one byte per entry
-                std::vector<uint8_t> dest(first.size(), 0);
-                std::vector<int64_t> start(exact.size() + 1, 0);
-                for (size_t i = 0; i < exact.size(); ++i) start[i + 1] = start[i] + (exact[i].second - exact[i].first);
-                bool fits = fused_wanted;
-                for (const auto& sg : plan->segs) {
-                    if (!fits) break;
-                    if (sg.dst == c->rank) { note_sender(sg.src); continue; }
-                    uint8_t bit = 0;
-                    if (!peer_bit(sg.dst, &bit)) { fits = false; break; }
-                    // the range of `exact` that holds [a, b): the last one that starts at or before a
-                    size_t i = (size_t)(std::upper_bound(exact.begin(), exact.end(), std::make_pair(sg.a, INT64_MAX)) - exact.begin()) - 1;
-                    if (i >= exact.size() || sg.a < exact[i].first || sg.b > exact[i].second) { fits = false; break; }
-                    for (int64_t q = sg.a; q < sg.b; ++q) dest[(size_t)(start[i] + (q - exact[i].first))] |= bit;
-                }
-                if (fits && !dest.empty()) {
-                    drop_deliveries_for_tests(dest);
-                    PI_HIP(hipMalloc((void**)&plan->d_first_dest, dest.size()));
-                    PI_HIP(hipMemcpy(plan->d_first_dest, dest.data(), dest.size(), hipMemcpyHostToDevice));
-                    plan->push_ok = true;
-                } else {
-                    plan->push_peers.clear();
-                    plan->push_senders.clear();
-                }
-            }
-        }
-        if (!plan->row_exact && fused_wanted && pi::live_usable(h, term, plan->s_begin, plan->s_end)) {
-            // later sweeps of a batch visit the shard's live states only: who reads which of them
-            int64_t base = 0, total = 0;
-            pi::live_span(h, plan->s_begin, plan->s_end, &base, &total);
-            std::vector<uint8_t> dest((size_t)total, 0);
-            std::vector<int32_t> states;
-            bool fits = total > 0;
-            for (const auto& sg : plan->segs) {
-                if (!fits) break;
-                if (sg.dst == c->rank) { note_sender(sg.src); continue; }
-                uint8_t bit = 0;
-                if (!peer_bit(sg.dst, &bit)) { fits = false; break; }
-                int64_t first = 0, count = 0;
-                pi::live_span(h, sg.a, sg.b, &first, &count);
-                if (need2.empty()) {
-                    for (int64_t k = first - base; k < first - base + count; ++k) dest[(size_t)k] |= bit;
-                } else {
-                    states.clear();
-                    pi::live_states(h, sg.a, sg.b, states);              // the listed states of [a, b), ascending
-                    for (int64_t k = 0; k < count; ++k)
-                        if (wanted_by(sg.dst, states[(size_t)k])) dest[(size_t)(first - base + k)] |= bit;
-                }
-            }
-            if (fits) {
-                plan->live_list = h->d_live;
-                plan->live_list_count = h->live_count;
-                plan->live_push_ok = true;
-                plan->fused_send_elems = 0;
-                for (uint8_t m : dest) plan->fused_send_elems += __builtin_popcount(m);
-                // State-exact lists for these sweeps too: swept first = the live states some peer reads (with their
-                // masks), interior = the shard's other live states — instead of the coarse ranges, which in the orders
-                // that keep the coupling velocity off memory dimension 1 are whole bands of planes.
-                std::vector<int32_t> every, first, inner;
-                std::vector<uint8_t> dfirst;
-                pi::live_states(h, plan->s_begin, plan->s_end, every);
-                if ((int64_t)every.size() == total) {
-                    for (int64_t k = 0; k < total; ++k) {
-                        if (dest[(size_t)k]) { first.push_back(every[(size_t)k]); dfirst.push_back(dest[(size_t)k]); }
-                        else inner.push_back(every[(size_t)k]);
-                    }
-                }
-                if (!first.empty() && !inner.empty()) {
-                    drop_deliveries_for_tests(dfirst);
-                    plan->n_first = (int64_t)first.size();
-                    plan->n_inner = (int64_t)inner.size();
-                    PI_HIP(hipMalloc((void**)&plan->d_first, first.size() * sizeof(int32_t)));
-                    PI_HIP(hipMalloc((void**)&plan->d_inner, inner.size() * sizeof(int32_t)));
-                    PI_HIP(hipMalloc((void**)&plan->d_first_dest, dfirst.size()));
-                    PI_HIP(hipMemcpy(plan->d_first, first.data(), first.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-                    PI_HIP(hipMemcpy(plan->d_inner, inner.data(), inner.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-                    PI_HIP(hipMemcpy(plan->d_first_dest, dfirst.data(), dfirst.size(), hipMemcpyHostToDevice));
-                    plan->live_exact = true;
-                } else {
-                    PI_HIP(hipMalloc((void**)&plan->d_live_dest, dest.size()));
-                    PI_HIP(hipMemcpy(plan->d_live_dest, dest.data(), dest.size(), hipMemcpyHostToDevice));
-                    plan->live_dest_base = base;
-                }
-            } else {
-                plan->push_peers.clear();
-                plan->push_senders.clear();
-            }
-        }
+        const bool lists_possible = term == nullptr && want != 0;
+        if (lists_possible && plan->pair_exact && !cuts.empty() && plan_state_lists(h, pairs, st, plan.get())) return 1;
+        if (lists_possible && plan->swept_first == SweptFirst::Ranges && plan_row_lists(h, cuts, want, fused, st, plan.get())) return 1;
+        const bool live = fused && pi::live_usable(h, term, plan->s_begin, plan->s_end);
+        if (live && plan->swept_first == SweptFirst::Ranges && plan_live_masks(h, pairs, st, plan.get())) return 1;
         PI_HIP(hipStreamCreateWithFlags(&plan->comm_stream, hipStreamNonBlocking));
         PI_HIP(hipEventCreateWithFlags(&plan->ev_ready, hipEventDisableTiming));
         PI_HIP(hipEventCreateWithFlags(&plan->ev_done, hipEventDisableTiming));
@@ -911,12 +965,10 @@ int64_t pi_plan_ranges(pi_handle* h, int64_t* ranges, int64_t cap) {
     if (need_plan(h)) return -1;
     const pi::ShardPlan* p = h->plan;
     std::vector<std::array<int64_t, 3>> all;
-    if (p->halo && p->comm_stream != nullptr && p->row_exact && !p->first_exact.empty()) {
-        for (const auto& r : p->first_exact) all.push_back({0, r.first, r.second});
-        for (const auto& r : p->inner_exact) all.push_back({1, r.first, r.second});
-    } else if (p->halo && p->comm_stream != nullptr) {
-        for (const auto& r : p->send_ranges) all.push_back({0, r.first, r.second});
-        for (const auto& r : p->interior) all.push_back({1, r.first, r.second});
+    const bool rows = !p->first_exact.empty();              // row-exact lists: the ranges they were made from
+    if (p->overlapped()) {
+        for (const auto& r : rows ? p->first_exact : p->send_ranges) all.push_back({0, r.first, r.second});
+        for (const auto& r : rows ? p->inner_exact : p->interior) all.push_back({1, r.first, r.second});
     } else if (p->s_end > p->s_begin) {
         all.push_back({0, p->s_begin, p->s_end});
     }
@@ -925,25 +977,17 @@ int64_t pi_plan_ranges(pi_handle* h, int64_t* ranges, int64_t cap) {
     return (int64_t)all.size();
 }
 
-// One part of a sharded evaluation sweep WITHOUT the exchange, exactly as pi_eval_sweeps_sharded launches it:
-// part 0 = what peers wait for (swept first), part 1 = the interior.  For measurements and tests: both parts
-// together are one sweep of the shard.  A plan without overlap has everything in part 0.
+// One part of a sharded evaluation sweep WITHOUT the exchange, launched by the functions pi_eval_sweeps_sharded
+// launches the first sweep of a batch with: part 0 = what peers wait for (swept first), part 1 = the interior.  For
+// measurements and tests: both parts together are one sweep of the shard.  A plan without overlap has everything in part 0.
 int pi_eval_sweep_part(pi_handle* h, const float* V, float* Vnew, const int32_t* policy, const uint8_t* term, int part,
                        float gamma, void* stream) {
     if (need_plan(h)) return 1;
     if (!V || !Vnew || !policy || V == Vnew) return fail("bad device pointer");
     if (part != 0 && part != 1) return fail("part must be 0 (swept first) or 1 (interior)");
     pi::DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const pi::ShardPlan* p = h->plan;
-    if (!(p->halo && p->comm_stream != nullptr))
-        return part == 0 ? pi::launch_eval(h, V, Vnew, policy, term, p->s_begin, p->s_end, gamma, false, st) : 0;
-    if (p->row_exact && term == nullptr)
-        return pi::launch_eval_live(h, V, Vnew, policy, 0, part == 0 ? p->n_first : p->n_inner, gamma, false, st,
-                                    part == 0 ? p->d_first : p->d_inner);
-    for (const auto& r : (part == 0 ? p->send_ranges : p->interior))
-        if (pi::launch_eval(h, V, Vnew, policy, term, r.first, r.second, gamma, false, st)) return 1;
-    return 0;
+    const ShardSweep s = {V, Vnew, policy, term, gamma, false, 0, false, false, (hipStream_t)stream};
+    return part == 0 ? sweep_first_part(h, s, nullptr) : sweep_interior_part(h, s);
 }
 
 // Make this rank's freshly written shard of `V_full` visible where the other ranks read it.
@@ -958,9 +1002,8 @@ int pi_exchange_V(pi_handle* h, float* V_full, void* stream) {
 // n_sweeps evaluation sweeps of this rank's shard, ping-ponging between Va and Vb exactly like
 // pi_eval_sweeps, with the exchange after every sweep; d_delta (nullable) receives the residual of
 // the LAST sweep, already reduced (MAX) over all ranks.  Nothing returns to the host in between.
-int pi_eval_sweeps_sharded(pi_handle* h, float* Va, float* Vb, const int32_t* policy,
-                           const uint8_t* term, float gamma, int n_sweeps, float* d_delta,
-                           void* stream) {
+int pi_eval_sweeps_sharded(pi_handle* h, float* Va, float* Vb, const int32_t* policy, const uint8_t* term, float gamma,
+                           int n_sweeps, float* d_delta, void* stream) {
     if (need_plan(h)) return 1;
     if (n_sweeps < 0) return fail("n_sweeps < 0");
     if (!Va || !Vb || !policy) return fail("null device pointer");
@@ -969,80 +1012,37 @@ int pi_eval_sweeps_sharded(pi_handle* h, float* Va, float* Vb, const int32_t* po
     pi::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
     pi::ShardPlan* p = h->plan;
-    const bool overlap = p->halo && p->comm_stream != nullptr;
-    // One launch range of one sweep: the later sweeps of a batch (k >= 1) visit only the range's live states when
-    // the handle holds a list for this mask (pi_prepare_mask) — the first one copies the terminal values.
+    pi::Comm* c = h->comm;
+    const bool overlap = p->overlapped();
     const bool live = pi::live_usable(h, term, p->s_begin, p->s_end);
-    auto sweep = [&](const float* src, float* dst, int64_t a, int64_t b, bool want, int k) -> int {
-        if (k >= 1 && live) {
-            int64_t first = 0, count = 0;
-            pi::live_span(h, a, b, &first, &count);
-            return pi::launch_eval_live(h, src, dst, policy, first, count, gamma, want, st);
-        }
-        return pi::launch_eval(h, src, dst, policy, term, a, b, gamma, want, st, k >= 1);
-    };
     auto batch = [&]() -> int {
         for (int k = 0; k < n_sweeps; ++k) {
             const float* src = (k & 1) ? Vb : Va;
             float* dst = (k & 1) ? Va : Vb;
             const bool want = k == n_sweeps - 1 && d_delta != nullptr;
-            if (overlap && p->row_exact && term == nullptr && p->push_ok) {
-                // fused exchange, everything on this stream: the swept-first kernel stores its rows into the peers'
-                // buffers itself, one-wave kernels hand-shake in front of it and behind it
-                pi::Comm* c = h->comm;
-                float* const* table = nullptr;
-                if (c->push_begin(p->push_peers, p->push_senders, dst, &table, st)) return 1;
-                if (pi::launch_eval_push(h, src, dst, policy, p->d_first, p->d_first_dest, table, (int)p->push_peers.size(),
-                                         p->n_first, gamma, want, st)) return 1;
+            // How the swept-first part reaches the peers: fused (everything on this stream: the swept-first kernel stores
+            // its states into the peers' buffers itself, one-wave kernels hand-shake in front of it and behind it), as an
+            // exchange on the second stream while the interior is swept, or — no overlap — as a plain exchange after.
+            const ShardSweep s = {src, dst, policy, term, gamma, want, k, live, fused_sweep(h, term, k, live), st};
+            float* const* table = nullptr;
+            if (s.fused && c->push_begin(p->push_peers, p->push_senders, dst, &table, st)) return 1;
+            if (sweep_first_part(h, s, table)) return 1;
+            if (s.fused) {
                 if (c->push_signal(st)) return 1;
-                if (pi::launch_eval_live(h, src, dst, policy, 0, p->n_inner, gamma, want, st, p->d_inner)) return 1;
-                if (k + 1 < n_sweeps ? c->push_wait_deferred(st) : c->push_wait(st)) return 1;     // the next sweep is fused too
-            } else if (overlap && k >= 1 && live && p->live_push_ok && p->live_list == h->d_live &&
-                       p->live_list_count == h->live_count) {
-                // the same fused exchange for the later sweeps of a batch on a grid with terminal states: the live
-                // states of the ranges peers wait for are swept by the push kernel, which delivers them (terminal
-                // states' values never change: every rank's buffers hold them since the batch's first sweep)
-                pi::Comm* c = h->comm;
-                float* const* table = nullptr;
-                if (c->push_begin(p->push_peers, p->push_senders, dst, &table, st)) return 1;
-                if (p->live_exact) {
-                    if (pi::launch_eval_push(h, src, dst, policy, p->d_first, p->d_first_dest, table, (int)p->push_peers.size(),
-                                             p->n_first, gamma, want, st)) return 1;
-                    if (c->push_signal(st)) return 1;
-                    if (pi::launch_eval_live(h, src, dst, policy, 0, p->n_inner, gamma, want, st, p->d_inner)) return 1;
-                } else {
-                    for (const auto& r : p->send_ranges) {
-                        int64_t first = 0, count = 0;
-                        pi::live_span(h, r.first, r.second, &first, &count);
-                        if (pi::launch_eval_push(h, src, dst, policy, h->d_live + first, p->d_live_dest + (first - p->live_dest_base),
-                                                 table, (int)p->push_peers.size(), count, gamma, want, st)) return 1;
-                    }
-                    if (c->push_signal(st)) return 1;
-                    for (const auto& r : p->interior)
-                        if (sweep(src, dst, r.first, r.second, want, k)) return 1;
-                }
-                if (k + 1 < n_sweeps ? c->push_wait_deferred(st) : c->push_wait(st)) return 1;     // k + 1 >= 1: fused too
             } else if (overlap) {
-                if (p->row_exact && term == nullptr) {
-                    if (pi::launch_eval_live(h, src, dst, policy, 0, p->n_first, gamma, want, st, p->d_first)) return 1;
-                } else {
-                    for (const auto& r : p->send_ranges)
-                        if (sweep(src, dst, r.first, r.second, want, k)) return 1;
-                }
                 PI_HIP(hipEventRecord(p->ev_ready, st));
                 PI_HIP(hipStreamWaitEvent(p->comm_stream, p->ev_ready, 0));
                 if (post_exchange(h, dst, p->comm_stream)) return 1;
                 PI_HIP(hipEventRecord(p->ev_done, p->comm_stream));
-                if (p->row_exact && term == nullptr) {
-                    if (pi::launch_eval_live(h, src, dst, policy, 0, p->n_inner, gamma, want, st, p->d_inner)) return 1;
-                } else {
-                    for (const auto& r : p->interior)
-                        if (sweep(src, dst, r.first, r.second, want, k)) return 1;
-                }
+            } else if (pi_exchange_V(h, dst, stream)) {
+                return 1;
+            }
+            if (sweep_interior_part(h, s)) return 1;
+            if (s.fused) {
+                // a fused sweep is followed by fused sweeps only: the next one's push_begin waits for this one's data
+                if (k + 1 < n_sweeps ? c->push_wait_deferred(st) : c->push_wait(st)) return 1;
+            } else if (overlap) {
                 PI_HIP(hipStreamWaitEvent(st, p->ev_done, 0));
-            } else {
-                if (sweep(src, dst, p->s_begin, p->s_end, want, k)) return 1;
-                if (pi_exchange_V(h, dst, stream)) return 1;
             }
         }
         if (d_delta) {
@@ -1053,11 +1053,10 @@ int pi_eval_sweeps_sharded(pi_handle* h, float* Va, float* Vb, const int32_t* po
         return 0;
     };
     if (batch() == 0) return 0;
-    // Failure half-way through the batch: leave a DEFINED state behind.  Drain both streams (a
-    // launch or an event may be pending on either), clear the residual slots a finished sweep may
-    // have filled, and retire the plan — the peers are at an unknown sweep, so the next sharded call
-    // must be preceded by a new communicator and a collective pi_exchange_plan (need_plan says how).  The error of the
-    // failing call is kept.
+    // Failure half-way through the batch: leave a DEFINED state behind.  Drain both streams (a launch or an event may be
+    // pending on either), clear the residual slots a finished sweep may have filled, and retire the plan — the peers are at
+    // an unknown sweep, so the next sharded call must be preceded by a new communicator and a collective pi_exchange_plan
+    // (need_plan says how).  The error of the failing call is kept.
     const std::string why = pi::last_error();
     h->comm->give_up();                                                      // in-process peers stop waiting at once
     if (p->comm_stream) (void)hipStreamSynchronize(p->comm_stream);

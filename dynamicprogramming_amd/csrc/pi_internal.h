@@ -92,7 +92,7 @@ struct DeviceGuard {
 struct Comm {
     int rank = 0, world = 1;
     virtual ~Comm() {}
-    virtual const char* kind() const = 0;
+    virtual int transport() const = 0;                    // PI_TRANSPORT_* (pi_comm_info)
     virtual int group_begin() = 0;
     virtual int send(const void* p, size_t bytes, int peer, hipStream_t st) = 0;
     virtual int recv(void* p, size_t bytes, int peer, hipStream_t st) = 0;

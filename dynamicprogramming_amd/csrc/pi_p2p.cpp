@@ -150,7 +150,7 @@ struct P2pComm : pi::Comm {
         if (module) (void)hipModuleUnload(module);
         if (page) (void)hipFree(page);
     }
-    const char* kind() const override { return "p2p"; }
+    int transport() const override { return PI_TRANSPORT_P2P; }
     int alive() const { return dead.empty() ? 0 : fail(dead); }
 
     uint32_t* flag(char* pg, size_t off, int slot) const { return reinterpret_cast<uint32_t*>(pg + off) + slot; }

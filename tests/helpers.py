@@ -78,6 +78,32 @@ def golden(name: str):
     return np.load(GOLDEN / f"{name}.npz")
 
 
+# ---- exchange plans pinned to a record (tests/golden/shard_plans.json, tests/golden/make_shard_plans_golden.py) ----
+PLAN_INFO_KEYS = ("mode", "recv_elems", "send_elems", "send_ranges", "interior_ranges")      # info[0..4] of pi_exchange_plan
+PLAN_SELECTORS = ("PLAN", "REACH_UNITS", "ROW_EXACT", "FUSED", "PAIR_EXACT", "FUSED_VALUES", "FIRST_ENTRIES",
+                  "INTERIOR_ENTRIES")
+
+
+def plan_record(eng, info: dict) -> dict:
+    """Everything a rank can say about its exchange plan, as JSON-able data: the five info[] values of
+    pi_exchange_plan, pi_plan_ranges and every plan selector of pi_comm_info."""
+    from dynamicprogramming_amd._native import CommInfo
+    return {"info": [info[k] for k in PLAN_INFO_KEYS], "ranges": [list(r) for r in eng.plan_ranges()],
+            "comm_info": {k: int(eng.comm_info(CommInfo[k])) for k in PLAN_SELECTORS}}
+
+
+def plan_key(transport: str, world: int, name: str, shape, env: dict) -> str:
+    """Name of a recorded case.  TEST_* variables steer the test's worker, not the library: they do not name a plan."""
+    knobs = ",".join(f"{k}={v}" for k, v in sorted(env.items()) if not k.startswith("TEST_"))
+    return f"{transport} world={world} {name} {'x'.join(str(g) for g in shape)} {knobs}"
+
+
+def golden_plans(key: str) -> list:
+    """The recorded plan of every rank of the case `key`."""
+    import json
+    return json.loads((GOLDEN / "shard_plans.json").read_text())["plans"][key]
+
+
 def oracle_for(name: str, libm: bool = False) -> oracle.OracleLib:
     return oracle.build(envs.ENVS[name]._D, envs.dynamics_source(name), libm=libm)
 

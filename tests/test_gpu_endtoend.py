@@ -1178,8 +1178,11 @@ def test_plain_bench_run_dumps_what_its_last_timed_step_computed(cuda_device, tm
     assert np.array_equal(P[idx], dump["policy"].astype(np.int32))
 
 
-@pytest.mark.parametrize("world,name,shape", [(8, "double_pendulum_swingup", (40, 12, 8, 6)), (4, "double_pendulum_swingup", (24, 9, 7, 5)),
-                                               (3, "pendulum", (60, 33))])
+ROW_EXACT_CASES = [(8, "double_pendulum_swingup", (40, 12, 8, 6)), (4, "double_pendulum_swingup", (24, 9, 7, 5)),
+                   (3, "pendulum", (60, 33))]
+
+
+@pytest.mark.parametrize("world,name,shape", ROW_EXACT_CASES)
 def test_row_exact_swept_first_lists(world, name, shape, cuda_device, monkeypatch):
     """Row-exact exchange plans (grids without terminal states, PI_MI355_ROW_EXACT): what is swept first is exactly the
     rows that travel — as a state list swept by the list kernel in one launch — and the interior is the rest of the
@@ -1212,6 +1215,7 @@ def test_row_exact_swept_first_lists(world, name, shape, cuda_device, monkeypatc
                     s = cls(H.env_bins_space(name, shape), cls.ACTIONS, envs.CudaPIConfig(**cfg_kw), device=cuda_device,
                             transport=T.NativeTransport.local(r, world, group))
                     eng, info, ranges = s._backend.engine, dict(s._comm.info), s._backend.engine.plan_ranges()
+                    plan = H.plan_record(eng, info)
                     a, b = s._s_begin, s._s_end
                     # parts of one sweep against the plain range sweep of the shard
                     dV, dP = V0.to(cuda_device), P0.to(cuda_device)
@@ -1226,7 +1230,7 @@ def test_row_exact_swept_first_lists(world, name, shape, cuda_device, monkeypatc
                     same = bool(torch.equal(whole, parts))
                     touched_first = int((first_only != 0).sum().item())
                     s.run()
-                    out[r] = dict(info=info, ranges=ranges, shard=(a, b), same=same, touched_first=touched_first,
+                    out[r] = dict(info=info, ranges=ranges, plan=plan, shard=(a, b), same=same, touched_first=touched_first,
                                   V=s.value_function, P=s.policy, sweeps=list(s.stats["sweeps_per_iter"]))
             except Exception as exc:  # noqa: BLE001
                 errors.append((r, repr(exc)))
@@ -1240,6 +1244,9 @@ def test_row_exact_swept_first_lists(world, name, shape, cuda_device, monkeypatc
         return out
 
     exact, coarse = run(True), run(False)
+    for got, row_exact in ((exact, "1"), (coarse, "0")):       # the plans are the recorded ones (tests/golden/shard_plans.json)
+        key = H.plan_key("local", world, name, shape, {"PI_MI355_EXCHANGE": "halo", "PI_MI355_ROW_EXACT": row_exact})
+        assert [o["plan"] for o in got] == H.golden_plans(key), key
     for r, (e, c) in enumerate(zip(exact, coarse)):
         assert e["info"]["mode"] == "halo" and e["info"]["row_exact"] and not c["info"]["row_exact"]
         a, b = e["shard"]

@@ -14,6 +14,7 @@ No reference counterpart: src/cuda_policy_iteration.py:300-336 is a single-devic
 """
 from __future__ import annotations
 
+import json
 import os
 import socket
 import sys
@@ -56,6 +57,11 @@ def _worker(rank: int, world: int, port: int, name: str, shape, cfg_kw: dict, ou
         info = dict(s._comm.info)
         row_exact, fused, live, pairs = (eng.comm_info(CommInfo.ROW_EXACT), eng.comm_info(CommInfo.FUSED),    # before run()
                                          eng.info(Info.LIVE_STATES), eng.comm_info(CommInfo.PAIR_EXACT))
+        plan = H.plan_record(eng, info)
+        if env.get("TEST_PLAN_ONLY") == "1":            # tests/golden/make_shard_plans_golden.py: the plan, not the run
+            (Path(out_dir) / f"rank{rank}_plan.json").write_text(json.dumps(plan))
+            dist.barrier()
+            return
         if env.get("TEST_POISON") == "1":
             # Everything this rank neither owns nor is DELIVERED becomes NaN: both Jacobi buffers outside its shard are
             # poisoned, then its peers deliver the starting values it can reach (one whole-row exchange).  From here on a
@@ -75,7 +81,7 @@ def _worker(rank: int, world: int, port: int, name: str, shape, cfg_kw: dict, ou
         np.savez(Path(out_dir) / f"rank{rank}.npz", V=s.value_function, policy=s.policy,
                  sweeps=np.asarray(s.stats["sweeps_per_iter"]), mode=np.asarray(info["mode"]),
                  recv=np.int64(info["recv_elems"]), row_exact=np.int64(row_exact), fused=np.int64(fused), live=np.int64(live), pairs=np.int64(pairs),
-                 send=np.int64(info["send_elems"]), order=np.asarray(eng.order))
+                 send=np.int64(info["send_elems"]), order=np.asarray(eng.order), plan=np.asarray(json.dumps(plan)))
         dist.barrier()
     finally:
         dist.destroy_process_group()
@@ -132,8 +138,11 @@ def test_p2p_sharded_run_is_bit_identical_to_single_rank(world, name, shape, mod
     single.run()
     env = {"PI_MI355_EXCHANGE": mode, **extra}
     mp.spawn(_worker, args=(world, _free_port(), name, shape, cfg_kw, str(tmp_path), env), nprocs=world, join=True)
+    recorded = H.golden_plans(H.plan_key("p2p", world, name, shape, env))
+    assert len(recorded) == world
     for r in range(world):
         got = np.load(tmp_path / f"rank{r}.npz")
+        assert json.loads(str(got["plan"])) == recorded[r], f"rank {r}: the exchange plan is not the recorded one"
         H.assert_bits_equal(got["V"], single.value_function, f"rank {r} V")
         assert np.array_equal(got["policy"], single.policy)
         assert got["sweeps"].tolist() == single.stats["sweeps_per_iter"]

@@ -1,4 +1,4 @@
-"""tools/logical_ranks.py ENV BINS WORLD [SWEEPS] — the sharded driver of libpi_mi355.so at FULL size
+"""tools/logical_ranks.py ENV BINS WORLD [SWEEPS [BATCH]] — the sharded driver of libpi_mi355.so at FULL size
 with WORLD logical ranks on ONE GPU (GPU box; one host thread, one stream and one full set of V buffers
 per rank; the in-process transport of csrc/pi_comm.cpp, same planner, kernels and stream ordering as the
 RCCL transport).  Everything printed is "one GPU, logical ranks": it shows what each rank of a real
@@ -11,11 +11,16 @@ For the config it prints one JSON line with
     every rank's shard of V and of the policy equals the single-rank result;
   * the measured single-GPU time split: each rank's swept-first launches and interior launches timed
     alone on the GPU (HIP events), next to the whole-grid sweep time — compute a rank has to finish
-    before its halo can leave vs compute that can hide the transfer.
+    before its halo can leave vs compute that can hide the transfer;
+  * with BATCH > 0, per rank "batch_ms": the wall time of five whole sharded batches of BATCH evaluation sweeps
+    (exchanges included), all ranks started together at a barrier, each until its own stream is idle; one
+    batch before them warms up.  The in-process transport waits for its peers on the host inside every
+    exchange, so this is what the host side of the sharded driver costs.
 """
 import json
 import sys
 import threading
+import time
 import uuid
 from pathlib import Path
 
@@ -29,6 +34,7 @@ from dynamicprogramming_amd._native import CommInfo, Info
 
 env, bins, world = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
 sweeps = int(sys.argv[4]) if len(sys.argv) > 4 else 3
+batch = int(sys.argv[5]) if len(sys.argv) > 5 else 0
 dev = torch.device("cuda:0")
 cls = envs.ENVS[env]
 cfg = envs.CudaPIConfig(**cls.CONFIG)
@@ -69,6 +75,7 @@ delta_ref = float(single._d_delta.item())
 
 group = f"logical-{uuid.uuid4().hex}"
 out, errors = [None] * world, []
+barrier = threading.Barrier(world)
 
 
 def rank_main(r):
@@ -87,13 +94,21 @@ def rank_main(r):
             same_V = bool(torch.equal(s.d_value_function[a:b], V_ref[a:b]))
             same_P = bool(torch.equal(s.d_policy[a:b], P_ref[a:b]))
             ok_scalars = int(s._d_changed.item()) == changed_ref and float(s._d_delta.item()) == delta_ref
+            batch_ms = []
+            for _ in range(6 if batch > 0 else 0):
+                barrier.wait(timeout=600)
+                t0 = time.perf_counter()
+                s._evaluation_sweeps(batch, gamma)
+                stream.synchronize()
+                batch_ms.append((time.perf_counter() - t0) * 1e3)
             out[r] = {"rank": r, "states": b - a, "mode": info["mode"], "reach_units": info["reach_units"],
                       "row_exact_plan": info.get("row_exact"),
                       "bytes_received_per_sweep": 4 * info["recv_elems"], "bytes_sent_per_sweep": 4 * info["send_elems"],
                       "ranges": ranges, "bit_identical_V": same_V, "bit_identical_policy": same_P,
-                      "reduced_scalars_equal": ok_scalars, "_solver": s}
+                      "reduced_scalars_equal": ok_scalars, "batch_ms": batch_ms[1:], "_solver": s}
     except Exception as exc:  # noqa: BLE001
         errors.append((r, repr(exc)))
+        barrier.abort()
 
 
 threads = [threading.Thread(target=rank_main, args=(r,)) for r in range(world)]
@@ -148,7 +163,7 @@ for o in out:
     s._backend.close()
 
 print(json.dumps({"env": env, "bins": bins, "world": world, "states": n, "label": "one GPU, logical ranks",
-                  "whole_grid_eval_ms_single_rank": whole_ms, "sweeps_checked": sweeps,
+                  "whole_grid_eval_ms_single_rank": whole_ms, "sweeps_checked": sweeps, "batch_sweeps": batch,
                   "all_bit_identical": all(o["bit_identical_V"] and o["bit_identical_policy"] and o["reduced_scalars_equal"]
                                            for o in out),
                   "ranks": out}), flush=True)
