@@ -10,14 +10,15 @@ from __future__ import annotations
 
 import ctypes
 import enum
-import os
 from pathlib import Path
 
 import numpy as np
 
+from . import _knobs
+
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "libpi_mi355.so"
-KERNEL_CACHE = Path(os.environ.get("PI_MI355_KERNEL_CACHE", str(_PKG / "_kcache")))
+KERNEL_CACHE = Path(_knobs.read("KERNEL_CACHE"))
 
 _f32p = ctypes.POINTER(ctypes.c_float)
 _i32p = ctypes.POINTER(ctypes.c_int32)

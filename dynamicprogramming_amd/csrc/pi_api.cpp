@@ -5,7 +5,6 @@
 #include "pi_internal.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace pi {
 
@@ -16,14 +15,6 @@ int fail(const std::string& msg) {
     return 1;
 }
 const std::string& last_error() { return g_error; }
-
-int env_int(const char* name, int dflt, int lo, int hi) {
-    if (const char* e = std::getenv(name)) {
-        const int v = std::atoi(e);
-        if (v >= lo && v <= hi) return v;
-    }
-    return dflt;
-}
 
 // The strip period the sweeps of this handle use (PiSched): strip_mode > 0 as given, 0 none, -1 the library's choice,
 // from measurements on MI355X (profiles/r06/strip_schedule.txt):
@@ -145,12 +136,8 @@ void choose_dispatch(pi_handle* h) {
     // smaller grids keep 256-thread workgroups, two chunks each once there are enough chunks
     // (big 6-D grids: four and three, below).
     const bool big = D <= 4 && n >= (int64_t(1) << 24);
-    auto block_knob = [](const char* name, int dflt) {
-        const int v = env_int(name, dflt, 256, 1024);
-        return (v % 64 == 0) ? v : dflt;          // any whole number of waves, 256..1024 threads
-    };
-    h->block_eval = block_knob("PI_MI355_EVAL_BLOCK", big ? 1024 : 256);
-    h->block_improve = block_knob("PI_MI355_IMPROVE_BLOCK", big ? 512 : 256);
+    h->block_eval = knob_int(Knob::EVAL_BLOCK, big ? 1024 : 256);          // any whole number of waves, 256..1024 threads
+    h->block_improve = knob_int(Knob::IMPROVE_BLOCK, big ? 512 : 256);
     // 6-D grids of >= 2^24 states: four chunks per evaluation workgroup and three per improvement workgroup
     // (profiles/r03/block_cpw_sweep_6d.txt: 4.19 -> 4.11 ms and 9.05 -> 8.52 ms at 25^6).  Re-run under the strip schedule in
     // round 6 (profiles/r06/cpw_sweep_6d.txt): 6 or 8 evaluation chunks measure 1-2 % faster on one box (2.726 / 2.702 /
@@ -158,20 +145,16 @@ void choose_dispatch(pi_handle* h) {
     // L2 hits — the swing-up sweep fetches 18.2 GB past L2 instead of 11.7 GB for the same 4.52 ms under the profiler
     // (cpw_sweep_6d.txt, second table) — so four stay
     const bool big6 = D == 6 && n >= (int64_t(1) << 24);
-    h->cpw_eval = env_int("PI_MI355_EVAL_CPW", big6 ? 4 : n >= (int64_t(1) << 20) ? 2 : 1, 1, 64);
-    h->cpw_improve = env_int("PI_MI355_IMPROVE_CPW", big6 ? 3 : 1, 1, 64);
-    h->use_graphs = env_int("PI_MI355_GRAPHS", 1, 0, 1) != 0;
-    if (const char* e = std::getenv("PI_MI355_STRIP")) {          // states per period | 0 (slab schedule) | auto
-        char* end = nullptr;
-        const long long v = std::strtoll(e, &end, 10);
-        h->strip_mode = (end != e && *end == 0 && v >= 0 && v <= n) ? v : -1;
-    }
-    h->debug_bounds = env_int("PI_MI355_DEBUG", 0, 0, 1) != 0;
+    h->cpw_eval = knob_int(Knob::EVAL_CPW, big6 ? 4 : n >= (int64_t(1) << 20) ? 2 : 1);
+    h->cpw_improve = knob_int(Knob::IMPROVE_CPW, big6 ? 3 : 1);
+    h->use_graphs = knob_int(Knob::GRAPHS) != 0;
+    h->strip_mode = knob_count(Knob::STRIP, n);                   // states per period | 0 (slab schedule) | -1: auto
+    h->debug_bounds = knob_int(Knob::DEBUG) != 0;
     // Small grids: the whole value table in LDS, one 1024-thread workgroup runs a batch of sweeps
     // (pi_eval_resident_kernel).  The limits keep table + per-state registers inside one CU.
     const int64_t resident_max = D == 2 ? 12288 : D == 4 ? 4096 : 1024;
     h->resident_block = D == 2 ? 1024 : 512;
-    h->resident_k = (n <= resident_max && env_int("PI_MI355_RESIDENT", 1, 0, 1))
+    h->resident_k = (n <= resident_max && knob_int(Knob::RESIDENT))
                         ? (int)((n + h->resident_block - 1) / h->resident_block) : 0;
     // Launch-bound grids beyond that (BASELINE config C2, pendulum 200 x 200): the dataflow kernel, one launch per policy
     // evaluation across ceil(n / 256) workgroups (pi_eval_flow_kernel).  Per sweep it moves 2^D granules of 8 bytes per
@@ -180,13 +163,12 @@ void choose_dispatch(pi_handle* h) {
     // XCD's L2, the whole run in one launch), with the dataflow kernel behind it — and so do the bigger ones of the grids
     // one CU holds: beyond ~4 000 states 32 CUs are faster than one (pendulum 80 x 80: 0.9 against 1.3 us per sweep,
     // 110 x 110: 1.2 against 2.9), the LDS-resident kernel stays their fallback and serves their sweep batches.
-    const bool one_launch = env_int("PI_MI355_RESIDENT", 1, 0, 1) != 0 && env_int("PI_MI355_FLOW", 1, 0, 1) != 0;
-    const bool xcd_wanted = one_launch && D == 2 && n <= (int64_t)env_int("PI_MI355_XCD_MAX", 1 << 16, 1 << 12, 1 << 17) && env_int("PI_MI355_XCD", 1, 0, 1) != 0;
-    const int64_t flow_min = xcd_wanted ? std::min<int64_t>(resident_max, env_int("PI_MI355_XCD_MIN", 4096, 1024, 12288)) : resident_max;
+    const bool one_launch = knob_int(Knob::RESIDENT) != 0;
+    const bool xcd_wanted = one_launch && D == 2 && n <= (int64_t(1) << 16) && knob_int(Knob::XCD) != 0;
+    const int64_t flow_min = xcd_wanted ? std::min<int64_t>(resident_max, 4096) : resident_max;
     const int64_t flow_max = D <= 4 ? (int64_t(1) << 17) : 0;
     h->flow = one_launch && n > flow_min && n <= flow_max;    // PI_MI355_RESIDENT=0 switches all one-launch kernels off
     h->xcd = h->flow && xcd_wanted;
-    h->xcd_ring = env_int("PI_MI355_XCD_RING", 64, 4, 1024);
     h->xcd_states = (int)(((n + 31) / 32 + 31) / 32 * 32);  // states per workgroup: n over 32 CUs, whole 128-byte lines
 }
 
@@ -312,7 +294,7 @@ pi_handle* pi_create(int device, int D, const int32_t* grid_shape, const float* 
         h->rcp.push_back(1.0f / span);
         h->fastdiv.push_back(pi::validate_fast_division(span) ? 1 : 0);
     }
-    if (std::getenv("PI_MI355_IEEE_DIV")) std::fill(h->fastdiv.begin(), h->fastdiv.end(), 0);
+    if (pi::knob_flag(pi::Knob::IEEE_DIV)) std::fill(h->fastdiv.begin(), h->fastdiv.end(), 0);
     h->tab.insert(h->tab.end(), actions, actions + n_actions);
     for (int d = 0; d < D; ++d) h->tab.insert(h->tab.end(), bins[d], bins[d] + grid_shape[d]);
     if (h->tab.size() * sizeof(float) > 60 * 1024) {

@@ -25,7 +25,6 @@
 #include <array>
 #include <chrono>
 #include <condition_variable>
-#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <map>
@@ -95,18 +94,6 @@ void release_comm(pi_handle* h) {
     drop_p2p_pending(h);
 }
 
-// How long a rank waits for a peer before it declares the exchange dead (seconds).  The RCCL
-// transport has its own watchdog-free wait on the GPU; what is bounded here are the HOST waits of the
-// in-process transport and the host-side polls for an asynchronous RCCL error.
-double comm_timeout_seconds() {
-    if (const char* e = std::getenv("PI_MI355_COMM_TIMEOUT")) {
-        const double v = std::atof(e);
-        if (v > 0.0) return v;
-    }
-    return 120.0;
-}
-
-
 }  // namespace pi
 
 namespace {
@@ -118,7 +105,7 @@ namespace {
             return fail(std::string(#expr) + ": " + ncclGetErrorString(r_));               \
     } while (0)
 
-using pi::comm_timeout_seconds;
+using pi::Knob;
 
 // ---- RCCL ------------------------------------------------------------------------------
 // Failure handling ("RCCL error -> abort with message"): every RCCL call goes
@@ -239,7 +226,7 @@ struct LocalComm : pi::Comm {
     // an error on all members after PI_MI355_COMM_TIMEOUT seconds instead of a hang.
     template <typename Pred>
     int wait_for(std::unique_lock<std::mutex>& lk, Pred ready, const char* what) {
-        const auto limit = std::chrono::duration<double>(comm_timeout_seconds());
+        const auto limit = std::chrono::duration<double>(pi::knob_seconds(Knob::COMM_TIMEOUT));
         if (!grp->cv.wait_for(lk, limit, [&] { return grp->failed || ready(); }) || grp->failed) {
             grp->failed = true;
             grp->cv.notify_all();
@@ -391,8 +378,7 @@ int post_exchange(pi_handle* h, float* full, hipStream_t st) {
 // the state is still swept, its value is just not delivered — so that a test can show its poisoning check FAILS when a
 // delivery is missing (tests/test_gpu_p2p.py).  Off unless the variable is set.
 void drop_deliveries_for_tests(std::vector<uint8_t>& dest) {
-    const char* e = std::getenv("PI_MI355_DEBUG_DROP_DELIVERY");
-    const int k = e ? std::atoi(e) : 0;
+    const int k = pi::knob_int(Knob::DEBUG_DROP_DELIVERY);
     if (k > 0)
         for (size_t i = (size_t)k - 1; i < dest.size(); i += (size_t)k) dest[i] = 0;
 }
@@ -433,9 +419,7 @@ using SweptFirst = pi::ShardPlan::SweptFirst;
 // Units the reach is measured in: rows (i0, i1) where the grid has them (2-4x fewer values to
 // exchange than whole planes of dimension 0), planes otherwise; PI_MI355_REACH_DEPTH overrides.
 int reach_depth(pi_handle* h) {
-    int depth = pi_reach_depth_max(h);
-    if (const char* e = std::getenv("PI_MI355_REACH_DEPTH")) depth = std::max(1, std::min(depth, std::atoi(e)));
-    return depth;
+    return pi::knob_clamped(Knob::REACH_DEPTH, pi_reach_depth_max(h));
 }
 // Reach bitmap of this shard -> all ranks -> who sends what to whom -> halo or all-gather (`mode`; PI_PLAN_NONE: halo
 // unless a rank would receive > 60 % of an all-gather).  A halo plan keeps the segments that involve this rank.  Collective.
@@ -505,8 +489,7 @@ int agree_on_fused(pi_handle* h, hipStream_t st, bool* fused) {
     pi::Comm* c = h->comm;
     *fused = false;
     if (!c->can_push()) return 0;
-    const char* env = std::getenv("PI_MI355_P2P_FUSED");
-    const uint32_t mine = !(env && std::atoi(env) == 0) && pi::ensure_push_module(h) == 0 ? 1u : 0u;
+    const uint32_t mine = pi::knob_flag(Knob::P2P_FUSED) && pi::ensure_push_module(h) == 0 ? 1u : 0u;
     uint32_t* d_votes = nullptr;
     PI_HIP(hipMalloc((void**)&d_votes, sizeof(uint32_t)));
     uint32_t all = 0;
@@ -535,9 +518,8 @@ struct PairReach {
 // Measured where it can be and PI_MI355_PAIR_REACH is not 0.  Collective: every rank measures or none (same grid, same
 // order, same transport, same environment).
 int gather_pair_reach(pi_handle* h, const uint8_t* term, const pi::ShardPlan& plan, hipStream_t st, PairReach* pr) {
-    const char* e = std::getenv("PI_MI355_PAIR_REACH");
     const int v = h->D >= 2 ? h->mem_of_user[1] : 0;
-    if (!pi::pairs_possible(h) || v == 1 || (e && std::atoi(e) == 0)) return 0;
+    if (!pi::pairs_possible(h) || v == 1 || !pi::knob_flag(Knob::PAIR_REACH)) return 0;
     pr->st0 = h->n_states / h->shape[0];
     pr->gv = h->shape[v];
     for (int d = v + 1; d < h->D; ++d) pr->stv *= h->shape[d];
@@ -931,8 +913,7 @@ int pi_exchange_plan(pi_handle* h, const uint8_t* term, int64_t per, int mode, i
         //   state-exact lists   no terminal states, pair reach measured, this shard sends something; always fused
         //   row-exact lists     no terminal states, where they pay or PI_MI355_ROW_EXACT = 1 (= 0: neither kind of list)
         //   live-state masks    the shard keeps a live-state list for this mask; fused exchange only
-        int want = -1;
-        if (const char* e = std::getenv("PI_MI355_ROW_EXACT")) want = std::atoi(e) != 0 ? 1 : 0;
+        const int want = pi::knob_flag(Knob::ROW_EXACT);
         const bool lists_possible = term == nullptr && want != 0;
         if (lists_possible && plan->pair_exact && !cuts.empty() && plan_state_lists(h, pairs, st, plan.get())) return 1;
         if (lists_possible && plan->swept_first == SweptFirst::Ranges && plan_row_lists(h, cuts, want, fused, st, plan.get())) return 1;

@@ -1,4 +1,5 @@
 // pi_internal.h — shared between the host sources of libpi_mi355.so.  Not part of the C ABI.  What lives where:
+//   pi_knobs.cpp      the PI_MI355_* environment knobs: one table, the only readers of the environment (pi_knobs.h)
 //   pi_api.cpp        error state, pi_create / pi_destroy and the dispatch policy, the sweep launchers and the graph cache,
 //                     the sweep entry points, pi_set_option, pi_info
 //   pi_probe.cpp      the reach and probe entry points
@@ -9,6 +10,7 @@
 //   pi_infer.cpp, pi_rollout.cpp   the inference handle and its rollouts;  pi_hybrid.cpp  rollouts that switch between two handles
 #pragma once
 
+#include "pi_knobs.h"
 #include "pi_mi355.h"
 
 #include <hip/hip_runtime.h>
@@ -34,6 +36,7 @@ constexpr int kProbeBlock = 256; // threads per workgroup of the probe kernels' 
 constexpr int kXcds = 8;         // PI_NXCD
 constexpr int kSlots = 256;      // PI_NSLOT
 constexpr int kXcdCtlWords = 128 + 256;   // control block of the XCD-local kernel: PI_XCD_CTL_FLAGS + 2 banks x 64 flag granules
+constexpr int kXcdRing = 64;              // granule versions of V the XCD-local kernel keeps (PI_XCD_RING)
 constexpr const char* kArch = "gfx950";
 
 // Where a kernel launch goes: onto a stream, or into a graph under construction as the node behind *prev.
@@ -62,7 +65,6 @@ hipError_t launch(hipFunction_t f, Grid2 grid, unsigned block, LaunchTo to, A...
     return e;
 }
 
-int env_int(const char* name, int dflt, int lo, int hi);   // integer knob from the environment, dflt when unset or outside [lo, hi]
 // PI_*_INIT lists of the generated translation units: "{a,b,c}", floats as hexadecimal literals (%af)
 std::string hex_float(float v);
 template <typename T, typename F>
@@ -193,16 +195,14 @@ struct pi_handle {
     // XCD-local evaluation / whole run (pi_xcd_kernel, csrc/pi_onelaunch_kernels.hip): one 1 024-thread workgroup per CU of
     // ONE XCD, the iterates as tagged granules through that XCD's L2, flag granules as the barrier every 32nd sweep.
     // xcd: this grid qualifies; xcd_off: switched off after repeated failures (pi_policy_evaluation counts its own; a failed
-    // whole run is reported back through PI_OPTION_XCD_RUN_FAILED).  d_xcd: ring of xcd_ring versions | scratch policy | control
+    // whole run is reported back through PI_OPTION_XCD_RUN_FAILED).  d_xcd: ring of kXcdRing versions | scratch policy | control
     // words (owned).  Counters for PI_INFO_XCD_ENABLED - PI_INFO_WHOLE_RUNS.
     bool xcd = false, xcd_off = false;
     int xcd_states = 1024;                               // states per workgroup (PI_XCD_S)
-    int xcd_ring = 64;                                   // granule versions of V the kernel keeps (PI_XCD_RING)
     hipFunction_t f_xcd = nullptr, f_xcd_finish = nullptr;
     void* d_xcd = nullptr;
     size_t xcd_bytes = 0;
     int64_t xcd_used = 0, xcd_failed = 0, whole_runs = 0;
-    unsigned int* xcd_ctl = nullptr;                     // control words of the last launch (inside d_xcd)
     std::vector<pi::GraphEntry> graphs;
     uint64_t graph_clock = 0;
     // pi_prepare_mask: the non-terminal states of the mask at live_term, ascending (device, owned); in use only
@@ -299,7 +299,6 @@ int reach_pairs(pi_handle* h, const uint8_t* term, int64_t s_begin, int64_t s_en
 void drop_eval_list(pi_handle* h);     // the policy may have changed: forget the per-evaluation list
 void release_comm(pi_handle* h);      // pi_comm.cpp: tears down the transport and the exchange plan
 void drop_p2p_pending(pi_handle* h);  // pi_p2p.cpp
-double comm_timeout_seconds();        // PI_MI355_COMM_TIMEOUT (default 120): how long a rank waits for a peer
 void drop_graphs(pi_handle* h);       // the cached graphs hold launch geometry and kernel handles: forget them
 void resolve_strip(pi_handle* h);     // strip_mode -> strip_states (the library's choice needs the final memory order)
 bool validate_fast_division(float span);   // pi_compile.cpp: is the reciprocal division exact for this divisor?

@@ -6,7 +6,8 @@
 
 #include <algorithm>
 
-using pi::env_int;
+using pi::Knob;
+using pi::knob_int;
 using pi::fail;
 
 namespace pi {
@@ -101,7 +102,7 @@ int pi_prepare_mask_range(pi_handle* h, const uint8_t* d_term, int64_t s_begin, 
     // not the grid — 1 / world of the device list, of the host index and of the host pass (at 25^6 on 8 ranks:
     // 80 MB instead of 630 MB of list per rank).
     const int64_t n = s_end - s_begin;
-    if (h->n_states < env_int("PI_MI355_LIVE_MIN", 1 << 20, 1, 1 << 30) || !env_int("PI_MI355_LIVE", 1, 0, 1)) return 0;
+    if (h->n_states < knob_int(Knob::LIVE_MIN) || !knob_int(Knob::LIVE)) return 0;
     // Built on the device (pi_mask_list_kernel: bitmap + per-block counts, scan, ordered write); the host keeps the
     // bitmap only — 1 bit per state, 30 MB at 25^6 — and derives the live states in front of every 64-state block from it,
     // which is what positions of sub-ranges (live_span) and the sharded planner (live_states) need.
@@ -172,7 +173,7 @@ int pi_eval_begin(pi_handle* h, const int32_t* policy, const uint8_t* term, void
     if (pi::check_ready(h)) return 1;
     if (!policy) return fail("null device pointer");
     pi::drop_eval_list(h);
-    if (!pi::live_usable(h, term, 0, h->n_states) || !env_int("PI_MI355_EVAL_LIST", 1, 0, 1)) return 0;   // nothing to shorten
+    if (!pi::live_usable(h, term, 0, h->n_states) || !knob_int(Knob::EVAL_LIST)) return 0;   // nothing to shorten
     pi::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
     const long long nblocks = (h->live_count + pi::kProbeBlock - 1) / pi::kProbeBlock;

@@ -5,8 +5,6 @@
 #include "pi_internal.h"
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 
 using pi::check_ready;
 using pi::fail;
@@ -33,16 +31,13 @@ int scratch_block(void** block, size_t* have, size_t bytes, hipStream_t st) {
     return 0;
 }
 
-// How long a wave of these kernels waits for another: `name` in seconds (dflt_s when unset or not positive), in ticks
-// of wall_clock64 (100 MHz)
-unsigned long long timeout_ticks(const char* name, double dflt_s) {
-    const char* e = std::getenv(name);
-    const double s = e && std::atof(e) > 0.0 ? std::atof(e) : dflt_s;
-    return std::max<unsigned long long>((unsigned long long)(s * 1e8), 1ull);
+// How long a wave of these kernels waits for another: the knob's seconds in ticks of wall_clock64 (100 MHz)
+unsigned long long timeout_ticks(pi::Knob k) {
+    return std::max<unsigned long long>((unsigned long long)(pi::knob_seconds(k) * 1e8), 1ull);
 }
 
 // pi_xcd_kernel + pi_xcd_finish_kernel on `st`: one policy evaluation (max_pi_iter == 0) or the whole run.  Device
-// block (owned by the handle): ring of xcd_ring (PI_XCD_RING, 64) granule versions of V (whole 128-byte lines each) |
+// block (owned by the handle): ring of kXcdRing (PI_XCD_RING) granule versions of V (whole 128-byte lines each) |
 // scratch policy | kXcdCtlWords control words (tickets, status, result, two banks of 64 flag granules: the kernel's
 // PI_XCD_CTL_WORDS, checked against this constant by a static_assert in the generated unit).
 int launch_xcd(pi_handle* h, float* V, int32_t* policy, const uint8_t* term, float gamma, double theta, int max_sweeps,
@@ -50,34 +45,20 @@ int launch_xcd(pi_handle* h, float* V, int32_t* policy, const uint8_t* term, flo
                hipStream_t st) {
     const size_t n = (size_t)h->n_states;
     const unsigned wgs = (unsigned)((h->n_states + h->xcd_states - 1) / h->xcd_states);
-    const size_t ring_bytes = (size_t)h->xcd_ring * ((n + 15) & ~size_t(15)) * sizeof(unsigned long long);   // PI_XCD_RING versions
+    const size_t ring_bytes = (size_t)pi::kXcdRing * ((n + 15) & ~size_t(15)) * sizeof(unsigned long long);   // PI_XCD_RING versions
     const size_t pol_bytes = ((n * sizeof(int32_t)) + 255) & ~size_t(255);
     if (scratch_block(&h->d_xcd, &h->xcd_bytes, ring_bytes + pol_bytes + (size_t)kXcdCtlWords * sizeof(unsigned int), st)) return 1;
     unsigned long long* ring = (unsigned long long*)h->d_xcd;
     int32_t* pol_out = (int32_t*)((char*)h->d_xcd + ring_bytes);
     unsigned int* ctl = (unsigned int*)((char*)h->d_xcd + ring_bytes + pol_bytes);
-    h->xcd_ctl = ctl;
     // placement is checked, not assumed: a quarter of a second is ample for a sweep and short for a wrong guess
-    const unsigned long long ticks = timeout_ticks("PI_MI355_XCD_TIMEOUT", 0.25);
+    const unsigned long long ticks = timeout_ticks(pi::Knob::XCD_TIMEOUT);
     const unsigned grid = (unsigned)kXcds * (wgs + std::max(wgs / 4, 2u));        // spare workgroups: the first `wgs` on XCD 0 take part
     PI_HIP(launch(h->f_xcd, {grid, 1}, 1024, st, (const float*)V, (const int32_t*)policy, term, (const float*)h->d_tab, gamma,
                   max_sweeps, theta, check_interval, max_pi_iter, d_residual_log, d_iter_log, ring, pol_out, ctl, ticks));
     const int whole_run = max_pi_iter > 0 ? 1 : 0;
     PI_HIP(launch(h->f_xcd_finish, {(unsigned)((n + 255) / 256), 1}, 256, st, V, policy, (const unsigned long long*)ring,
                   (const int32_t*)pol_out, (const unsigned int*)ctl, whole_run, d_out, d_delta));
-    return 0;
-}
-
-// PI_MI355_XCD_TRACE: what the last launch left in its control words (synchronous; diagnostics only)
-int xcd_trace(pi_handle* h, int done) {
-    if (!std::getenv("PI_MI355_XCD_TRACE")) return 0;
-    unsigned int w[96];
-    PI_HIP(hipMemcpy(w, h->xcd_ctl, sizeof w, hipMemcpyDeviceToHost));
-    std::fprintf(stderr, "[pi] xcd launch: result %d tickets %u status %u sweeps %u rounds %u stable %u\n", done, w[0], w[64], w[80], w[82],
-                 w[83]);
-    if (std::getenv("PI_MI355_XCD_TIMING"))
-        std::fprintf(stderr, "[pi] xcd cycles per sweep (gather | backup + store | barrier share | polls x 1000): first workgroup %u %u %u "
-                     "%u, last %u %u %u %u\n", w[8], w[9], w[10], w[11], w[16], w[17], w[18], w[19]);
     return 0;
 }
 
@@ -108,7 +89,6 @@ int pi_policy_evaluation(pi_handle* h, float* V, const int32_t* policy, const ui
         PI_HIP(hipMemcpyAsync(&done, d_sweeps, sizeof done, hipMemcpyDeviceToHost, st));
         PI_HIP(hipStreamSynchronize(st));
         ++h->xcd_used;
-        if (xcd_trace(h, done)) return 1;
         if (done >= 0) return 0;
         if (++h->xcd_failed >= 2) h->xcd_off = true;
     }
@@ -123,7 +103,7 @@ int pi_policy_evaluation(pi_handle* h, float* V, const int32_t* policy, const ui
         unsigned long long* ring = (unsigned long long*)h->d_flow;
         unsigned int* progress = (unsigned int*)((char*)h->d_flow + ring_bytes);
         unsigned int* checks = progress + progress_words;
-        const unsigned long long ticks = timeout_ticks("PI_MI355_FLOW_TIMEOUT", 2.0);
+        const unsigned long long ticks = timeout_ticks(pi::Knob::FLOW_TIMEOUT);
         PI_HIP(launch(h->f_flow, {wgs, 1}, h->flow_block, st, V, policy, term, tab, gamma, max_sweeps, d_delta, theta,
                       check_interval, d_sweeps, d_residual_log, ring, progress, checks, ticks));
         // the finish kernel is the only writer of V: the last version out of the ring when no wave gave up, nothing otherwise
@@ -158,12 +138,6 @@ int pi_policy_iteration(pi_handle* h, float* V, int32_t* policy, const uint8_t* 
                    d_iter_log, st))
         return 1;
     ++h->whole_runs;
-    if (std::getenv("PI_MI355_XCD_TRACE")) {
-        int32_t done = 0;
-        PI_HIP(hipMemcpyAsync(&done, d_result, sizeof done, hipMemcpyDeviceToHost, st));
-        PI_HIP(hipStreamSynchronize(st));
-        return xcd_trace(h, done);
-    }
     return 0;
 }
 

@@ -635,9 +635,6 @@ pi_eval_flow_kernel(float* __restrict__ Va, const int* __restrict__ policy, cons
 #endif
 #if PI_XCD
 #define PI_XCD_BLOCK 1024
-#ifndef PI_XCD_TIMING
-#define PI_XCD_TIMING 0
-#endif
 #ifndef PI_XCD_RING
 #define PI_XCD_RING 64
 #endif
@@ -848,12 +845,6 @@ pi_xcd_kernel(const float* __restrict__ Va, const int* __restrict__ policy, cons
     unsigned int rounds = 0u, stable = 0u;
     float residual = 0.0f;
     bool dead = false;                                     // wave-uniform inside a gather, workgroup-uniform behind a barrier
-#if PI_XCD_TIMING
-    unsigned long long tacc[5] = {0ull, 0ull, 0ull, 0ull, 0ull}, tp = __builtin_readcyclecounter();
-#define PI_XCD_STAMP(k) do { const unsigned long long tn = __builtin_readcyclecounter(); tacc[k] += tn - tp; tp = tn; } while (0)
-#else
-#define PI_XCD_STAMP(k)
-#endif
     const int n_rounds = max_pi_iter > 0 ? max_pi_iter : 1;
     for (int it = 0; it < n_rounds && !dead; ++it) {
         // ---- under the current policy, once per state: 0 = no state, 1 = keeps its value, 2 = done successor (no
@@ -903,7 +894,6 @@ pi_xcd_kernel(const float* __restrict__ Va, const int* __restrict__ policy, cons
                     break;
                 }
             }
-            PI_XCD_STAMP(0);
             PiGranule* dst = ring + (size_t)(g % PI_XCD_RING) * PI_XCD_NPAD;
             float dmax = 0.0f;
 #pragma unroll
@@ -921,7 +911,6 @@ pi_xcd_kernel(const float* __restrict__ Va, const int* __restrict__ policy, cons
             }
             ++g;
             sweeps = j + 1;
-            PI_XCD_STAMP(1);
             if (!sync) continue;
             if (look) {
                 const float wmax = pi_wave_max(dmax);
@@ -934,7 +923,6 @@ pi_xcd_kernel(const float* __restrict__ Va, const int* __restrict__ policy, cons
                 dead = true;
                 break;
             }
-            PI_XCD_STAMP(2);
             if (look) {
                 residual = __uint_as_float(bits);
                 if (max_pi_iter == 0 && wg == 0u && tid == 0u) residual_log[slot] = residual;
@@ -1011,12 +999,6 @@ pi_xcd_kernel(const float* __restrict__ Va, const int* __restrict__ policy, cons
         for (int k = 0; k < PI_XCD_K; ++k)
             if (role[k] != 0u) pol_out[s0 + (unsigned int)k * PI_XCD_BLOCK] = act[k];
     }
-#if PI_XCD_TIMING
-    if ((wg == 0u || wg == W - 1u) && tid == 0u) {
-        for (int k = 0; k < 3; ++k) ctl[8 + (wg == 0u ? 0 : 8) + k] = (unsigned int)(tacc[k] / (unsigned long long)g);
-        ctl[8 + (wg == 0u ? 0 : 8) + 3] = (unsigned int)((unsigned long long)polls * 1000ull / (unsigned long long)g);
-    }
-#endif
     if (wg == 0u && tid == 0u) {
         ctl[PI_XCD_CTL_DONE] = g;
         ctl[PI_XCD_CTL_DONE + 1] = __float_as_uint(residual);

@@ -500,7 +500,7 @@ int pi_comm_init_p2p(pi_handle* h, int rank, int world, const void* descs, const
     c->device = h->device;
     c->page = pend->page;
     pend->page = nullptr;
-    c->ticks = (unsigned long long)(pi::comm_timeout_seconds() * 1.0e8);        // wall_clock64: 100 MHz
+    c->ticks = (unsigned long long)(pi::knob_seconds(pi::Knob::COMM_TIMEOUT) * 1.0e8);        // wall_clock64: 100 MHz
     c->sent_n.assign((size_t)world, 0u);
     c->recv_n.assign((size_t)world, 0u);
     c->mine.push_back({c->page + kOffScratch, kScratchBytes});

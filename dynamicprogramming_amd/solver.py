@@ -32,7 +32,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _native
+from . import _knobs, _native
 from ._native import Info, Option, XcdFailure
 
 try:  # the reference logs through loguru; use it when present, stdlib logging otherwise
@@ -154,7 +154,7 @@ class HipSweepBackend:
         (Info.WHOLE_RUN_AVAILABLE: grids one CU's LDS holds, and 2-D grids of up to 2^16 states beyond those);
         PI_MI355_WHOLE_RUN=0 keeps the round-by-round loop."""
         return (self.resident and self.engine.info(Info.WHOLE_RUN_AVAILABLE) > 0
-                and os.environ.get("PI_MI355_WHOLE_RUN", "1") != "0")
+                and _knobs.read("WHOLE_RUN"))
 
     def policy_iteration(self, V, policy, term, gamma, theta, max_eval_sweeps, check_interval, max_pi_iter, retried=False):
         """The whole run on the device (pi_policy_iteration).  Returns (rounds done, stable, [(sweeps, residual,
@@ -313,12 +313,11 @@ class _CudaPolicyIterationBase(abc.ABC):
     def _shards_over_p2p(self) -> bool:
         """Whether the multi-rank transport of this solver will be the peer-to-peer one (decided as _init_sharding
         decides it): the only one that can deliver a halo that is not made of contiguous rows."""
-        import os
         comm = self._transport_arg
         if comm is not None and comm is not False:
             from . import transport as T
             return isinstance(comm, T.P2pTransport)
-        return os.environ.get("PI_MI355_TRANSPORT", "rccl").lower() == "p2p" and os.environ.get("PI_MI355_P2P_FUSED", "1") != "0"
+        return _knobs.read("TRANSPORT") == "p2p" and _knobs.read("P2P_FUSED")
 
     def _choose_memory_order(self):
         """The class's MEMORY_ORDER on big single-rank grids; the env's own order otherwise.  Sharded solvers keep the
@@ -333,8 +332,7 @@ class _CudaPolicyIterationBase(abc.ABC):
         candidate orders derived from the plugin's own dynamics, each timed on the device; the decision is cached beside
         the code objects) instead of running in the env's order; PI_MI355_ORDER=user is the opt-out, and so is
         MEMORY_ORDER = "user" on a class whose own order has been measured to be as good as any."""
-        import os
-        env = os.environ.get("PI_MI355_ORDER", "").strip().lower()
+        env = _knobs.read("ORDER")
         if env in ("user", "identity", "none"):
             return None
         big = self.n_states >= self._ORDER_MIN_STATES
@@ -446,7 +444,6 @@ class _CudaPolicyIterationBase(abc.ABC):
         Results never depend on the order; only the sweeps' speed does."""
         import hashlib
         import json
-        import os
         import torch
         D, n = self._D, self.n_states
         dev = torch.device("cuda", torch.cuda.current_device() if self._device_arg is None
@@ -458,7 +455,7 @@ class _CudaPolicyIterationBase(abc.ABC):
             key.update(part)
             key.update(b"|")
         cache = _native.KERNEL_CACHE / f"order_{key.hexdigest()[:24]}.json"
-        if os.environ.get("PI_MI355_ORDER_CACHE", "1") != "0" and cache.exists():
+        if _knobs.read("ORDER_CACHE") and cache.exists():
             try:
                 rec = json.loads(cache.read_text())
                 order = tuple(int(v) for v in rec["order"])
@@ -631,8 +628,7 @@ class _CudaPolicyIterationBase(abc.ABC):
         # only — the states its launches visit)
         if self._term_arg is not None and hasattr(self._backend, "prepare_mask"):
             if self._comm is not None:
-                import os
-                if getattr(self._comm, "delivers_per_state", False) and os.environ.get("PI_MI355_P2P_FUSED", "1") != "0":
+                if getattr(self._comm, "delivers_per_state", False) and _knobs.read("P2P_FUSED"):
                     # the fused exchange of a grid with terminal states delivers from the list sweeps: keep the list
                     # even where it fills no idle lanes
                     self._backend.engine.set_option(Option.KEEP_LIVE_LIST, 1)
@@ -889,7 +885,6 @@ class _CudaPolicyIterationBase(abc.ABC):
         reference can only save after run() has dropped its device arrays (:392-409).  Collective
         on several ranks (every rank calls it); rank 0 writes, to a temporary file that is renamed
         into place."""
-        import os
         filepath = Path(filepath).with_suffix(".npz")
         n = self.n_states
         if self._comm is not None:

@@ -24,11 +24,9 @@ with a transport of its own (tests/dist_transport.py); it is not part of this pa
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 
-from . import _native
+from . import _knobs, _native
 from ._native import Plan
 
 
@@ -73,8 +71,8 @@ class NativeTransport:
             self.engine.comm_init(self.rank, self.world, self._unique_id)
 
     def plan(self, solver) -> None:
-        mode = {"auto": Plan.NONE, "allgather": Plan.ALLGATHER, "halo": Plan.HALO}[os.environ.get("PI_MI355_EXCHANGE", "auto")]
-        overlap = os.environ.get("PI_MI355_OVERLAP", "1") != "0"
+        mode = {"auto": Plan.NONE, "allgather": Plan.ALLGATHER, "halo": Plan.HALO}[_knobs.read("EXCHANGE")]
+        overlap = _knobs.read("OVERLAP")
         self.info = self.engine.exchange_plan(solver._backend._ptr(solver._mask_arg()), solver._shard_len,
                                               mode, overlap, self._stream())
         self.halo_elems = self.info["recv_elems"] if self.info["mode"] == "halo" else -1
@@ -164,7 +162,7 @@ class P2pTransport(NativeTransport):
 
 def from_environment(group=None):
     """The transport a sharded solver uses when it is given none: PI_MI355_TRANSPORT = rccl (default) | p2p."""
-    kind = os.environ.get("PI_MI355_TRANSPORT", "rccl").lower()
+    kind = _knobs.read("TRANSPORT")
     if kind == "p2p":
         return P2pTransport.from_torch_distributed(group)
     if kind != "rccl":

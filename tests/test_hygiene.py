@@ -191,3 +191,48 @@ def test_selector_codes_are_named_not_numbered():
             text = p.read_text()
             offenders += [f"{p.relative_to(ROOT)}:{text.count(chr(10), 0, m.start()) + 1}" for m in pat.finditer(text)]
     assert not offenders, offenders
+
+
+def test_environment_knobs_live_in_two_tables_and_one_document():
+    """Every PI_MI355_* knob is a row of csrc/pi_knobs.cpp or of dynamicprogramming_amd/_knobs.py, which hold the only
+    reads of the environment, and a line of INTEGRATION.md's section "Environment knobs" that repeats the row's
+    description; the product names no other knob, and the knobs of the closed experiments stay gone."""
+    from dynamicprogramming_amd import _knobs
+    token = re.compile(r"PI_MI355_[A-Z0-9_]+")
+    knobs_cpp = ROOT / "dynamicprogramming_amd" / "csrc" / "pi_knobs.cpp"
+    native = dict(re.findall(r'\{K::\w+, "(PI_MI355_[A-Z0-9_]+)",[^"\n]*"([^"\n]*)"\},$', knobs_cpp.read_text(), re.M))
+    assert len(native) == len(re.findall(r"\{K::", knobs_cpp.read_text())) == 21
+    python = {name: doc for name, (_, _, doc) in _knobs.KNOBS.items()}
+    assert len(python) == 8
+    # the one knob both languages read: one rule, spelled the same
+    assert set(native) & set(python) == {"PI_MI355_P2P_FUSED"}
+    assert native["PI_MI355_P2P_FUSED"] == python["PI_MI355_P2P_FUSED"] and _knobs.KNOBS["PI_MI355_P2P_FUSED"][0] == "OffIfZero"
+    assert re.search(r'"PI_MI355_P2P_FUSED", T::OffIfZero,', knobs_cpp.read_text())
+    tables = set(native) | set(python)
+    assert len(tables) == 28
+
+    named = set()
+    for p in list(_product_sources()) + [q for q in (ROOT / "include").rglob("*") if q.is_file()]:
+        text = p.read_text()
+        named |= set(token.findall(text))
+        if p != knobs_cpp:
+            assert "getenv" not in text, p
+        if p.name != "_knobs.py":
+            assert not [ln for ln in text.splitlines() if re.search(r"\benviron\b", ln) and "PI_MI355_" in ln], p
+    assert named - {"PI_MI355_ABI_VERSION", "PI_MI355_H_"} == tables
+
+    section = (ROOT / "INTEGRATION.md").read_text().split("## F. Environment knobs", 1)[1]
+    documented = re.findall(r"^- `(PI_MI355_[A-Z0-9_]+)` — (.*)$", section, re.M)
+    assert sorted(name for name, _ in documented) == sorted(list(native) + [n for n in python if n not in native] + ["PI_MI355_P2P_FUSED"])
+    for name, doc in documented:
+        assert doc in (native.get(name), python.get(name)), name
+    assert set(token.findall(section)) == tables
+
+    removed = {"PI_MI355_" + s for s in ("XCD_TIMING", "XCD_TRACE", "XCD_FIRST_SLEEP", "XCD_RING", "XCD_MIN", "XCD_MAX", "FLOW")}
+    assert not removed & tables
+    for d in PRODUCT_DIRS + ["include", "tools", "tests"]:
+        for p in (ROOT / d).rglob("*"):
+            if p.is_file() and p.suffix in (".py", ".cpp", ".h", ".hip", ".sh", ".md", ".json") and "__pycache__" not in p.parts:
+                assert not removed & set(token.findall(p.read_text())), p
+    # the benchmark sets survivors only
+    assert set(token.findall((ROOT / "bench.py").read_text())) <= tables
