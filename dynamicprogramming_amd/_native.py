@@ -84,6 +84,9 @@ SIGNATURES = {
     "pi_infer_set_partner": (ctypes.c_int, [_vp, _vp, ctypes.c_char_p, ctypes.c_size_t]),
     "pi_infer_rollout_hybrid": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, _f32p, _f32p,
                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "pi_infer_set_values": (ctypes.c_int, [_vp, _f32p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]),
+    "pi_infer_resample": (ctypes.c_int, [_vp, _i32p, ctypes.POINTER(ctypes.c_int64), _f32p, _i32p, ctypes.c_int, _vp, _vp,
+                                         _vp, _vp]),
     "pi_plan_schedule": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_uint64)]),
     "pi_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64]),
@@ -588,6 +591,7 @@ class InferenceEngine:
         act = np.ascontiguousarray(action_space, dtype=np.float32)
         _check(lib().pi_infer_set_policy(self._h, pol.ctypes.data_as(_i32p), len(pol), act.ctypes.data_as(_f32p),
                                          len(act)), "pi_infer_set_policy")
+        self._n_actions = len(act)
 
     def query(self, d_points, m, d_actions=0, d_weights=0, d_indices=0, stream=0) -> None:
         _check(lib().pi_infer_query(self._h, d_points, int(m), d_actions or None, d_weights or None,
@@ -635,6 +639,40 @@ class InferenceEngine:
                                              d_length or None, d_terminated or None, d_secondary_steps or None,
                                              d_last_mode or None, d_traj or None, int(traj_every), stream or None),
                "pi_infer_rollout_hybrid")
+
+    def set_values(self, values) -> str:
+        """Upload the value function of this handle's grid (the user's order) and build the resample kernel (a compile
+        check on a host-only handle); returns the compiler's log."""
+        val = np.ascontiguousarray(values, dtype=np.float32).ravel()
+        log = ctypes.create_string_buffer(1 << 16)
+        rc = lib().pi_infer_set_values(self._h, val.ctypes.data_as(_f32p), len(val), log, len(log))
+        text = log.value.decode(errors="replace")
+        if rc != 0:
+            raise NativeError(f"pi_infer_set_values failed:\n{last_error()}")
+        return text
+
+    def resample(self, dst_shape, dst_strides, dst_bins, d_term=0, d_values=0, d_policy=0, action_map=None, n_actions=0,
+                 stream=0) -> None:
+        """This handle's solution interpolated onto the nodes of another grid in one launch (pi_infer_resample; host
+        arrays for the destination's shape, element strides and per-dimension bin tables, raw device pointers for its
+        mask and outputs; asynchronous).  `action_map`: one destination action index per source action, None = identity."""
+        shape = np.ascontiguousarray(dst_shape, dtype=np.int32)
+        strides = np.ascontiguousarray(dst_strides, dtype=np.int64)
+        tables = [np.ascontiguousarray(b, dtype=np.float32).ravel() for b in dst_bins]
+        if shape.shape != (self.D,) or strides.shape != (self.D,) or [len(t) for t in tables] != shape.tolist():
+            raise ValueError(f"the destination needs {self.D} dimensions: a shape, a stride and a bin table of that length each")
+        bins = np.concatenate(tables)
+        amap = None
+        if action_map is not None:
+            amap = np.ascontiguousarray(action_map, dtype=np.int32)
+            if amap.ndim != 1 or ((amap < 0) | (amap >= int(n_actions))).any():
+                raise ValueError(f"action_map must hold indices into the destination's {int(n_actions)} actions")
+            if len(amap) != getattr(self, "_n_actions", len(amap)):
+                raise ValueError(f"action_map needs one entry per source action ({self._n_actions})")
+        _check(lib().pi_infer_resample(self._h, shape.ctypes.data_as(_i32p), strides.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                       bins.ctypes.data_as(_f32p), None if amap is None else amap.ctypes.data_as(_i32p),
+                                       int(n_actions), d_term or None, d_values or None, d_policy or None, stream or None),
+               "pi_infer_resample")
 
     def close(self) -> None:
         if getattr(self, "_h", None):

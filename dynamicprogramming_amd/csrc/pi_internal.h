@@ -8,6 +8,7 @@
 //   pi_live.cpp       the live-state list of pi_prepare_mask and the per-evaluation list of pi_eval_begin
 //   pi_comm.cpp       multi-GPU transports and the sharded sweep driver;  pi_p2p.cpp  the peer-to-peer transport
 //   pi_infer.cpp, pi_rollout.cpp   the inference handle and its rollouts;  pi_hybrid.cpp  rollouts that switch between two handles
+//   pi_resample.cpp   the inference handle's solution interpolated onto another grid (grid continuation)
 #pragma once
 
 #include "pi_knobs.h"
@@ -253,6 +254,16 @@ struct pi_infer {
     hipFunction_t f_hybrid = nullptr;
     bool has_partner = false;            // pi_infer_set_partner went through (host-only handles: it compiled)
     std::string partner_defines;
+    // fourth module (pi_infer_set_values, pi_resample.cpp): this grid + csrc/pi_resample_kernels.hip, and the value
+    // function of the solution.  d_resample_tab: the destination's bin tables | action map of the last pi_infer_resample
+    // (owned; resample_tab: the same words on the host — a call that brings the same destination uploads nothing)
+    hipModule_t module_resample = nullptr;
+    hipFunction_t f_resample = nullptr, f_resample_wide = nullptr;
+    bool has_values = false;             // pi_infer_set_values went through (host-only handles: the module compiled)
+    float* d_values = nullptr;
+    uint32_t* d_resample_tab = nullptr;
+    size_t resample_tab_capacity = 0;    // words allocated at d_resample_tab
+    std::vector<uint32_t> resample_tab;
 };
 
 namespace pi {

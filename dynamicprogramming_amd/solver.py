@@ -517,6 +517,16 @@ class _CudaPolicyIterationBase(abc.ABC):
     def _to_user(self, a):
         return a if self._order is None else self._backend.to_user(a)
 
+    def _memory_strides(self) -> np.ndarray:
+        """Element stride of every USER dimension in the device arrays (int64): `strides` in the user's order, the
+        strides of the permuted array under a memory order."""
+        order = tuple(range(self._D)) if self._order is None else tuple(self._order)
+        strides, step = np.zeros(self._D, dtype=np.int64), 1
+        for d in reversed(order):
+            strides[d] = step
+            step *= int(self.grid_shape[d])
+        return strides
+
     def _precompute_grid_metadata(self) -> None:
         # Same quantities as :95-109 / :497-514 / :912-937, from the bin tables instead of
         # the materialised (n, D) array (min/max/unique of a column = those of its table).
@@ -654,7 +664,8 @@ class _CudaPolicyIterationBase(abc.ABC):
     def _seed_values(self, mask: np.ndarray, value: float) -> None:
         """Set V (both Jacobi buffers) on the masked grid nodes — supported way to give goal
         cells a non-zero starting value (the crane runner does this by reaching into cupy,
-        runners/overhead_crane_cuda.py:193-206)."""
+        runners/overhead_crane_cuda.py:193-206).  Call it AFTER ``continue_from``, which overwrites the seeds of
+        non-terminal nodes."""
         import torch
         m = torch.from_numpy(np.ascontiguousarray(self._to_memory(np.ascontiguousarray(mask, dtype=bool)))).to(
             self.d_value_function.device)
@@ -873,6 +884,52 @@ class _CudaPolicyIterationBase(abc.ABC):
                     break
         self.stats["value_sweeps"] = self.stats.get("value_sweeps", 0) + sweeps
         return delta
+
+    def continue_from(self, source, *, policy: bool = True) -> None:
+        """Grid continuation: start this (freshly constructed) solver from a solution on ANOTHER grid of the same env —
+        usually a coarser one, which costs 1 / 2^D as much per sweep at half the bins.  `source`: a solver after run(), a
+        load()ed instance, or the path of a save() archive.  Its value function is interpolated onto this grid's nodes
+        (multilinear, the arithmetic of utils.barycentric: the node clamped to the source's bounds) into both Jacobi
+        buffers, and every node takes the greedy action of the nearest source node — the corner of largest weight —
+        translated to the nearest value of this solver's action table when the tables differ; `policy=False` transfers V
+        only.  Terminal nodes keep what construction gave them.  One kernel launch in this solver's own memory order
+        (utils.barycentric.DevicePolicy.resample; csrc/pi_resample_kernels.hip); run(), policy_evaluation() and
+        value_iteration() go on from there.  Seeds of `_seed_values` on non-terminal nodes are overwritten: seed after.
+        Records stats["continued_from"] = {"grid_shape", "seconds"}."""
+        import torch
+        from utils.barycentric import DevicePolicy, action_map
+        if not hasattr(self, "d_value_function"):
+            raise RuntimeError("continue_from needs the device arrays: call it on a freshly constructed solver, before run()")
+        if self._comm is not None:
+            raise NotImplementedError("continue_from on a sharded solver: the multi-GPU path is frozen and has no resample "
+                                      "step; continue on one GPU")
+        keys = ("value_function", "policy", "bounds_low", "bounds_high", "grid_shape", "strides", "corner_bits", "action_space")
+        if isinstance(source, (str, os.PathLike)):
+            data = np.load(Path(source).with_suffix(".npz"))
+            src = {k: data[k] for k in keys}
+        else:
+            src = {k: getattr(source, k, None) for k in keys}
+            if src["value_function"] is None or src["policy"] is None:
+                raise RuntimeError("continue_from needs a solution in host memory: call run() or load() on the source first")
+        if len(np.asarray(src["grid_shape"])) != self._D:
+            raise ValueError(f"the source grid has {len(np.asarray(src['grid_shape']))} dimensions, this solver {self._D}")
+        t0 = time.perf_counter()
+        dev = self.d_value_function.device
+        dp = DevicePolicy(src["policy"] if policy else None, src["action_space"], src["bounds_low"], src["bounds_high"],
+                          src["grid_shape"], src["strides"], src["corner_bits"], device=dev)
+        try:
+            dp.set_values(src["value_function"])
+            dp.resample(self._bins, self._memory_strides(), self._mask_arg(), self.d_value_function, self.d_policy if policy else None,
+                        action_map=action_map(src["action_space"], self.action_space) if policy else None,
+                        n_actions=self.n_actions)
+            torch.cuda.synchronize(dev)
+        finally:
+            dp.close()
+        self.d_new_value_function.copy_(self.d_value_function)
+        self.stats["continued_from"] = {"grid_shape": [int(g) for g in np.asarray(src["grid_shape"])],
+                                        "seconds": time.perf_counter() - t0}
+        logger.info(f"continued from a {'x'.join(str(g) for g in self.stats['continued_from']['grid_shape'])} solution "
+                    f"in {self.stats['continued_from']['seconds']:.3f} s")
 
     def debug_report(self) -> dict:
         """Checked build only (PI_MI355_DEBUG=1 in the environment when the solver was constructed): the

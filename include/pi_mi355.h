@@ -468,6 +468,29 @@ int pi_plan_schedule(pi_handle* h, int block, int64_t first, int64_t count, int6
  *                       both handles are read at launch: a later pi_infer_set_policy on either is picked up.  The
  *                       partner must have the grid the module was built for.  m == 0 is a no-op, n_steps == 0 copies
  *                       the start (lengths, returns, secondary_steps, last_mode 0).  Asynchronous.
+ * Grid continuation on the same handle (no reference counterpart: the reference starts every run from V = 0): the
+ * handle's solution — value function and policy on ITS grid, the SOURCE — interpolated onto the nodes of a DESTINATION
+ * grid of the same D with its own per-dimension bin tables, any bounds, any shape, any memory order of the dimensions
+ * and its own action table, as ONE launch.  For the destination node s with coordinates x_d = bins_d[i_d]:
+ *   1. (w, idx) = the weights and indices pi_infer_query returns for the point x (same bits: the point clamped to the
+ *      source's bounds, corners in the order of the source's corner_bits)
+ *   2. V[s] = float32 sum from 0.0f over ASCENDING corners c of w[c] * V_source[idx[c]], multiply then add
+ *   3. policy[s] = map[policy_source[idx[c*]]], c* the corner of largest w (strict >, from c = 0: the first maximum)
+ *   4. a node whose terminal-mask byte is non-zero is not written.
+ *   pi_infer_set_values    host array: the source's value function (n_states float32, the user's order), copied to the
+ *                       device; builds the handle's FOURTH module, its grid + csrc/pi_resample_kernels.hip (same cache,
+ *                       flags and log convention as pi_infer_set_dynamics).  device = -1: compile check
+ *   pi_infer_resample   dst_shape, dst_strides HOST arrays of D entries in the user's dimension order; dst_strides are
+ *                       the element strides of a dense array of that shape in SOME order of the dimensions (validated),
+ *                       every flat position of the outputs and of the mask is sum_d i_d * dst_strides[d].  dst_bins: the
+ *                       HOST concatenation of the D bin tables (sum_d dst_shape[d] float32; at most 60 KiB, the table
+ *                       pi_create admits).  action_map: HOST, one entry per source action, each in [0, dst_n_actions);
+ *                       null = the identity, which needs dst_n_actions >= the source's action count.  d_dst_term
+ *                       (n uint8 on the device) may be null: every node is written.  d_dst_V (n float32) needs
+ *                       pi_infer_set_values, d_dst_policy (n int32) needs pi_infer_set_policy; one of them may be null.
+ *                       Every refusal is an error code and pi_last_error, never a launch.  The launch is asynchronous on
+ *                       `stream`; a call whose tables or map differ from the previous call's first waits for the device
+ *                       and uploads them.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pi_infer pi_infer;
 pi_infer* pi_infer_create(int device, int D, const float* lo, const float* hi, const int32_t* grid_shape,
@@ -487,6 +510,10 @@ int pi_infer_rollout_hybrid(pi_infer* h, pi_infer* partner, const float* d_start
                             const float* enter, const float* leave, float* d_final, float* d_return, int32_t* d_length,
                             uint8_t* d_terminated, int32_t* d_secondary_steps, uint8_t* d_last_mode, float* d_traj,
                             int traj_every, void* stream);
+int pi_infer_set_values(pi_infer* h, const float* values, int64_t n_states, char* log, size_t log_len);
+int pi_infer_resample(pi_infer* h, const int32_t* dst_shape, const int64_t* dst_strides, const float* dst_bins,
+                      const int32_t* action_map, int dst_n_actions, const uint8_t* d_dst_term, float* d_dst_V,
+                      int32_t* d_dst_policy, void* stream);
 
 /* Tuning: the `what` of pi_set_option. */
 enum pi_option_code {

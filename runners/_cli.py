@@ -20,6 +20,10 @@ the env's start distribution (envs.<Env>.start_states, seeded by --seed; crane: 
 episode; those four flags are then honoured, not ignored.  The 6-D swing-up also writes results/last_trajectory.npz
 (the last 100 states of every episode), the file the reference's scoring script reads.
 
+A third extension flag, --coarse-bins N [N ...] (off by default), trains by grid continuation: the env is solved at
+each N in turn — each level started from the previous level's solution interpolated onto its grid
+(solver.continue_from) — and then at --bins; sweeps and seconds are printed per level.  Only the --bins solution is saved.
+
 The ignored group drives the reference's gymnasium / pygame / matplotlib evaluation harness, which is
 outside the scope of this package: training, saving and loading behave as in
 the reference (train when the archive is missing or --retrain is given, otherwise load it), the
@@ -47,13 +51,28 @@ def bins_space_for(env_name: str, bins: int) -> dict:
 
 
 def train(env_name: str, bins: int | None = None, save_path: Path | str | None = None,
-          value_iteration: bool = False, **kw):
+          value_iteration: bool = False, coarse_bins=(), **kw):
     """Build the env on its reference grid, run policy iteration on the GPU, save the .npz
     (reference: each runner's train(), e.g. pendulum_cuda.py:116-130).  value_iteration=True (extension):
-    fused value-iteration sweeps to the same theta instead, at most max_pi_iter slices of max_eval_iter."""
+    fused value-iteration sweeps to the same theta instead, at most max_pi_iter slices of max_eval_iter.
+    coarse_bins (extension): grid continuation — solve at each of these bins per dimension first, every level
+    (the last one at `bins`) continued from the one before it."""
     from dynamicprogramming_amd import envs
+    previous = None
+    for level in coarse_bins:
+        t0 = time.perf_counter()
+        coarse = envs.make(env_name, int(level), **kw)
+        if previous is not None:
+            coarse.continue_from(previous)
+        coarse.run()
+        st = coarse.stats
+        print(f"[{env_name}] continuation level {int(level)} bins: {st['pi_iterations']} PI iterations, "
+              f"{st['eval_sweeps']} eval sweeps in {time.perf_counter() - t0:.2f} s")
+        previous = coarse
     solver = envs.make(env_name, bins, **kw)
     t0 = time.perf_counter()
+    if previous is not None:
+        solver.continue_from(previous)
     if value_iteration:
         delta = float("inf")
         for _ in range(solver.config.max_pi_iter):
@@ -102,6 +121,9 @@ def build_parser(env_name: str, default_save: str) -> argparse.ArgumentParser:
     p.add_argument("--save-path", type=Path, default=Path(default_save))
     p.add_argument("--value-iteration", action="store_true",
                    help="(extension) train with fused value-iteration sweeps instead of policy iteration")
+    p.add_argument("--coarse-bins", type=int, nargs="+", default=[], metavar="N",
+                   help="(extension) grid continuation: solve at each N bins per dimension first, every level started "
+                        "from the previous level's interpolated solution, then at --bins")
     p.add_argument("--rollout", action="store_true",
                    help="(extension) after training / loading, roll the policy out on the GPU: --episodes episodes of "
                         "--steps steps from the env's start states (--seed; crane: --start-x), one line per episode")
@@ -174,7 +196,7 @@ def main(env_name: str, default_save: str, argv=None):
         print(f"[{env_name}] {pi.n_states:,} states, {pi.n_actions} actions; use --retrain to recompute")
     else:
         print("[*] Training new policy...")
-        pi = train(env_name, args.bins, path, value_iteration=args.value_iteration, **kw)
+        pi = train(env_name, args.bins, path, value_iteration=args.value_iteration, coarse_bins=args.coarse_bins, **kw)
     if args.rollout:
         evaluate(env_name, pi, args.episodes, args.steps, args.seed, start_x=getattr(args, "start_x", None),
                  traj_path=Path("results") / "last_trajectory.npz" if env_name == "double_cartpole_swingup" else None)

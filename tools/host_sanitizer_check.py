@@ -17,7 +17,7 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 # the host sources of libpi_mi355.so (HOST_SRC in csrc/Makefile)
 HOST_SOURCES = ("pi_knobs.cpp", "pi_api.cpp", "pi_probe.cpp", "pi_compile.cpp", "pi_onelaunch.cpp", "pi_live.cpp", "pi_comm.cpp", "pi_p2p.cpp",
-                "pi_infer.cpp", "pi_rollout.cpp", "pi_hybrid.cpp")
+                "pi_infer.cpp", "pi_rollout.cpp", "pi_hybrid.cpp", "pi_resample.cpp")
 
 
 def host_runtime_is_clean_under_address_and_ub_sanitizers(tmp_path: Path) -> str:

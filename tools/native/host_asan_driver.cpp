@@ -122,6 +122,26 @@ int main(int argc, char** argv) {
         const float acts[1] = {0.0f};
         CHECK(pi_infer_set_policy(q, pol, 1, acts, 1) != 0);           // host-only handle holds no policy
         CHECK(pi_infer_query(q, nullptr, 4, nullptr, nullptr, nullptr, nullptr) != 0);
+        // grid continuation: the resample module compiles, every refusal comes before a launch
+        std::vector<float> values(5 * 4 * 6 * 3, 0.5f);
+        CHECK(pi_infer_set_values(q, values.data(), 359, nullptr, 0) != 0);
+        const int32_t dshape[4] = {9, 7, 11, 5};
+        const int64_t dense[4] = {385, 55, 5, 1}, permuted[4] = {5, 45, 315, 1}, holes[4] = {385, 56, 5, 1};
+        std::vector<float> tables(9 + 7 + 11 + 5, 0.25f);
+        float* out_v = reinterpret_cast<float*>(uintptr_t(4096));       // never dereferenced: no device, no launch
+        int32_t* out_p = reinterpret_cast<int32_t*>(uintptr_t(8192));
+        CHECK(pi_infer_resample(q, dshape, dense, tables.data(), nullptr, 1, nullptr, out_v, nullptr, nullptr) != 0);   // no values yet
+        CHECK(pi_infer_set_values(q, values.data(), 360, nullptr, 0) == 0);
+        CHECK(pi_infer_resample(q, dshape, dense, tables.data(), nullptr, 1, nullptr, nullptr, nullptr, nullptr) != 0);
+        CHECK(pi_infer_resample(q, dshape, holes, tables.data(), nullptr, 1, nullptr, out_v, nullptr, nullptr) != 0);
+        CHECK(pi_infer_resample(q, dshape, dense, tables.data(), nullptr, 1, nullptr, out_v, out_p, nullptr) != 0);     // no policy
+        CHECK(pi_infer_resample(q, dshape, permuted, tables.data(), nullptr, 1, nullptr, out_v, nullptr, nullptr) != 0 &&
+              std::strstr(pi_last_error(), "host-only") != nullptr);                                                    // all in order
+        const int32_t wide_shape[4] = {15355, 2, 2, 2};
+        const int64_t wide_strides[4] = {8, 4, 2, 1};
+        std::vector<float> wide(15355 + 6, 0.0f);
+        CHECK(pi_infer_resample(q, wide_shape, wide_strides, wide.data(), nullptr, 1, nullptr, out_v, nullptr, nullptr) != 0 &&
+              std::strstr(pi_last_error(), "60 KiB") != nullptr);
         pi_infer_destroy(q);
         bits[5] = 2;
         CHECK(pi_infer_create(-1, 4, lo, hi, shape, strides, bits, 16, cache) == nullptr);

@@ -13,6 +13,11 @@ ONE hand-written HIP kernel over the whole batch (libpi_mi355.so, ``pi_infer_que
 weights bit-identical to the functions below, the action summed in float32 in ascending corner order.
 Without the keyword nothing here touches the GPU or the native library.
 
+Grid continuation (no reference counterpart): ``resample`` interpolates a solution — value function and policy on one
+grid — onto the nodes of another grid of the same D; ``DevicePolicy.set_values`` + ``DevicePolicy.resample`` are its
+device twin, one HIP kernel launch (``pi_infer_resample``), same bits.  ``action_map`` translates action indices
+between two action tables.
+
 Semantics kept from the reference helper (they differ slightly from the training kernels):
 the POINT is clamped to the bounds (not the cell coordinate), cell widths are float64
 ``(hi - lo) / (shape - 1)``, corners follow the rows of ``corner_bits`` (MSB-first
@@ -54,8 +59,10 @@ class DevicePolicy:
         self._engine = _native.InferenceEngine(bounds_low, bounds_high, grid_shape, strides, corner_bits,
                                                device=self.device.index or 0)
         self._has_policy = policy is not None
+        self._n_actions = 0
         if self._has_policy:
             self._engine.set_policy(policy, action_space)
+            self._n_actions = len(np.asarray(action_space))
 
     def _points(self, states):
         pts = np.ascontiguousarray(np.atleast_2d(states), dtype=np.float32)
@@ -139,6 +146,40 @@ class DevicePolicy:
             return RolloutResult(final, ret, length, term, traj)
         return RolloutResult(final.cpu().numpy(), ret.cpu().numpy(), length.cpu().numpy(), term.cpu().numpy(),
                              traj.cpu().numpy() if every else None)
+
+    def set_values(self, V) -> str:
+        """The value function that goes with this policy's grid (n_states float32, the user's order), for ``resample``;
+        returns the compiler's log of the resample kernel.  Calling it again replaces the values."""
+        log = self._engine.set_values(V)
+        self._has_values = True
+        return log
+
+    def resample(self, bins, strides, term, out_values, out_policy, action_map=None, n_actions=None):
+        """This solution interpolated onto the nodes of another grid in ONE kernel launch — the device twin of the
+        module's ``resample``, same bits.  ``bins``: the destination's D bin tables; ``strides``: the element strides of
+        its dense device arrays, one per dimension in the user's order (any memory order of the dimensions); ``term``:
+        its terminal mask, a uint8 tensor on this device in that memory layout, or None — masked nodes are not written;
+        ``out_values`` (float32) and ``out_policy`` (int32): tensors on this device with at least one entry per node,
+        either may be None.  ``action_map`` (see ``action_map``) and ``n_actions`` describe the destination's action
+        table; by default the destination shares the source's.  Asynchronous on torch's current stream."""
+        torch = self._torch
+        tables = [np.ascontiguousarray(b, dtype=np.float32).ravel() for b in bins]
+        n = int(np.prod([len(t) for t in tables], dtype=np.int64))
+        if out_values is None and out_policy is None:
+            raise ValueError("resample needs out_values or out_policy")
+        if out_values is not None and not getattr(self, "_has_values", False):
+            raise RuntimeError("resample of values needs the value function: call set_values(V) first")
+        if out_policy is not None and not self._has_policy:
+            raise RuntimeError("this DevicePolicy was built without a policy table")
+        for t, dtype, what in ((term, torch.uint8, "term"), (out_values, torch.float32, "out_values"),
+                               (out_policy, torch.int32, "out_policy")):
+            if t is not None and (not torch.is_tensor(t) or t.device != self.device or t.dtype != dtype
+                                  or not t.is_contiguous() or t.numel() < n):
+                raise ValueError(f"{what} must be a contiguous {dtype} tensor on {self.device} with at least {n} entries")
+        ptr = lambda t: 0 if t is None else t.data_ptr()     # noqa: E731
+        self._engine.resample([len(t) for t in tables], strides, tables, d_term=ptr(term), d_values=ptr(out_values),
+                              d_policy=ptr(out_policy), action_map=action_map,
+                              n_actions=self._n_actions if n_actions is None else int(n_actions), stream=self._stream())
 
     def close(self) -> None:
         self._engine.close()
@@ -242,6 +283,49 @@ def get_optimal_action(state, policy, action_space, bounds_low, bounds_high, gri
     lambdas = lambdas.flatten()
     flat = flat.flatten()
     return lambdas @ np.asarray(action_space)[np.asarray(policy)[flat]]
+
+
+def action_map(source_actions, destination_actions):
+    """For every source action the index of the nearest destination action VALUE — float32 absolute difference, the
+    lowest index on ties — as an int32 array; None (the identity) when the two tables are equal."""
+    src = np.ascontiguousarray(source_actions, dtype=np.float32).ravel()
+    dst = np.ascontiguousarray(destination_actions, dtype=np.float32).ravel()
+    if np.array_equal(src, dst):
+        return None
+    return np.abs(src[:, None] - dst[None, :]).argmin(axis=1).astype(np.int32)
+
+
+def resample(value_function, policy, bounds_low, bounds_high, grid_shape, strides, corner_bits, bins, *,
+             action_map=None, at=None, chunk=1 << 18):
+    """A solution on one grid — ``value_function`` and ``policy`` (either may be None) with the grid description
+    ``get_barycentric_weights_and_indices`` takes — interpolated onto the nodes of the grid spanned by the D bin tables
+    ``bins`` (numpy): the twin of ``DevicePolicy.resample``, same definition.  For the node with coordinates
+    ``x_d = bins[d][i_d]``: weights and indices from ``get_barycentric_weights_and_indices`` (the point clamped to the
+    source's bounds); ``V = V + w[c] * value_function[idx[c]]`` in float32 from 0 over ascending corners (multiply,
+    then add); ``policy[idx[c*]]`` at the corner c* of largest weight, the first one on ties, sent through
+    ``action_map`` when one is given.  ``at``: flat indices of the nodes wanted, in the destination's row-major user
+    order (default: every node, in that order).  Returns (V float32 or None, policy int32 or None).  What happens to the
+    destination's terminal nodes is the caller's business: the device leaves them unwritten."""
+    tables = [np.ascontiguousarray(b, dtype=np.float32).ravel() for b in bins]
+    shape = [len(t) for t in tables]
+    at = np.arange(int(np.prod(shape, dtype=np.int64)), dtype=np.int64) if at is None else np.asarray(at, dtype=np.int64)
+    val = None if value_function is None else np.asarray(value_function, dtype=np.float32).ravel()
+    pol = None if policy is None else np.asarray(policy).ravel()
+    V = None if val is None else np.empty(len(at), np.float32)
+    P = None if pol is None else np.empty(len(at), np.int32)
+    for k in range(0, len(at), int(chunk)):
+        node = np.unravel_index(at[k:k + chunk], shape)
+        pts = np.stack([t[i] for t, i in zip(tables, node)], axis=1)
+        w, idx = get_barycentric_weights_and_indices(pts, bounds_low, bounds_high, grid_shape, strides, corner_bits)
+        if val is not None:
+            v = np.zeros(len(pts), np.float32)
+            for c in range(w.shape[1]):
+                v = v + w[:, c] * val[idx[:, c]]
+            V[k:k + chunk] = v
+        if pol is not None:
+            a = pol[idx[np.arange(len(pts)), w.argmax(axis=1)]]
+            P[k:k + chunk] = a if action_map is None else np.asarray(action_map)[a]
+    return V, P
 
 
 def _interpolated_actions(points, policy, action_space, bounds_low, bounds_high, grid_shape, strides, corner_bits):
