@@ -87,6 +87,10 @@ SIGNATURES = {
     "pi_infer_set_values": (ctypes.c_int, [_vp, _f32p, ctypes.c_int64, ctypes.c_char_p, ctypes.c_size_t]),
     "pi_infer_resample": (ctypes.c_int, [_vp, _i32p, ctypes.POINTER(ctypes.c_int64), _f32p, _i32p, ctypes.c_int, _vp, _vp,
                                          _vp, _vp]),
+    "pi_infer_set_greedy": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
+    "pi_infer_greedy": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "pi_infer_rollout_greedy": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                               _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "pi_plan_schedule": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_uint64)]),
     "pi_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64]),
@@ -673,6 +677,34 @@ class InferenceEngine:
                                        bins.ctypes.data_as(_f32p), None if amap is None else amap.ctypes.data_as(_i32p),
                                        int(n_actions), d_term or None, d_values or None, d_policy or None, stream or None),
                "pi_infer_resample")
+
+    def set_greedy(self, action_space) -> str:
+        """Upload the action table of the value-greedy controller and build the greedy kernels behind the plugin of the
+        last set_dynamics (a compile check on a host-only handle); needs set_values and set_dynamics; returns the
+        compiler's log.  A later set_dynamics drops the module again."""
+        act = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        log = ctypes.create_string_buffer(1 << 16)
+        rc = lib().pi_infer_set_greedy(self._h, None if act is None else act.ctypes.data_as(_f32p),
+                                       0 if act is None else len(act), log, len(log))
+        text = log.value.decode(errors="replace")
+        if rc != 0:
+            raise NativeError(f"pi_infer_set_greedy failed:\n{last_error()}")
+        return text
+
+    def greedy(self, d_points, m, gamma, d_best=0, d_action=0, d_q_best=0, d_q_all=0, stream=0) -> None:
+        """The one-step lookahead on the value function at m query points in one launch (pi_infer_greedy; raw device
+        pointers, asynchronous): greedy index, its action value, its Q and the (m, n_actions) matrix of all Q."""
+        _check(lib().pi_infer_greedy(self._h, d_points or None, int(m), float(gamma), d_best or None, d_action or None,
+                                     d_q_best or None, d_q_all or None, stream or None), "pi_infer_greedy")
+
+    def rollout_greedy(self, d_start, m, n_steps, lookahead_gamma, gamma=1.0, d_final=0, d_return=0, d_length=0,
+                       d_terminated=0, d_traj=0, traj_every=0, stream=0) -> None:
+        """m episodes of n_steps closed-loop steps under the value-greedy controller in one launch
+        (pi_infer_rollout_greedy; raw device pointers, asynchronous)."""
+        _check(lib().pi_infer_rollout_greedy(self._h, d_start or None, int(m), int(n_steps), float(gamma),
+                                             float(lookahead_gamma), d_final or None, d_return or None, d_length or None,
+                                             d_terminated or None, d_traj or None, int(traj_every), stream or None),
+               "pi_infer_rollout_greedy")
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -9,6 +9,7 @@
 //   pi_comm.cpp       multi-GPU transports and the sharded sweep driver;  pi_p2p.cpp  the peer-to-peer transport
 //   pi_infer.cpp, pi_rollout.cpp   the inference handle and its rollouts;  pi_hybrid.cpp  rollouts that switch between two handles
 //   pi_resample.cpp   the inference handle's solution interpolated onto another grid (grid continuation)
+//   pi_greedy.cpp     value-greedy control on the inference handle: one-step lookahead on V, queries and rollouts
 #pragma once
 
 #include "pi_knobs.h"
@@ -264,6 +265,14 @@ struct pi_infer {
     uint32_t* d_resample_tab = nullptr;
     size_t resample_tab_capacity = 0;    // words allocated at d_resample_tab
     std::vector<uint32_t> resample_tab;
+    // fifth module (pi_infer_set_greedy, pi_greedy.cpp): this grid + pi_math.h + the env plugin + the helpers of
+    // csrc/pi_rollout_kernels.hip + csrc/pi_greedy_kernels.hip.  d_greedy_actions: the action table of that call
+    // (owned: a handle without a policy has no d_actions); the value function its launches read is d_values
+    hipModule_t module_greedy = nullptr;
+    hipFunction_t f_greedy = nullptr, f_greedy_rollout = nullptr;
+    bool has_greedy = false;             // pi_infer_set_greedy went through (host-only handles: it compiled)
+    float* d_greedy_actions = nullptr;
+    int n_greedy_actions = 0;
 };
 
 namespace pi {
@@ -321,5 +330,6 @@ int compile_image(const std::string& src, const char* cache_dir, char* log, size
 int check_rollout_args(int D, const float* d_start, int64_t m, int n_steps, const float* d_final, const float* d_traj,
                        int traj_every, int64_t* blocks);
 int drop_hybrid(pi_infer* h);           // pi_hybrid.cpp: unloads the third module (after a device synchronisation)
+int drop_greedy(pi_infer* h);           // pi_greedy.cpp: unloads the fifth module (after a device synchronisation)
 
 }  // namespace pi

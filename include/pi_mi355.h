@@ -491,6 +491,30 @@ int pi_plan_schedule(pi_handle* h, int block, int64_t first, int64_t count, int6
  *                       Every refusal is an error code and pi_last_error, never a launch.  The launch is asynchronous on
  *                       `stream`; a call whose tables or map differ from the previous call's first waits for the device
  *                       and uploads them.
+ * Value-greedy control on the same handle (no reference counterpart: the reference acts on the policy table only): the
+ * one-step lookahead on the interpolated value function, a*(s) = argmax_a Q(s, a), at ANY continuous state s.
+ * Q(s, a) is the backup of the sweeps evaluated at s instead of a grid node, bit for bit (NOT the arithmetic of
+ * pi_infer_query): (s', r, done) = step_dynamics(s, a); E = 0 when done, otherwise per dimension
+ * n = (s' - lo) / (hi - lo) * (float)(g - 1) in float32 (IEEE division, then multiply), n = fmaxf(0, fminf(n, g - 1)),
+ * i = min((int)n, g - 2), frac = n - (float)i; corner c takes bit d of c for dimension d (2-D: dimension 1 toggles
+ * fastest; the handle's corner_bits play no part), its weight is the left-to-right float32 product from 1.0f, its index
+ * sum_d (i_d + bit) * strides[d]; E one fmaf chain over ascending corners from 0.0f; Q = r + gamma * E, multiply then add.
+ * The argmax is strict > from -1.0e30f over ascending action indices: the lowest index wins ties, NaN never wins, index 0
+ * with Q = -1.0e30f when nothing wins.  At a non-terminal node of a converged run it returns that node's policy entry.
+ *   pi_infer_set_greedy  host array: the action table (n_actions >= 1 float32), copied to the device — the handle's own
+ *                       copy, a handle without a policy will do; builds the handle's FIFTH module: its grid + the plugin
+ *                       last given to pi_infer_set_dynamics + csrc/pi_greedy_kernels.hip.  Needs pi_infer_set_values and
+ *                       pi_infer_set_dynamics.  Same cache, flags and log convention as pi_infer_set_dynamics; device = -1
+ *                       handles: compile check.  pi_infer_set_dynamics drops the module again (the next greedy call then
+ *                       fails, naming pi_infer_set_greedy); pi_infer_set_values only replaces the values the launches read
+ *   pi_infer_greedy     m query points (m, D) float32 on the device, `gamma` the discount inside Q (not NaN).  Outputs on
+ *                       the device, each may be null but not all: d_best (m) int32 the greedy index, d_action (m) float32
+ *                       its action VALUE, d_q_best (m) float32 its Q, d_q_all (m, n_actions) float32 row-major all of
+ *                       Q(s, .).  m == 0 is a no-op.  Asynchronous.
+ *   pi_infer_rollout_greedy  pi_infer_rollout with the action of every step chosen by the lookahead with the discount
+ *                       `lookahead_gamma`, a property of the solution; `gamma` discounts the return as in pi_infer_rollout
+ *                       (neither may be NaN).  The step taken is step_dynamics(s, actions[best]).  Outputs, trajectory
+ *                       layout, alignment and argument rules are pi_infer_rollout's.  Needs no policy.  Asynchronous.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pi_infer pi_infer;
 pi_infer* pi_infer_create(int device, int D, const float* lo, const float* hi, const int32_t* grid_shape,
@@ -514,6 +538,12 @@ int pi_infer_set_values(pi_infer* h, const float* values, int64_t n_states, char
 int pi_infer_resample(pi_infer* h, const int32_t* dst_shape, const int64_t* dst_strides, const float* dst_bins,
                       const int32_t* action_map, int dst_n_actions, const uint8_t* d_dst_term, float* d_dst_V,
                       int32_t* d_dst_policy, void* stream);
+int pi_infer_set_greedy(pi_infer* h, const float* action_space, int n_actions, char* log, size_t log_len);
+int pi_infer_greedy(pi_infer* h, const float* d_points, int64_t m, float gamma, int32_t* d_best, float* d_action,
+                    float* d_q_best, float* d_q_all, void* stream);
+int pi_infer_rollout_greedy(pi_infer* h, const float* d_start, int64_t m, int n_steps, float gamma, float lookahead_gamma,
+                            float* d_final, float* d_return, int32_t* d_length, uint8_t* d_terminated, float* d_traj,
+                            int traj_every, void* stream);
 
 /* Tuning: the `what` of pi_set_option. */
 enum pi_option_code {

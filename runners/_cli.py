@@ -20,6 +20,10 @@ the env's start distribution (envs.<Env>.start_states, seeded by --seed; crane: 
 episode; those four flags are then honoured, not ignored.  The 6-D swing-up also writes results/last_trajectory.npz
 (the last 100 states of every episode), the file the reference's scoring script reads.
 
+--controller {policy,greedy} (extension, default policy) chooses what acts in those episodes: the interpolated policy table,
+or the greedy one-step lookahead on the interpolated value function (solver.rollout(controller="greedy")), which needs
+only V.  The printed lines and last_trajectory.npz keep their form.
+
 A third extension flag, --coarse-bins N [N ...] (off by default), trains by grid continuation: the env is solved at
 each N in turn — each level started from the previous level's solution interpolated onto its grid
 (solver.continue_from) — and then at --bins; sweeps and seconds are printed per level.  Only the --bins solution is saved.
@@ -127,6 +131,9 @@ def build_parser(env_name: str, default_save: str) -> argparse.ArgumentParser:
     p.add_argument("--rollout", action="store_true",
                    help="(extension) after training / loading, roll the policy out on the GPU: --episodes episodes of "
                         "--steps steps from the env's start states (--seed; crane: --start-x), one line per episode")
+    p.add_argument("--controller", choices=("policy", "greedy"), default="policy",
+                   help="(extension, with --rollout) what acts in the episodes: the interpolated policy table, or the "
+                        "greedy one-step lookahead on the interpolated value function")
     return p
 
 
@@ -134,18 +141,18 @@ STEADY_WINDOW = 100     # states per episode in results/last_trajectory.npz (the
 
 
 def evaluate(env_name: str, pi, episodes: int, steps: int, seed: int, start_x: float | None = None,
-             traj_path: Path | None = None):
+             traj_path: Path | None = None, controller: str = "policy"):
     """--rollout: `episodes` closed-loop episodes of at most `steps` steps in one kernel launch (solver.rollout), one
     line each.  `traj_path`: also dump the last min(100, length + 1) states of every episode, concatenated, as the
-    reference's evaluate() does for its scoring script (double_cartpole_swingup_cuda.py:583-592).  Returns the
-    RolloutResult."""
+    reference's evaluate() does for its scoring script (double_cartpole_swingup_cuda.py:583-592).  `controller`:
+    "policy" or "greedy" (--controller).  Returns the RolloutResult."""
     import numpy as np
     from dynamicprogramming_amd import envs
     cls = envs.ENVS[env_name]
     rng = np.random.default_rng(seed)
     kw = {} if start_x is None else {"start_x": start_x}
     starts = cls.start_states(rng, episodes, **kw)
-    res = pi.rollout(starts, steps, gamma=1.0, record_every=1 if traj_path is not None else 0)
+    res = pi.rollout(starts, steps, gamma=1.0, record_every=1 if traj_path is not None else 0, controller=controller)
     for ep in range(episodes):
         outcome = "terminated" if res.terminated[ep] else f"{steps} steps"
         final = "  ".join(f"{v:+.4f}" for v in res.states[ep])
@@ -166,12 +173,13 @@ def evaluate(env_name: str, pi, episodes: int, steps: int, seed: int, start_x: f
 
 def ignored_flags(args) -> list:
     """The flags of this command line that nothing here acts on.  --render, --record and --no-plot always; --episodes,
-    --steps, --seed and --start-x unless --rollout runs the evaluation they belong to."""
+    --steps, --seed, --start-x and --controller unless --rollout runs the evaluation they belong to."""
     harness = not args.rollout
     return [f for f, on in (("--render", args.render), ("--record", args.record is not None),
                             ("--episodes", harness and args.episodes != 5), ("--steps", harness and args.steps != 1000),
                             ("--seed", harness and args.seed != 42), ("--no-plot", args.no_plot),
-                            ("--start-x", harness and getattr(args, "start_x", 2.5) != 2.5)) if on]
+                            ("--start-x", harness and getattr(args, "start_x", 2.5) != 2.5),
+                            ("--controller", harness and args.controller != "policy")) if on]
 
 
 def main(env_name: str, default_save: str, argv=None):
@@ -199,5 +207,6 @@ def main(env_name: str, default_save: str, argv=None):
         pi = train(env_name, args.bins, path, value_iteration=args.value_iteration, coarse_bins=args.coarse_bins, **kw)
     if args.rollout:
         evaluate(env_name, pi, args.episodes, args.steps, args.seed, start_x=getattr(args, "start_x", None),
-                 traj_path=Path("results") / "last_trajectory.npz" if env_name == "double_cartpole_swingup" else None)
+                 traj_path=Path("results") / "last_trajectory.npz" if env_name == "double_cartpole_swingup" else None,
+                 controller=args.controller)
     return pi

@@ -16,7 +16,13 @@ swing-up grid with the 25^6 balance grid as its partner, seeded random policies,
 uniform in the swing-up grid; per m the fused hybrid call, the loop it replaces (a query on each handle and one plugin
 step per time step, the mode rule and the bookkeeping as torch ops) and the single-policy fused rollout of the same
 batch.  The table is appended to --out.
-usage: python tools/rollout_bench.py [--hybrid] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
+--greedy: the value-greedy controller instead (pi_infer_rollout_greedy, csrc/pi_greedy_kernels.hip): C2, C3 and the 25^6
+double cart-pole with the env plugins' action tables, a seeded value function V ~ 30 N(0, 1) and a seeded random policy,
+m = 4 096 episodes of --steps steps; per config the fused greedy rollout, the loop it replaces (one pi_infer_greedy and
+one pi_probe_step launch per time step plus the bookkeeping as torch ops) and the fused interpolated-policy rollout of the
+same batch, then the registers and scratch of both greedy kernels (hipcc -Rpass-analysis=kernel-resource-usage on the
+translation unit pi_infer_set_greedy builds).  The table is written to --out.
+usage: python tools/rollout_bench.py [--hybrid | --greedy] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
 """
 import argparse
 import json
@@ -202,6 +208,169 @@ def hybrid_child(args):
     eng.close()
 
 
+def greedy_child(args):
+    import numpy as np
+    import torch
+    from dynamicprogramming_amd import _native, envs
+    from utils import barycentric as B
+    env, bins = CONFIGS[args.config]
+    cls = envs.ENVS[env]
+    tabs = [np.asarray(b, np.float32) for b in cls.bins_space(bins).values()]
+    D = len(tabs)
+    shape = np.array([len(t) for t in tabs], np.int32)
+    lo, hi = np.array([t.min() for t in tabs], np.float32), np.array([t.max() for t in tabs], np.float32)
+    strides = np.array([int(np.prod(shape[d + 1:])) for d in range(D)], np.int32)
+    bits = np.array(list(product([0, 1], repeat=D)), dtype=np.int32)
+    acts = np.asarray(cls.ACTIONS, np.float32)
+    rng = np.random.default_rng(0)
+    n = int(np.prod(shape.astype(np.int64)))
+    policy = rng.integers(0, len(acts), size=n, dtype=np.int32)
+    V = (30.0 * rng.standard_normal(n, dtype=np.float32)).astype(np.float32)
+    m, steps, lookahead = args.m, args.steps, 0.99
+    dev = torch.device("cuda:0")
+    starts = torch.from_numpy((lo + (hi - lo) * rng.random((m, D), dtype=np.float32)).astype(np.float32)).to(dev)
+    dp = B.DevicePolicy(policy, acts, lo, hi, shape, strides, bits, device=dev)
+    dp.set_dynamics(envs.dynamics_source(env))
+    dp.set_values(V)
+    dp.set_greedy()
+    eng = _native.Engine(D, shape, lo, hi, tabs, acts, device=0)
+    eng.compile(envs.dynamics_source(env))
+    st = torch.cuda.current_stream(dev).cuda_stream
+
+    def fused():
+        return dp.rollout(starts, steps, controller="greedy", lookahead_gamma=lookahead)
+
+    def single():
+        return dp.rollout(starts, steps)
+
+    def loop():
+        states = starts.clone()
+        nxt = torch.empty_like(states)
+        rew = torch.empty(m, dtype=torch.float32, device=dev)
+        done = torch.empty(m, dtype=torch.uint8, device=dev)
+        ret = torch.zeros(m, dtype=torch.float32, device=dev)
+        length = torch.zeros(m, dtype=torch.int32, device=dev)
+        ended = torch.zeros(m, dtype=torch.bool, device=dev)
+        for t in range(steps):
+            act = dp.greedy(states, lookahead)[1]
+            eng.probe_step(states.data_ptr(), act.data_ptr(), nxt.data_ptr(), rew.data_ptr(), done.data_ptr(), m, st)
+            run = ~ended
+            ret = torch.where(run, ret + rew, ret)
+            states = torch.where(run[:, None], nxt, states)
+            length = torch.where(run, torch.full_like(length, t + 1), length)
+            ended = ended | (run & (done != 0))
+        return B.RolloutResult(states, ret, length, ended, None)
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record()
+        out = fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1), out
+
+    a, b = fused(), loop()                                # warm-up of all paths, and: same results
+    c = single()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(a.states.view(torch.int32), b.states.view(torch.int32)) and torch.equal(a.lengths, b.lengths)
+                and torch.equal(a.returns.view(torch.int32), b.returns.view(torch.int32)))
+    t_fused, t_loop, t_single = [], [], []
+    for _ in range(args.repeat):
+        t_fused.append(timed(fused)[0])
+        t_loop.append(timed(loop)[0])
+        t_single.append(timed(single)[0])
+    print(json.dumps({"config": args.config, "env": env, "bins": bins, "D": D, "actions": len(acts), "m": m, "steps": steps,
+                      "same_bits": same, "fused_ms": min(t_fused), "loop_ms": min(t_loop), "single_ms": min(t_single),
+                      "episode_steps": int(a.lengths.sum().item()), "single_episode_steps": int(c.lengths.sum().item()),
+                      "terminated_share": float(a.terminated.float().mean().item()), "launches_loop": 2 * steps}))
+    dp.close()
+    eng.close()
+
+
+def greedy_usage(env, bins):
+    """VGPRs and scratch bytes per lane of both greedy kernels for one grid: the translation unit pi_infer_set_greedy hands
+    to hipRTC, built ahead of time with the same flags."""
+    import tempfile
+    import numpy as np
+    from __graft_entry__ import HIPCC
+    from dynamicprogramming_amd import envs
+    cls = envs.ENVS[env]
+    tabs = [np.asarray(b, np.float32) for b in cls.bins_space(bins).values()]
+    D = len(tabs)
+    shape = [len(t) for t in tabs]
+    strides = [int(np.prod(shape[d + 1:])) for d in range(D)]
+
+    def braces(v, fmt):
+        return "{" + ",".join(fmt(x) for x in v) + "}"
+
+    def hexf(x):
+        return float(np.float32(x)).hex() + "f"
+    csrc = ROOT / "dynamicprogramming_amd" / "csrc"
+    text = (f"#define PI_GREEDY 1\n#define PI_D {D}\n#define PI_LO_INIT {braces([t.min() for t in tabs], hexf)}\n"
+            f"#define PI_HI_INIT {braces([t.max() for t in tabs], hexf)}\n#define PI_SHAPE_INIT {braces(shape, str)}\n"
+            f"#define PI_STRIDES_INIT {braces(strides, str)}\n"
+            f"#define PI_BITS_INIT {braces(list(product([0, 1], repeat=D)), lambda r: braces(r, str))}\n"
+            f"{(ROOT / 'include' / 'pi_math.h').read_text()}\n#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n"
+            f"{envs.dynamics_source(env)}\n{(csrc / 'pi_rollout_kernels.hip').read_text()}\n"
+            f"{(csrc / 'pi_greedy_kernels.hip').read_text()}\n")
+    usage, fn = {}, None
+    with tempfile.TemporaryDirectory(prefix="pi_greedy_") as tmp:
+        src = Path(tmp) / "greedy.hip"
+        src.write_text(text)
+        res = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
+                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src), "-o",
+                              str(Path(tmp) / "greedy.hsaco")], capture_output=True, text=True)
+    if res.returncode != 0:
+        sys.exit(f"hipcc failed on the greedy translation unit of {env} {bins}^{D}\n{res.stderr[-2000:]}")
+    for line in res.stderr.splitlines():
+        if "Function Name:" in line:
+            fn = line.split("Function Name:")[1].split()[0]
+            usage[fn] = {}
+        elif fn and " VGPRs:" in line:
+            usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
+        elif fn and "ScratchSize" in line:
+            usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+    return usage
+
+
+def greedy_driver(args):
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    me = [sys.executable, str(Path(__file__).resolve())]
+    rows = []
+    for config in CONFIGS:
+        res = subprocess.run(["timeout", "-k", "10", str(CHILD_SECONDS), *me, "--child", "--greedy", "--config", config, "--m",
+                              str(args.m), "--steps", str(args.steps), "--repeat", str(args.repeat)], capture_output=True, text=True)
+        if res.returncode != 0:                           # a fault, an abort or a time limit: nothing more runs
+            sys.exit(f"greedy {config} ended with status {res.returncode}; stopping\n{res.stdout[-2000:]}\n{res.stderr[-2000:]}")
+        rows.append(json.loads(res.stdout.strip().splitlines()[-1]))
+        print(rows[-1], flush=True)
+    lines = [f"value-greedy rollouts (one-step lookahead on V) vs the step-by-step loop, MI355X, commit {args.commit}",
+             f"{args.m} episodes of {args.steps} steps, the env plugins' action tables, V ~ 30 N(0, 1) and a random policy (seeded), "
+             f"lookahead gamma 0.99, starts uniform in the grid; times in ms: the better of {args.repeat} after one warm-up, "
+             "device events around the whole call",
+             "policy: the fused interpolated-policy rollout (pi_infer_rollout) of the same batch; ep-steps: steps actually "
+             "taken under the greedy controller (episodes that ended stop)",
+             "",
+             f"{'config':30s} {'actions':>7s} {'fused':>10s} {'loop':>10s} {'loop/fused':>10s} {'policy':>10s} {'ep-steps':>12s} "
+             f"{'M ep-steps/s':>12s} {'ended':>6s} {'same bits':>9s}"]
+    for r in rows:
+        lines.append(f"{r['config'] + ' ' + r['env'] + ' ' + str(r['bins']) + '^' + str(r['D']):30s} {r['actions']:7d} "
+                     f"{r['fused_ms']:10.3f} {r['loop_ms']:10.3f} {r['loop_ms'] / r['fused_ms']:10.1f} {r['single_ms']:10.3f} "
+                     f"{r['episode_steps']:12d} {r['episode_steps'] / r['fused_ms'] / 1e3:12.2f} {r['terminated_share']:6.3f} "
+                     f"{str(r['same_bits']):>9s}")
+    slower = [r["config"] for r in rows if r["fused_ms"] >= r["loop_ms"]]
+    lines += ["", "the fused kernel is faster than its own step-by-step loop on every config" if not slower else
+              f"the fused kernel is NOT faster than its own step-by-step loop on: {', '.join(slower)}", "",
+              "registers and scratch (hipcc -Rpass-analysis=kernel-resource-usage, the translation unit of pi_infer_set_greedy):"]
+    for config, (env, bins) in CONFIGS.items():
+        for fn, k in sorted(greedy_usage(env, bins).items()):
+            lines.append(f"  {config} {env:24s} {fn:26s} VGPRs {k['vgpr']:4d}  scratch {k['scratch']} bytes/lane")
+    out.write_text("\n".join(lines) + "\n")
+    print(out.read_text())
+
+
 def hybrid_driver(args):
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
@@ -278,10 +447,13 @@ def main():
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--hybrid", action="store_true")
+    ap.add_argument("--greedy", action="store_true")
     ap.add_argument("--config", choices=list(CONFIGS), default="c3")
     ap.add_argument("--m", type=int, default=4096)
     args = ap.parse_args()
-    if args.hybrid:
+    if args.greedy:
+        (greedy_child if args.child else greedy_driver)(args)
+    elif args.hybrid:
         (hybrid_child if args.child else hybrid_driver)(args)
     else:
         (child if args.child else driver)(args)

@@ -18,6 +18,12 @@ grid — onto the nodes of another grid of the same D; ``DevicePolicy.set_values
 device twin, one HIP kernel launch (``pi_infer_resample``), same bits.  ``action_map`` translates action indices
 between two action tables.
 
+Value-greedy control (no reference counterpart): ``greedy_action`` is the one-step lookahead on the interpolated VALUE
+function, ``a*(s) = argmax_a [r(s, a) + gamma * E[V](s')]`` — the improvement backup of the training kernels at an
+arbitrary continuous state, in their arithmetic, not this helper's — and ``greedy_rollout`` the closed loop under it;
+``DevicePolicy.set_greedy`` + ``DevicePolicy.greedy`` / ``DevicePolicy.rollout(controller="greedy")`` are their device
+twins, one HIP kernel launch each (``pi_infer_greedy``, ``pi_infer_rollout_greedy``), same bits.  It needs only V.
+
 Semantics kept from the reference helper (they differ slightly from the training kernels):
 the POINT is clamped to the bounds (not the cell coordinate), cell widths are float64
 ``(hi - lo) / (shape - 1)``, corners follow the rows of ``corner_bits`` (MSB-first
@@ -44,7 +50,8 @@ class DevicePolicy:
     bounds_low, bounds_high, grid_shape, strides, corner_bits, device="cuda:0")``; calling it with
     states (m, D) returns the m interpolated actions (float32 numpy array); ``weights_and_indices``
     returns what ``get_barycentric_weights_and_indices`` returns.  ``policy`` may be None when only
-    weights and indices are wanted.  Raises if the native library or a GPU is missing (no fallback)."""
+    weights and indices, or the value-greedy controller (``set_values``, ``set_dynamics``, ``set_greedy``: it acts on
+    the value function and ``action_space``), are wanted.  Raises if the native library or a GPU is missing (no fallback)."""
 
     def __init__(self, policy, action_space, bounds_low, bounds_high, grid_shape, strides, corner_bits,
                  device="cuda:0"):
@@ -60,6 +67,9 @@ class DevicePolicy:
                                                device=self.device.index or 0)
         self._has_policy = policy is not None
         self._n_actions = 0
+        # the action table on its own: the value-greedy controller needs no policy (set_greedy)
+        self._action_space = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        self._greedy_actions = None                # the table of the last set_greedy; None: no greedy module
         if self._has_policy:
             self._engine.set_policy(policy, action_space)
             self._n_actions = len(np.asarray(action_space))
@@ -102,13 +112,14 @@ class DevicePolicy:
         log = self._engine.set_dynamics(dynamics_src)
         self._has_dynamics = True
         self._dynamics_serial = getattr(self, "_dynamics_serial", 0) + 1      # HybridPolicy rebuilds its module after this
+        self._greedy_actions = None                                           # the library dropped the greedy module
         return log
 
-    def _rollout_buffers(self, states, steps, record_every):
+    def _rollout_buffers(self, states, steps, record_every, need_policy=True):
         """Checked arguments and the output tensors every rollout fills: (on_device, d_start, m, steps, every, final,
         returns, lengths, terminated (uint8), trajectory or None)."""
         torch = self._torch
-        if not self._has_policy:
+        if need_policy and not self._has_policy:
             raise RuntimeError("this DevicePolicy was built without a policy table")
         if not getattr(self, "_has_dynamics", False):
             raise RuntimeError("rollout needs the env's dynamics: call set_dynamics(dynamics_src) first")
@@ -130,17 +141,32 @@ class DevicePolicy:
         traj = torch.empty((steps // every + 1, m, self.D), dtype=torch.float32, device=self.device) if every else None
         return on_device, d_start, m, steps, every, final, ret, length, term, traj
 
-    def rollout(self, states, steps, gamma=1.0, record_every=0):
+    def rollout(self, states, steps, gamma=1.0, record_every=0, controller="policy", lookahead_gamma=None):
         """Closed-loop episodes from ``states`` (m, D) in ONE kernel launch: per step the interpolated action (what
         calling this object returns for the state, same bits) and the plugin's ``step_dynamics``; an episode whose
         step reports `done` keeps the state it reached.  ``returns`` accumulates ``ret + disc * r`` in float32,
         ``disc`` running through ``gamma``.  ``record_every = k > 0``: ``trajectory[j]`` holds all states after
         ``j * k`` steps (row 0 the start, ended episodes repeat their last state), ``steps // k + 1`` rows.
-        A float32 tensor on this device in -> torch tensors on the device out; a numpy array in -> numpy out."""
-        on_device, d_start, m, steps, every, final, ret, length, term, traj = self._rollout_buffers(states, steps, record_every)
-        self._engine.rollout(d_start.data_ptr(), m, steps, gamma, d_final=final.data_ptr(), d_return=ret.data_ptr(),
-                             d_length=length.data_ptr(), d_terminated=term.data_ptr(),
-                             d_traj=traj.data_ptr() if every else 0, traj_every=every, stream=self._stream())
+        A float32 tensor on this device in -> torch tensors on the device out; a numpy array in -> numpy out.
+        ``controller="greedy"``: per step the action ``greedy`` returns for the state with the discount
+        ``lookahead_gamma`` (required; a property of the solution, not the ``gamma`` the return is summed with) instead
+        of the interpolated one — after ``set_greedy``, no policy table needed; everything else is the same."""
+        if controller not in ("policy", "greedy"):
+            raise ValueError(f"controller must be 'policy' or 'greedy', not {controller!r}")
+        greedy = controller == "greedy"
+        if greedy and lookahead_gamma is None:
+            raise ValueError("controller='greedy' needs lookahead_gamma, the discount the value function was solved with")
+        if greedy and getattr(self, "_greedy_actions", None) is None:
+            raise RuntimeError("the greedy controller needs set_greedy() (again after every set_dynamics)")
+        on_device, d_start, m, steps, every, final, ret, length, term, traj = \
+            self._rollout_buffers(states, steps, record_every, need_policy=not greedy)
+        outs = dict(d_final=final.data_ptr(), d_return=ret.data_ptr(), d_length=length.data_ptr(),
+                    d_terminated=term.data_ptr(), d_traj=traj.data_ptr() if every else 0, traj_every=every,
+                    stream=self._stream())
+        if greedy:
+            self._engine.rollout_greedy(d_start.data_ptr(), m, steps, lookahead_gamma, gamma, **outs)
+        else:
+            self._engine.rollout(d_start.data_ptr(), m, steps, gamma, **outs)
         term = term != 0
         if on_device:
             return RolloutResult(final, ret, length, term, traj)
@@ -153,6 +179,48 @@ class DevicePolicy:
         log = self._engine.set_values(V)
         self._has_values = True
         return log
+
+    def set_greedy(self, action_space=None) -> str:
+        """Build the value-greedy controller — the one-step lookahead on the value function of ``set_values`` through
+        the plugin of ``set_dynamics`` — over ``action_space`` (default: the table the constructor was given); returns
+        the compiler's log.  Needs no policy table.  ``set_dynamics`` drops it again; ``set_values`` only replaces the
+        values it reads."""
+        acts = self._action_space if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        if acts is None:
+            raise ValueError("set_greedy needs an action table: this DevicePolicy was built without one")
+        if not getattr(self, "_has_values", False):
+            raise RuntimeError("the greedy controller needs the value function: call set_values(V) first")
+        if not getattr(self, "_has_dynamics", False):
+            raise RuntimeError("the greedy controller needs the env's dynamics: call set_dynamics(dynamics_src) first")
+        log = self._engine.set_greedy(acts)
+        self._greedy_actions = acts
+        return log
+
+    def greedy(self, states, gamma, q_values=False):
+        """The greedy one-step lookahead at ``states`` (m, D) in ONE kernel launch — the device twin of the module's
+        ``greedy_action``, same bits: ``(best_index (m,) int32, action (m,) float32, q_best (m,) float32)`` and, with
+        ``q_values=True``, the matrix ``Q (m, n_actions)`` float32 behind them.  A numpy array in -> numpy out, a float32
+        tensor on this device in -> torch tensors on the device out, like calling this object."""
+        torch = self._torch
+        if getattr(self, "_greedy_actions", None) is None:
+            raise RuntimeError("the greedy controller needs set_greedy() (again after every set_dynamics)")
+        on_device = torch.is_tensor(states)
+        if on_device:
+            if states.device != self.device or states.dtype != torch.float32 or states.dim() != 2 \
+                    or states.shape[1] != self.D:
+                raise ValueError(f"device states must be a float32 (m, {self.D}) tensor on {self.device}")
+            d_pts, m = states.contiguous(), states.shape[0]
+        else:
+            d_pts, m = self._points(states)
+        best = torch.empty(m, dtype=torch.int32, device=self.device)
+        act = torch.empty(m, dtype=torch.float32, device=self.device)
+        qb = torch.empty(m, dtype=torch.float32, device=self.device)
+        out = [best, act, qb]
+        if q_values:
+            out.append(torch.empty((m, len(self._greedy_actions)), dtype=torch.float32, device=self.device))
+        self._engine.greedy(d_pts.data_ptr(), m, gamma, d_best=best.data_ptr(), d_action=act.data_ptr(),
+                            d_q_best=qb.data_ptr(), d_q_all=out[3].data_ptr() if q_values else 0, stream=self._stream())
+        return tuple(out) if on_device else tuple(x.cpu().numpy() for x in out)
 
     def resample(self, bins, strides, term, out_values, out_policy, action_map=None, n_actions=None):
         """This solution interpolated onto the nodes of another grid in ONE kernel launch — the device twin of the
@@ -416,3 +484,97 @@ def hybrid_rollout(step, states, steps, primary, secondary, enter, leave, gamma=
                 a[which] = _interpolated_actions(pts[which], *tables)
         return a
     return HybridRolloutResult(*_closed_loop(step, states, steps, gamma, record_every, act), second, mode.astype(np.uint8))
+
+
+def _fmaf(a, b, c):
+    """``fmaf(a, b, c)`` on float32 arrays, exactly: numpy has no fused multiply-add.  The product of two float32 is
+    exact in float64; the sum with c is rounded to ODD there — TwoSum recovers the rounding error, and an inexact sum
+    with an even last bit moves to its odd neighbour on the error's side — so the one final rounding to float32 sees
+    a sticky bit and cannot round twice."""
+    a, b, c = (np.asarray(x, dtype=np.float32) for x in (a, b, c))
+    with np.errstate(over="ignore", invalid="ignore"):
+        p = a.astype(np.float64) * b.astype(np.float64)
+        c64 = c.astype(np.float64)
+        s = p + c64
+        bb = s - p
+        err = (p - (s - bb)) + (c64 - bb)
+        s, err = np.atleast_1d(s).ravel(), np.atleast_1d(err).ravel()
+        # an overflowed sum leaves a NaN error term: nothing to fix there
+        fix = np.flatnonzero(np.isfinite(err) & (err != 0.0) & ((s.view(np.int64) & 1) == 0))
+        if len(fix):
+            s[fix] = np.nextafter(s[fix], np.where(err[fix] > 0.0, np.inf, -np.inf))
+        return s.astype(np.float32).reshape(p.shape)
+
+
+def _expected_value(points, value_function, bounds_low, bounds_high, grid_shape, strides):
+    """E[V] at ``points`` (k, D) in the arithmetic of the training kernels' backup: per dimension
+    ``n = (x - lo) / (hi - lo) * (g - 1)`` in float32 (divide, then multiply), clamped to [0, g - 1] (a NaN lands on the
+    top border), ``i = min(int(n), g - 2)``, ``frac = n - i``; corner c takes bit d of c for dimension d (2-D: dimension
+    1 toggles fastest), its weight the left-to-right float32 product from 1, its index ``sum (i_d + bit) * stride_d``
+    in int32; one fmaf chain over ascending corners from 0."""
+    pts = np.asarray(points, dtype=np.float32)
+    V = np.asarray(value_function, dtype=np.float32).ravel()
+    lo, hi = np.asarray(bounds_low, dtype=np.float32), np.asarray(bounds_high, dtype=np.float32)
+    g, st = np.asarray(grid_shape, dtype=np.int32), np.asarray(strides, dtype=np.int32)
+    k, D = pts.shape
+    corners = np.arange(1 << D)
+    w = np.ones((k, 1 << D), np.float32)                       # all corners at once: one multiply per dimension, in order
+    idx = np.zeros((k, 1 << D), np.int32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for d in range(D):
+            top = np.float32(g[d] - 1)
+            n = (pts[:, d] - lo[d]) / np.float32(hi[d] - lo[d]) * top
+            n = np.fmax(np.float32(0.0), np.fmin(n, top))
+            i = np.minimum(n.astype(np.int32), np.int32(g[d] - 2))
+            frac = n - i.astype(np.float32)
+            bit = ((corners >> (1 - d if D == 2 else d)) & 1).astype(np.int32)
+            w = w * np.where(bit[None, :] == 1, frac[:, None], (np.float32(1.0) - frac)[:, None])
+            idx = idx + (i[:, None] + bit[None, :]) * st[d]
+        values = V[idx]
+        e = np.zeros(k, np.float32)
+        for c in corners:
+            e = _fmaf(w[:, c], values[:, c], e)
+    return e
+
+
+def greedy_action(step, points, value_function, action_space, bounds_low, bounds_high, grid_shape, strides, gamma,
+                  q_values=False):
+    """Greedy one-step lookahead on the interpolated value function at ``points`` (m, D) (numpy): the twin of
+    ``DevicePolicy.greedy``, same definition.  ``step`` is the batched env step ``rollout`` takes.  For every action
+    ``a`` of ``action_space`` in ascending order: ``(s', r, done) = step(points, a)``, ``E = 0`` where done and the
+    interpolation of ``_expected_value`` elsewhere, ``Q = r + gamma * E`` in float32 (multiply, then add); the greedy
+    action is the strict ``>`` argmax from -1e30: the lowest index wins ties, NaN never wins, index 0 with Q = -1e30
+    when nothing wins.  Returns ``(best_index int32, action float32, q_best float32)`` and, with ``q_values=True``,
+    ``Q (m, n_actions)`` float32."""
+    pts = np.ascontiguousarray(np.atleast_2d(points), dtype=np.float32)
+    acts = np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+    m = len(pts)
+    g32 = np.float32(gamma)
+    best = np.zeros(m, np.int32)
+    best_q = np.full(m, np.float32(-1.0e30), np.float32)
+    Q = np.empty((m, len(acts)), np.float32)
+    for a, u in enumerate(acts):
+        nxt, rew, done = step(pts, np.full(m, u, np.float32))
+        nxt, done = np.asarray(nxt, np.float32), np.asarray(done, bool)
+        e = np.zeros(m, np.float32)
+        if not done.all():
+            e[~done] = _expected_value(nxt[~done], value_function, bounds_low, bounds_high, grid_shape, strides)
+        with np.errstate(over="ignore", invalid="ignore"):
+            q = np.asarray(rew, np.float32) + g32 * e
+            wins = q > best_q
+        Q[:, a] = q
+        best_q = np.where(wins, q, best_q)
+        best = np.where(wins, np.int32(a), best)
+    out = (best, acts[best], best_q)
+    return out + (Q,) if q_values else out
+
+
+def greedy_rollout(step, states, steps, value_function, action_space, bounds_low, bounds_high, grid_shape, strides,
+                   lookahead_gamma, gamma=1.0, record_every=0):
+    """Closed-loop episodes under the value-greedy controller on the CPU (numpy): the twin of
+    ``DevicePolicy.rollout(controller="greedy")``.  Per step the action value ``greedy_action`` returns for the state
+    with the discount ``lookahead_gamma``; the step's bookkeeping, ``gamma`` and ``record_every`` are ``rollout``'s.
+    Returns a ``RolloutResult`` of numpy arrays."""
+    tables = (value_function, action_space, bounds_low, bounds_high, grid_shape, strides, lookahead_gamma)
+    return RolloutResult(*_closed_loop(step, states, steps, gamma, record_every,
+                                       lambda live, pts: greedy_action(step, pts, *tables)[1]))
