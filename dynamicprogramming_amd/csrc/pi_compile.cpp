@@ -118,8 +118,23 @@ std::string pi::hex_float(float v) {
 
 namespace {
 
-std::string build_source(const pi_handle* h, const char* dynamics_src) {
+// `fast_first`: the plugin text is instantiated a second time, as the member functions of PiCommonEnv, against the
+// common-path-only math of include/pi_math.h (csrc/pi_sweep_kernels.hip, "common paths first").  Inside the struct the
+// three names resolve to members that pass the struct's rare flag along, so step_dynamics and its helper functions
+// share it through `this`.  The two inclusions are byte-identical copies of the caller's string.
+// Not on 6-D grids: there the exact pass, which has to hold a cell's 64 corner values like the hot one, raises the
+// kernels' register allocation past an occupancy step (25^6 evaluation: 112 -> 136 VGPRs, four waves -> three).
+// Nor for a plugin whose text holds a word that means something else inside a struct than at file scope (`__constant__`
+// data would silently become a per-instance member): such a plugin is built exactly as before.
+bool fits_struct(const char* dynamics_src) {
+    for (const char* word : {"__constant__", "__shared__", "__managed__", "static", "extern", "namespace", "template", "#include"})
+        if (std::strstr(dynamics_src, word)) return false;
+    return true;
+}
+
+std::string build_source(const pi_handle* h, const char* dynamics_src, bool fast_first) {
     std::ostringstream o;
+    fast_first = fast_first && h->D <= 4 && fits_struct(dynamics_src);
     auto dec = [](int x) { return std::to_string(x); };
     auto list = [](const auto& v, auto fmt) { return pi::brace_list(v.data(), v.size(), fmt); };
     o << "// generated by libpi_mi355 for " << pi::kArch << "\n";
@@ -139,10 +154,25 @@ std::string build_source(const pi_handle* h, const char* dynamics_src) {
     o << "#define PI_RCP_INIT " << list(h->rcp, pi::hex_float) << "\n";
     o << "#define PI_FASTDIV_INIT " << list(h->fastdiv, dec) << "\n";
     o << "#define PI_MEM_OF_INIT " << list(h->mem_of_user, dec) << "\n";
+    if (fast_first) o << "#define PI_FAST_FIRST 1\n";
     o << pi_embedded_math << "\n";
     o << "#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n";
     o << "// ---- env plugin (user string) ----\n";
     o << dynamics_src << "\n";
+    if (fast_first) {
+        o << "// ---- env plugin again: common math paths only, rare arguments flagged ----\n";
+        o << "#undef sinf\n#undef cosf\n#undef fmodf\n";
+        o << "#define sinf pi_common_sinf\n#define cosf pi_common_cosf\n#define fmodf pi_common_fmodf\n";
+        o << "struct PiCommonEnv {\n";
+        o << "unsigned int pi_rare;\n";
+        o << "__device__ __forceinline__ float pi_common_sinf(float x) { return pi_sinf_common(x, &pi_rare); }\n";
+        o << "__device__ __forceinline__ float pi_common_cosf(float x) { return pi_cosf_common(x, &pi_rare); }\n";
+        o << "__device__ __forceinline__ float pi_common_fmodf(float x, float y) { return pi_fmodf_common(x, y, &pi_rare); }\n";
+        o << dynamics_src << "\n";
+        o << "};\n";
+        o << "#undef sinf\n#undef cosf\n#undef fmodf\n";
+        o << "#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n";
+    }
     o << "// ---- sweep kernels ----\n";
     o << pi_embedded_kernels << "\n";
     // the one-launch kernels of launch-bound grids (csrc/pi_onelaunch_kernels.hip): only where the grid qualifies, so
@@ -234,7 +264,7 @@ int ensure_push_module(pi_handle* h) {
     if (h->f_eval_push) return 0;
     if (!h->compiled || h->dynamics_src.empty()) return fail("ensure_push_module: pi_compile has not run on this handle");
     std::vector<char> image;
-    const std::string src = build_source(h, h->dynamics_src.c_str()) + "// ---- fused swept-first kernel ----\n" + pi_embedded_push + "\n";
+    const std::string src = build_source(h, h->dynamics_src.c_str(), h->fast_first) + "// ---- fused swept-first kernel ----\n" + pi_embedded_push + "\n";
     if (compile_image(src, h->has_cache_dir ? h->cache_dir.c_str() : nullptr, nullptr, 0, image, nullptr)) return 1;
     if (h->device < 0) return 0;            // host-only handle: compile check only
     DeviceGuard guard(h->device);
@@ -318,7 +348,21 @@ int pi_compile(pi_handle* h, const char* dynamics_src, const char* cache_dir, ch
     if (log && log_len) log[0] = 0;
     if (!h || !dynamics_src) return fail("null argument");
     std::vector<char> image;
-    if (pi::compile_image(build_source(h, dynamics_src), cache_dir, log, log_len, image, &h->cache_hit)) return 1;
+    // Common paths first: the plugin is instantiated twice (build_source).  A plugin that is legal at file scope but not
+    // as the body of a struct (file-scope __constant__ data, static helpers, ...) is built exactly as before instead,
+    // and the log says so; a plugin that does not compile either way fails with the diagnostics of the plain form.
+    h->fast_first = fits_struct(dynamics_src);
+    if (!h->fast_first || pi::compile_image(build_source(h, dynamics_src, true), cache_dir, log, log_len, image, &h->cache_hit)) {
+        h->fast_first = false;
+        image.clear();
+        if (pi::compile_image(build_source(h, dynamics_src, false), cache_dir, log, log_len, image, &h->cache_hit)) return 1;
+        pi::fail("");
+        if (log && log_len && h->D <= 4) {
+            const std::string rest = log;
+            std::snprintf(log, log_len, "note: this plugin cannot be instantiated as member functions; its sweep kernels are built "
+                          "without the common-path-first instantiation\n%s", rest.c_str());
+        }
+    }
     h->compiled = true;
     pi::resolve_strip(h);               // the memory order is final now
     h->dynamics_src = dynamics_src;
@@ -329,7 +373,7 @@ int pi_compile(pi_handle* h, const char* dynamics_src, const char* cache_dir, ch
 
 size_t pi_kernel_source(pi_handle* h, const char* dynamics_src, char* buf, size_t buf_len) {
     if (!h || !dynamics_src) return 0;
-    std::string s = build_source(h, dynamics_src);
+    std::string s = build_source(h, dynamics_src, h->fast_first);
     if (buf && buf_len) {
         size_t k = std::min(buf_len - 1, s.size());
         std::memcpy(buf, s.data(), k);

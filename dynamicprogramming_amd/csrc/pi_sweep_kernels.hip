@@ -7,6 +7,7 @@
 //                          PI_FASTDIV_INIT>
 //     <include/pi_math.h>  + #define sinf/cosf/fmodf -> pi_*   (deterministic math)
 //     <the user's step_dynamics C string>                       (env plugin)
+//     <the same string again inside struct PiCommonEnv>         (2-D / 4-D: "common paths first" below)
 //     <this file>
 //
 // and compiles it with hipRTC (--offload-arch=gfx950 -O3 -ffp-contract=off).
@@ -163,6 +164,50 @@ __device__ __forceinline__ void pi_dynamics(const float (&sm)[PI_D], float a, fl
                   &PI_U(nm, 0), &PI_U(nm, 1), &PI_U(nm, 2), &PI_U(nm, 3), &PI_U(nm, 4), &PI_U(nm, 5), reward, done);
 #else
 #error "PI_D must be 2, 4 or 6"
+#endif
+}
+
+// ---- common paths first ------------------------------------------------------------------
+// pi_sinf / pi_cosf / pi_fmodf keep their rare paths (float64 reduction beyond |x| = 1e5, the twelve division steps of
+// the general fmodf) as straight-line code, because only such code can be hoisted out of the improvement sweep's action
+// loop — and hoisted it is, branches and all: the rare arithmetic then runs for every state and is selected away
+// (80^4: 726 instructions per state in front of the action loop, 274 without it).  So the improvement and value sweeps
+// of 2-D and 4-D grids run the plugin's SECOND instantiation (PiCommonEnv, generated by build_source in pi_compile.cpp:
+// the same text as member functions, against pi_*_common of include/pi_math.h), which performs the common path of every
+// call unconditionally and ORs "this call would have left it" into a per-lane flag; a lane whose flag is set —
+// practically never — stores nothing for that state and redoes its whole argmax with the exact instantiation
+// (pi_dynamics) in a pass of its own after the chunk loop.  Same bits by construction: a common function is the first
+// branch of the full one, the flag is that branch's condition.  The exact pass is a separate loop, not a block inside the
+// hot one, because whatever it keeps in registers would otherwise be live across the hot action loop (its packed-math
+// constants alone are ten registers on 80^4), and for the same reason the hot loop holds nothing across its action loop
+// that is only needed after it: 80^4 compiles to 78 VGPRs, six waves per SIMD (parent: 86, five).  Measured on MI355X,
+// 80^4 x 11 actions: the improvement sweep is 7 % faster than the parent's (profiles/r10/fast_first_ab.txt).  The
+// evaluation sweeps keep the exact instantiation — the same scheme made them 5 % SLOWER (3.73 -> 3.94 ms per
+// ten) — and so do 6-D grids, for registers (profiles/r10/fast_first_ab.txt, negative_results.txt).
+// A flagged lane computes garbage (any float, NaN and Inf included) until it is redone.  Its loads stay in bounds because
+// pi_locate clamps every coordinate to the grid and sends NaN down its IEEE path onto a border cell; nothing else on the
+// way uses a computed value as an index.  No ballot and no other convergent operation (profiles/r02/
+// negative_results.txt (2)), and no patched value flows through the action loop ((13) there).
+// Without PI_FAST_FIRST (a plugin that cannot be pasted into a struct) `rare` stays a constant 0 and all of this folds
+// away to the exact form.
+__device__ __forceinline__ void pi_dynamics_common(const float (&sm)[PI_D], float a, float (&nm)[PI_D],
+                                                   float* reward, bool* done, unsigned int& rare) {
+#ifdef PI_FAST_FIRST
+    PiCommonEnv env;
+    env.pi_rare = 0u;
+#if PI_D == 2
+    env.step_dynamics(PI_U(sm, 0), PI_U(sm, 1), a, &PI_U(nm, 0), &PI_U(nm, 1), reward, done);
+#elif PI_D == 4
+    env.step_dynamics(PI_U(sm, 0), PI_U(sm, 1), PI_U(sm, 2), PI_U(sm, 3), a,
+                      &PI_U(nm, 0), &PI_U(nm, 1), &PI_U(nm, 2), &PI_U(nm, 3), reward, done);
+#else
+    env.step_dynamics(PI_U(sm, 0), PI_U(sm, 1), PI_U(sm, 2), PI_U(sm, 3), PI_U(sm, 4), PI_U(sm, 5), a,
+                      &PI_U(nm, 0), &PI_U(nm, 1), &PI_U(nm, 2), &PI_U(nm, 3), &PI_U(nm, 4), &PI_U(nm, 5), reward, done);
+#endif
+    rare |= env.pi_rare;
+#else
+    (void)rare;
+    pi_dynamics(sm, a, nm, reward, done);
 #endif
 }
 
@@ -381,7 +426,22 @@ __device__ __forceinline__ float pi_backup(const float (&s)[PI_D], float a,
     }
     return reward + gamma * e;
 }
-
+// The same backup through the plugin's common-path instantiation; meaningful only where `rare` comes back clear.
+__device__ __forceinline__ float pi_backup_common(const float (&s)[PI_D], float a, const float* __restrict__ V,
+                                                  float gamma, unsigned int& rare) {
+    float ns[PI_D], reward;
+    bool done;
+    pi_dynamics_common(s, a, ns, &reward, &done, rare);
+    float e = 0.0f;
+    if (!done) {
+        unsigned int base;
+        float fr[PI_D];
+        pi_locate(ns, base, fr);                     // clamps: a flagged lane's garbage still names a cell of the grid
+        e = pi_interpolate(V, base, fr);
+    }
+    return reward + gamma * e;
+}
+// One state's evaluation backup: common paths first, the exact backup for a flagged lane.
 // ---- state coordinates -------------------------------------------------------------
 // Flat state index -> coordinates, through the LDS copy of the bin tables (the divisions are by
 // compile-time constants: a multiply-high, a shift and a multiply-add each; on gfx950 a 32-bit
@@ -808,9 +868,23 @@ pi_mask_list_kernel(const unsigned char* __restrict__ term, long long s_begin, l
 #endif
 // The greedy action of one state: argmax_a r(s, a) + gamma E[V](s'), strict '>' from -1.0e30f in ascending
 // action order (reference :262-280).  Shared by the state-order sweeps and the live-list improvement sweep.
-__device__ __forceinline__ void pi_best_action(const float (&x)[PI_D], const float* lds_tab,
-                                               const float* __restrict__ V, float gamma, int& best_out,
-                                               float& best_q_out) {
+// The exact pass of the improvement sweeps takes its coordinates through a copy per action that the compiler cannot see
+// through, so that nothing of the exact instantiation is loop-invariant: hoisted, its flattened rare paths hold ~86
+// registers across the action loop (80^4), more than the hot loop needs, and the kernel is allocated for the larger of
+// the two.  The pass is rare; it may recompute.
+__device__ __forceinline__ void pi_exact_coords(const float (&x)[PI_D], float (&c)[PI_D]) {
+#pragma unroll
+    for (int d = 0; d < PI_D; ++d) {
+        c[d] = x[d];
+        asm volatile("" : "+v"(c[d]));
+    }
+}
+// COMMON: through the plugin's common-path instantiation, `rare` collecting the flag over ALL actions (the caller
+// redoes the whole argmax with COMMON == false when it is set); otherwise the exact instantiation, `rare` untouched.
+template <bool COMMON>
+__device__ __forceinline__ void pi_argmax(const float (&x)[PI_D], const float* lds_tab,
+                                          const float* __restrict__ V, float gamma, int& best_out,
+                                          float& best_q_out, unsigned int& rare) {
     float best_q = -1.0e30f;
     int best = 0;
 #if PI_IMPROVE_REUSE
@@ -825,12 +899,18 @@ __device__ __forceinline__ void pi_best_action(const float (&x)[PI_D], const flo
     for (int a = 0; a < PI_NA; ++a) {
         float ns[PI_D], reward;
         bool done;
-        pi_dynamics(x, lds_tab[PI_TAB_ACT + a], ns, &reward, &done);
+        if (COMMON) {
+            pi_dynamics_common(x, lds_tab[PI_TAB_ACT + a], ns, &reward, &done, rare);
+        } else {
+            float c[PI_D];
+            pi_exact_coords(x, c);
+            pi_dynamics(c, lds_tab[PI_TAB_ACT + a], ns, &reward, &done);
+        }
         float e = 0.0f;
         if (!done) {
             unsigned int base;
             float fr[PI_D];
-            pi_locate(ns, base, fr);
+            pi_locate(ns, base, fr);                 // clamps: a flagged lane's garbage still names a cell of the grid
             if (base != held) {
                 pi_request_corners(V, base, vp);
                 held = base;
@@ -844,14 +924,20 @@ __device__ __forceinline__ void pi_best_action(const float (&x)[PI_D], const flo
     }
 #else
     for (int a = 0; a < PI_NA; ++a) {
-        const float q = pi_backup(x, lds_tab[PI_TAB_ACT + a], V, gamma);
+        float q;
+        if (COMMON) {
+            q = pi_backup_common(x, lds_tab[PI_TAB_ACT + a], V, gamma, rare);
+        } else {
+            float c[PI_D];
+            pi_exact_coords(x, c);
+            q = pi_backup(c, lds_tab[PI_TAB_ACT + a], V, gamma);
+        }
         if (q > best_q) { best_q = q; best = a; }
     }
 #endif
     best_out = best;
     best_q_out = best_q;
 }
-
 template <bool WRITE_V>
 __device__ __forceinline__ void pi_improve_body(const float* __restrict__ V, float* __restrict__ Vn,
                                                 int* __restrict__ policy,
@@ -870,13 +956,23 @@ __device__ __forceinline__ void pi_improve_body(const float* __restrict__ V, flo
     unsigned int lane = min(tid, (unsigned int)(min(s_end - sb, (long long)PI_BLOCK_IMPROVE) - 1));
     // the old value is only needed by the value sweep (residual, terminal copy)
     const bool need_old = WRITE_V && (delta_bits != nullptr || term != nullptr);
+#ifndef PI_FAST_FIRST
     PiStateIn nxt = pi_load_state(V, policy, term, sb, lane, need_old);
+#endif
     pi_stage_table<PI_BLOCK_IMPROVE>(tab, lds_tab);
     __syncthreads();
 
     unsigned int n_changed = 0;
     float dmax = 0.0f;
+    bool redo = false;                                               // one of this lane's states was flagged
     for (int k = 0; k < n_here; ++k) {
+#ifdef PI_FAST_FIRST
+        // no prefetch of the next chunk's inputs here: they would be held across the whole action loop (80^4: 86 VGPRs with
+        // it, 82 without), and this form is built by default only where a workgroup takes one chunk
+        const long long sb_c = s_begin + (chunk0 + k) * PI_BLOCK_IMPROVE;
+        const unsigned int lane_c = min(tid, (unsigned int)(min(s_end - sb_c, (long long)PI_BLOCK_IMPROVE) - 1));
+        const PiStateIn cur = pi_load_state(V, policy, term, sb_c, lane_c, need_old);
+#else
         const PiStateIn cur = nxt;
         const long long sb_c = sb;
         const unsigned int lane_c = lane;
@@ -885,24 +981,75 @@ __device__ __forceinline__ void pi_improve_body(const float* __restrict__ V, flo
             lane = min(tid, (unsigned int)(min(s_end - sb, (long long)PI_BLOCK_IMPROVE) - 1));
             nxt = pi_load_state(V, policy, term, sb, lane, need_old);
         }
+#endif
         const bool live = tid == lane_c;
         if (!cur.term) {
             float x[PI_D];
             pi_state_coords((unsigned int)sb_c + lane_c, lds_tab, x);
             float best_q;
             int best;
-            pi_best_action(x, lds_tab, V, gamma, best, best_q);
-            if (live) {
-                pi_store_lane(policy + sb_c, lane_c, best);
-                n_changed += (cur.action != best) ? 1u : 0u;
+            unsigned int rare = 0u;
+            pi_argmax<true>(x, lds_tab, V, gamma, best, best_q, rare);
+            redo |= rare != 0u;
+#ifdef PI_FAST_FIRST
+            // Nothing that is only needed after the action loop is held across it (80^4: 82 VGPRs with the lane held, 78
+            // without — the step between five and six waves per SIMD).  The lane is taken again from a copy of the thread
+            // index that the compiler cannot see through, the old policy entry is read again.
+            unsigned int tid_s = tid;
+            asm volatile("" : "+v"(tid_s));
+            const unsigned int lane_s = min(tid_s, (unsigned int)(min(s_end - sb_c, (long long)PI_BLOCK_IMPROVE) - 1));
+            const bool live_s = tid_s == lane_s;
+#else
+            const unsigned int lane_s = lane_c;
+            const bool live_s = live;
+#endif
+            if (live_s && rare == 0u) {
+#ifdef PI_FAST_FIRST
+                const int old_action = __builtin_nontemporal_load(pi_lane_ptr(policy + sb_c, lane_s));
+#else
+                const int old_action = cur.action;
+#endif
+                pi_store_lane(policy + sb_c, lane_s, best);
+                n_changed += (old_action != best) ? 1u : 0u;
                 if (WRITE_V) {
-                    pi_store_lane(Vn + sb_c, lane_c, best_q);
+                    pi_store_lane(Vn + sb_c, lane_s, best_q);
                     const float dlt = fabsf(best_q - cur.v_old);
                     dmax = dlt > dmax ? dlt : dmax;
                 }
             }
         } else if (WRITE_V && live) {
             pi_store_lane(Vn + sb_c, lane_c, cur.v_old);
+        }
+    }
+    // The exact pass (see "common paths first"): a lane one of whose states was flagged walks ALL its chunks again and
+    // redoes the whole argmax with the exact instantiation.  The hot pass stored nothing for a flagged state, so its policy
+    // entry is still the old one and counts as changed here if it changes; an unflagged state of the same lane reads back
+    // the action the hot pass stored, finds the same one again and counts nothing twice.
+    if (__builtin_expect(redo, 0)) {
+        for (int k = 0; k < n_here; ++k) {
+            const long long sb_k = s_begin + (chunk0 + k) * PI_BLOCK_IMPROVE;
+            const unsigned int lane_k = min(tid, (unsigned int)(min(s_end - sb_k, (long long)PI_BLOCK_IMPROVE) - 1));
+            const PiStateIn cur = pi_load_state(V, policy, term, sb_k, lane_k, need_old);
+            const bool live = tid == lane_k;
+            if (!cur.term) {
+                float x[PI_D];
+                pi_state_coords((unsigned int)sb_k + lane_k, lds_tab, x);
+                float best_q;
+                int best;
+                unsigned int unused = 0u;
+                pi_argmax<false>(x, lds_tab, V, gamma, best, best_q, unused);
+                if (live) {
+                    pi_store_lane(policy + sb_k, lane_k, best);
+                    n_changed += (cur.action != best) ? 1u : 0u;
+                    if (WRITE_V) {
+                        pi_store_lane(Vn + sb_k, lane_k, best_q);
+                        const float dlt = fabsf(best_q - cur.v_old);
+                        dmax = dlt > dmax ? dlt : dmax;
+                    }
+                }
+            } else if (WRITE_V && live) {
+                pi_store_lane(Vn + sb_k, lane_k, cur.v_old);
+            }
         }
     }
     if (changed != nullptr) pi_wave_sum_to<PI_BLOCK_IMPROVE>(n_changed, changed);
@@ -940,6 +1087,7 @@ pi_improve_live_kernel(const float* __restrict__ V, int* __restrict__ policy, co
     pi_stage_table<PI_BLOCK_IMPROVE>(tab, lds_tab);
     __syncthreads();
     unsigned int n_changed = 0;
+    bool redo = false;
     for (int k = 0; k < n_here; ++k) {
         const unsigned int s = s_cur, lane_c = lane_cur;
         if (k + 1 < n_here) {
@@ -951,10 +1099,29 @@ pi_improve_live_kernel(const float* __restrict__ V, int* __restrict__ policy, co
         pi_state_coords(s, lds_tab, x);
         float best_q;
         int best;
-        pi_best_action(x, lds_tab, V, gamma, best, best_q);
-        if (tid == lane_c) {
+        unsigned int rare = 0u;
+        pi_argmax<true>(x, lds_tab, V, gamma, best, best_q, rare);
+        redo |= rare != 0u;
+        if (tid == lane_c && rare == 0u) {
             policy[s] = best;
             n_changed += (old_action != best) ? 1u : 0u;
+        }
+    }
+    if (__builtin_expect(redo, 0)) {                            // the exact pass, as in pi_improve_body
+        for (int k = 0; k < n_here; ++k) {
+            const unsigned int lane_k = lane_of(k);
+            const unsigned int s = entry(k, lane_k);
+            const int old_action = __builtin_nontemporal_load(policy + s);
+            float x[PI_D];
+            pi_state_coords(s, lds_tab, x);
+            float best_q;
+            int best;
+            unsigned int unused = 0u;
+            pi_argmax<false>(x, lds_tab, V, gamma, best, best_q, unused);
+            if (tid == lane_k) {
+                policy[s] = best;
+                n_changed += (old_action != best) ? 1u : 0u;
+            }
         }
     }
     if (changed != nullptr) pi_wave_sum_to<PI_BLOCK_IMPROVE>(n_changed, changed);

@@ -27,6 +27,10 @@
  *   pi_fmodf          : exact (the IEEE remainder-toward-zero is exactly
  *                       representable), bit-identical to glibc fmodf.
  *
+ * pi_sinf_common / pi_cosf_common / pi_fmodf_common (at the end) are the first branch of each function alone, with a
+ * flag for the arguments that would have left it; the improvement sweeps run them first and fall back to the full
+ * functions per state (tests/test_pi_math_common_path.py).
+ *
  * The header is plain C99/C++ and HIP device code at once: PI_MATH_FN expands
  * to `__device__ __forceinline__` under hipcc/hipRTC and `static inline` on
  * the host.
@@ -191,6 +195,49 @@ PI_MATH_FN float pi_fmodf(float x, float y) {
         }
         return PI_MATH_BITS_U2F(PI_MATH_BITS_F2U(as) | sx);
     }
+}
+
+/*
+ * Common-path entry points (the sweep kernels' hot instantiation of the plugin, csrc/pi_sweep_kernels.hip).
+ *
+ * pi_sinf / pi_cosf / pi_fmodf above keep their rare paths as straight-line code so that the action-independent
+ * calls of a plugin can be hoisted out of the improvement sweep's action loop; the price is that a hoisted call
+ * executes the rare arithmetic (float64 reduction, twelve division steps) for every state and selects it away.
+ * The functions below perform exactly the operations of the FIRST branch of their full counterpart, whatever the
+ * argument, and OR "the full function would not have taken that branch" into *rare (no branch; the predicate is
+ * the full function's `if` condition, unchanged).  So wherever *rare stays 0 the result is the full function's bit
+ * for bit, and a caller that sees it set recomputes with the full functions.  For an argument outside the common
+ * path the returned value is meaningless (possibly NaN or Inf) but every operation is still a plain IEEE one.
+ */
+PI_MATH_FN float pi_sinf_common(float x, unsigned int* rare) {
+    *rare |= (unsigned int)!(fabsf(x) <= PI__FAST_MAX);
+    float t = fmaf(x, PI__ONE_OVER_PI, PI__MAGIC);
+    float k = t - PI__MAGIC;
+    float r = fmaf(-k, PI__PI_HI, x);
+    r = fmaf(-k, PI__PI_MID, r);
+    r = fmaf(-k, PI__PI_LO, r);
+    return PI_MATH_BITS_U2F(PI_MATH_BITS_F2U(pi__sin_poly(r)) ^ (PI_MATH_BITS_F2U(t) << 31));
+}
+
+PI_MATH_FN float pi_cosf_common(float x, unsigned int* rare) {
+    *rare |= (unsigned int)!(fabsf(x) <= PI__FAST_MAX);
+    float t = fmaf(x, PI__ONE_OVER_PI, -0.5f) + PI__MAGIC;
+    float k = t - PI__MAGIC;
+    float h = fmaf(2.0f, k, 1.0f);
+    float r = fmaf(h, PI__PIO2_HI, -x);
+    r = fmaf(h, PI__PIO2_MID, r);
+    r = fmaf(h, PI__PIO2_LO, r);
+    return PI_MATH_BITS_U2F(PI_MATH_BITS_F2U(pi__sin_poly(r)) ^ (PI_MATH_BITS_F2U(t) << 31));
+}
+
+PI_MATH_FN float pi_fmodf_common(float x, float y, unsigned int* rare) {
+    const unsigned int ux = PI_MATH_BITS_F2U(x), uy = PI_MATH_BITS_F2U(y);
+    const unsigned int sx = ux & 0x80000000u;
+    const unsigned int ax = ux & 0x7FFFFFFFu, ay = uy & 0x7FFFFFFFu;
+    const float fx = PI_MATH_BITS_U2F(ax), fy = PI_MATH_BITS_U2F(ay);
+    *rare |= (unsigned int)!((ay - 0x00800000u < 0x7E800000u) & (fx < 2.0f * fy));
+    const float r = fx - (fx >= fy ? fy : 0.0f);
+    return PI_MATH_BITS_U2F(PI_MATH_BITS_F2U(r) | sx);
 }
 
 #endif /* PI_MATH_H_ */
