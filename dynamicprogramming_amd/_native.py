@@ -139,6 +139,7 @@ class Info(enum.IntEnum):
     WHOLE_RUNS = 33
     WHOLE_RUN_AVAILABLE = 34
     STRIP_STATES = 35
+    PAIR_TABLE = 37
 
 
 class Option(enum.IntEnum):
@@ -152,6 +153,7 @@ class Option(enum.IntEnum):
     KEEP_LIVE_LIST = 6
     STRIP_STATES = 7
     XCD_RUN_FAILED = 8
+    PAIR_TABLE = 9
 
 
 class XcdFailure(enum.IntEnum):

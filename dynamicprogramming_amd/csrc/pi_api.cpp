@@ -5,6 +5,7 @@
 #include "pi_internal.h"
 
 #include <algorithm>
+#include <cstdio>
 
 namespace pi {
 
@@ -33,6 +34,17 @@ void resolve_strip(pi_handle* h) {
         const int64_t sub = h->n_states / ((int64_t)h->shape[0] * h->shape[1]);
         h->strip_states = sub * std::max<int64_t>(1, ((int64_t(1) << 21) + sub / 2) / sub);
     }
+}
+
+// Pair table of the improvement sweeps (csrc/pi_sweep_kernels.hip, PI_PAIR_TABLE): which units get its kernels.  The grid
+// has to admit it — 4-D (in 6-D the doubled footprint loses, profiles/r03/negative_results.txt (18); 2-D has one pair load
+// per backup as it is) and 8 n < 2^32, so that the table's byte offsets stay 32-bit —, and the caller or the library has to
+// want it: PI_OPTION_PAIR_TABLE 1, or -1 (the default) on grids of at least kPairTableMinStates states, the class of grids
+// on which it was measured to pay (profiles/r11/pair_table_ab.txt).
+constexpr int64_t kPairTableMinStates = int64_t(1) << 24;
+bool pair_table_wanted(const pi_handle* h) {
+    if (h->D != 4 || h->n_states * 8 >= (int64_t(1) << 32)) return false;
+    return h->pair_mode == 1 || (h->pair_mode < 0 && h->n_states >= kPairTableMinStates);
 }
 
 void drop_graphs(pi_handle* h) {
@@ -100,7 +112,7 @@ void free_device_state(pi_handle* h) {
     if (h->module) (void)hipModuleUnload(h->module);
     if (h->module_push) (void)hipModuleUnload(h->module_push);
     for (void* p : {(void*)h->d_tab, (void*)h->d_slots, (void*)h->d_live, (void*)h->d_eval_list, (void*)h->d_eval_cursor,
-                    h->d_flow, h->d_xcd})
+                    h->d_flow, h->d_xcd, (void*)h->d_pairs})
         if (p) (void)hipFree(p);
 }
 
@@ -194,6 +206,27 @@ int build_eval_graph(pi_handle* h, float* Va, float* Vb, const int32_t* policy, 
         (void)hipGetLastError();
         return fail("could not build the evaluation-sweep graph");
     }
+    return 0;
+}
+
+// The pair table of `V` for a whole-grid improvement sweep on `st`, in *out: packed on EVERY call — callers write V
+// behind the library's back, so nothing is remembered from one call to the next.  *out stays null where the sweep takes
+// the plain kernels: the unit has no table kernels, the option says no, or the 8 n-byte buffer could not be had (said
+// once on stderr, never tried again).  A pack that cannot be launched is an error like any other launch.
+int pack_pair_table(pi_handle* h, const float* V, hipStream_t st, const float** out) {
+    *out = nullptr;
+    if (!h->pair_built || !pair_table_wanted(h) || h->pair_alloc_failed) return 0;
+    if (!h->d_pairs && hipMalloc((void**)&h->d_pairs, (size_t)h->n_states * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        h->d_pairs = nullptr;
+        h->pair_alloc_failed = true;
+        std::fprintf(stderr, "libpi_mi355: no memory for the %lld-byte pair table of the improvement sweeps; they read V\n",
+                     (long long)h->n_states * 8);
+        return 0;
+    }
+    const unsigned blocks = (unsigned)((h->n_states + kProbeBlock - 1) / kProbeBlock);
+    PI_HIP(launch(h->f_pack_pairs, {blocks, 1}, kProbeBlock, st, V, h->d_pairs));
+    *out = h->d_pairs;
     return 0;
 }
 
@@ -416,6 +449,11 @@ int pi_improve_sweep(pi_handle* h, const float* V, int32_t* policy, const uint8_
     const float* tab = h->d_tab;
     unsigned int* cslots = d_changed ? changed_slots(h) : nullptr;
     Sched sc;
+    // whole-grid sweeps gather from the pair table of V where the unit has the kernels; a sub-range (the shard of a rank,
+    // pi_comm.cpp) reads V: packing all of V for a shard's worth of work cannot pay
+    const float* pairs = nullptr;
+    if (s_begin == 0 && s_end == h->n_states && pack_pair_table(h, V, st, &pairs)) return 1;
+    h->pair_last = pairs != nullptr;
     if (pi::live_usable(h, term, s_begin, s_end)) {
         // the improvement sweep never touches terminal states: visit the listed live ones only (pi_prepare_mask)
         int64_t first = 0, cnt = 0;
@@ -423,14 +461,22 @@ int pi_improve_sweep(pi_handle* h, const float* V, int32_t* policy, const uint8_
         if (cnt > 0) {
             const pi::Grid2 blocks = plan_launch(h, h->block_improve, first, cnt, pi::live_list_total(h, h->live_count),
                                                 h->cpw_improve, &sc);
-            PI_HIP(launch(h->f_improve_live, blocks, h->block_improve, st, V, policy, (const int32_t*)(h->d_live + first), tab,
-                          (long long)cnt, gamma, cslots, sc));
+            if (pairs)
+                PI_HIP(launch(h->f_improve_live_pairs, blocks, h->block_improve, st, V, pairs, policy,
+                              (const int32_t*)(h->d_live + first), tab, (long long)cnt, gamma, cslots, sc));
+            else
+                PI_HIP(launch(h->f_improve_live, blocks, h->block_improve, st, V, policy, (const int32_t*)(h->d_live + first), tab,
+                              (long long)cnt, gamma, cslots, sc));
         }
         return pi::finalize(h, nullptr, d_changed, st);
     }
     const pi::Grid2 blocks = plan_launch(h, h->block_improve, s_begin, s_end - s_begin, h->n_states, h->cpw_improve, &sc);
-    PI_HIP(launch(h->f_improve, blocks, h->block_improve, st, V, policy, term, tab, (long long)s_begin, (long long)s_end, gamma,
-                  cslots, sc));
+    if (pairs)
+        PI_HIP(launch(h->f_improve_pairs, blocks, h->block_improve, st, V, pairs, policy, term, tab, (long long)s_begin,
+                      (long long)s_end, gamma, cslots, sc));
+    else
+        PI_HIP(launch(h->f_improve, blocks, h->block_improve, st, V, policy, term, tab, (long long)s_begin, (long long)s_end, gamma,
+                      cslots, sc));
     return pi::finalize(h, nullptr, d_changed, st);
 }
 
@@ -548,6 +594,20 @@ int pi_set_option(pi_handle* h, int what, int64_t value) {
                 return fail("option 8 takes 1 (count a failed whole run) or 2 (and switch the XCD-local kernel off)");
             if (++h->xcd_failed >= 2 || value == PI_XCD_FAILURE_SWITCH_OFF) h->xcd_off = true;
             return 0;
+        case PI_OPTION_PAIR_TABLE:
+            // the improvement sweeps' pair table: -1 = the library's choice for the grid, 0 = off, 1 = on where the grid
+            // admits it (4-D, 8 n < 2^32).  Which kernels a unit holds is settled when pi_compile builds it, so a handle
+            // whose unit was built without them cannot be switched on afterwards; switching off always works.
+            if (value < -1 || value > 1) return fail("the pair table option takes -1 (auto), 0 (off) or 1 (on)");
+            {
+                const int before = h->pair_mode;
+                h->pair_mode = (int)value;
+                if (h->compiled && !h->pair_built && pair_table_wanted(h)) {
+                    h->pair_mode = before;
+                    return fail("the pair table must be switched on before pi_compile: this handle's kernels were built without it");
+                }
+            }
+            return 0;
         default:
             return fail("unknown option");
     }
@@ -602,6 +662,7 @@ int64_t pi_info(pi_handle* h, int what) {
         case PI_INFO_WHOLE_RUNS: return h->whole_runs;
         case PI_INFO_WHOLE_RUN_AVAILABLE: return (h->f_run_resident && h->use_resident) || (h->f_xcd && !h->xcd_off) ? 1 : 0;
         case PI_INFO_STRIP_STATES: return h->strip_states;
+        case PI_INFO_PAIR_TABLE: return h->pair_last ? 1 : 0;
         default:
             if (what >= PI_INFO_RECIPROCAL_DIV && what < PI_INFO_RECIPROCAL_DIV + h->D)
                 return h->fastdiv[what - PI_INFO_RECIPROCAL_DIV];

@@ -154,6 +154,9 @@ std::string build_source(const pi_handle* h, const char* dynamics_src, bool fast
     o << "#define PI_RCP_INIT " << list(h->rcp, pi::hex_float) << "\n";
     o << "#define PI_FASTDIV_INIT " << list(h->fastdiv, dec) << "\n";
     o << "#define PI_MEM_OF_INIT " << list(h->mem_of_user, dec) << "\n";
+    // the pack kernel and the improvement kernels that read the pair table (PI_OPTION_PAIR_TABLE): what pi_compile decided
+    // once it has run, what it would decide now before
+    if (h->compiled ? h->pair_built : pi::pair_table_wanted(h)) o << "#define PI_PAIR_TABLE 1\n";
     if (fast_first) o << "#define PI_FAST_FIRST 1\n";
     o << pi_embedded_math << "\n";
     o << "#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n";
@@ -207,6 +210,12 @@ int load_module(pi_handle* h, const std::vector<char>& image) {
     PI_HIP(hipModuleGetFunction(&h->f_improve, h->module, "pi_improve_sweep_kernel"));
     PI_HIP(hipModuleGetFunction(&h->f_improve_live, h->module, "pi_improve_live_kernel"));
     PI_HIP(hipModuleGetFunction(&h->f_value, h->module, "pi_value_sweep_kernel"));
+    h->f_pack_pairs = h->f_improve_pairs = h->f_improve_live_pairs = nullptr;
+    if (h->pair_built) {
+        PI_HIP(hipModuleGetFunction(&h->f_pack_pairs, h->module, "pi_pack_pairs_kernel"));
+        PI_HIP(hipModuleGetFunction(&h->f_improve_pairs, h->module, "pi_improve_sweep_pairs_kernel"));
+        PI_HIP(hipModuleGetFunction(&h->f_improve_live_pairs, h->module, "pi_improve_live_pairs_kernel"));
+    }
     PI_HIP(hipModuleGetFunction(&h->f_finalize, h->module, "pi_finalize_kernel"));
     PI_HIP(hipModuleGetFunction(&h->f_reach_planes, h->module, "pi_reach_planes_kernel"));
     PI_HIP(hipModuleGetFunction(&h->f_reach_units, h->module, "pi_reach_units_kernel"));
@@ -348,6 +357,7 @@ int pi_compile(pi_handle* h, const char* dynamics_src, const char* cache_dir, ch
     if (log && log_len) log[0] = 0;
     if (!h || !dynamics_src) return fail("null argument");
     std::vector<char> image;
+    h->pair_built = pi::pair_table_wanted(h);      // fixed for this unit: an option set later does not change what was built
     // Common paths first: the plugin is instantiated twice (build_source).  A plugin that is legal at file scope but not
     // as the body of a struct (file-scope __constant__ data, static helpers, ...) is built exactly as before instead,
     // and the log says so; a plugin that does not compile either way fails with the diagnostics of the plain form.

@@ -179,6 +179,15 @@ struct pi_handle {
     int64_t strip_states = 0;
     int64_t strip_mode = -1;             // -1 the library's choice (resolve_strip), 0 off, > 0 states per period as given
     int vgpr_eval = -1, vgpr_improve = -1;
+    // Pair table of the improvement sweeps (PI_OPTION_PAIR_TABLE; csrc/pi_sweep_kernels.hip, PI_PAIR_TABLE).  pair_mode: -1 the
+    // library's choice (pi::pair_table_wanted), 0 off, 1 on where the grid admits it.  pair_built: the unit pi_compile built
+    // holds the pack kernel and the two table kernels.  d_pairs: the 8 n-byte table (owned), allocated by the first sweep
+    // that takes the path; pair_alloc_failed: that allocation failed once — the plain path from then on, logged once.
+    // pair_last: the last improvement sweep read the table (PI_INFO_PAIR_TABLE).
+    int pair_mode = -1;
+    bool pair_built = false, pair_alloc_failed = false, pair_last = false;
+    hipFunction_t f_pack_pairs = nullptr, f_improve_pairs = nullptr, f_improve_live_pairs = nullptr;
+    float* d_pairs = nullptr;
     bool cache_hit = false;
     bool debug_bounds = false;           // PI_MI355_DEBUG=1 at pi_create: checked kernels (pi_debug_report)
     bool use_graphs = true;
@@ -321,6 +330,7 @@ void drop_eval_list(pi_handle* h);     // the policy may have changed: forget th
 void release_comm(pi_handle* h);      // pi_comm.cpp: tears down the transport and the exchange plan
 void drop_p2p_pending(pi_handle* h);  // pi_p2p.cpp
 void drop_graphs(pi_handle* h);       // the cached graphs hold launch geometry and kernel handles: forget them
+bool pair_table_wanted(const pi_handle* h);   // pi_api.cpp: does this handle's unit get the pair-table kernels?
 void resolve_strip(pi_handle* h);     // strip_mode -> strip_states (the library's choice needs the final memory order)
 bool validate_fast_division(float span);   // pi_compile.cpp: is the reciprocal division exact for this divisor?
 // hipRTC (gfx950, -O3 -ffp-contract=off) or the on-disk code-object cache -> image of one translation unit

@@ -4,7 +4,7 @@
 //                                                      travelling between workgroups as tagged granules
 //   pi_xcd_kernel (+ pi_xcd_finish_kernel)             2-D grids of ~4 000 to 2^16 states on the CUs of ONE XCD: an
 //                                                      evaluation or the whole run()
-// A device-code TEMPLATE like pi_sweep_kernels.hip and never compiled on its own: libpi_mi355.so (pi_api.cpp, build_source)
+// A device-code TEMPLATE like pi_sweep_kernels.hip and never compiled on its own: libpi_mi355.so (pi_compile.cpp, build_source)
 // appends it to the translation unit <defines> + pi_math.h + <step_dynamics> + pi_sweep_kernels.hip — whose helpers
 // (pi_state_coords, pi_dynamics, pi_locate, pi_corner_weights, pi_stage_table, pi_wave_max, ...) it uses — ONLY for handles
 // whose grid qualifies (PI_RESIDENT_K > 0, PI_FLOW or PI_XCD among the generated defines): the units of the big grids the

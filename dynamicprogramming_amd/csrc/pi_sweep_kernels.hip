@@ -1,7 +1,7 @@
 // pi_sweep_kernels.hip — Bellman-backup sweep kernels for gfx950 (MI355X, CDNA4).
 //
 // This is a device-code TEMPLATE, never compiled on its own.  libpi_mi355.so
-// (pi_api.cpp) builds one translation unit per (grid, action count, env):
+// (pi_compile.cpp, build_source) builds one translation unit per (grid, action count, env):
 //
 //     <generated #defines: PI_D, PI_NA, PI_GRID_INIT, PI_LO_INIT, PI_SPAN_INIT, PI_RCP_INIT,
 //                          PI_FASTDIV_INIT>
@@ -44,7 +44,7 @@
 //   * the interpolation's IEEE divisions (s - lo) / (hi - lo) have a per-dimension constant
 //     divisor: they run as a * rcp, one residual fma and one correction fma — bit-identical to
 //     the IEEE quotient for every dividend in [2^-40, 2^40], which the host PROVES per divisor
-//     by exhaustive enumeration before it enables the path (pi_api.cpp, validate_fast_division);
+//     by exhaustive enumeration before it enables the path (pi_compile.cpp, validate_fast_division);
 //     lanes outside that range take the IEEE division; on the proven path the border clamp is the
 //     fma's free output modifier instead of a min and a max;
 //   * every address is a 32-bit byte offset from a scalar base (global_load ... v, s[..]), so
@@ -382,6 +382,36 @@ __device__ __forceinline__ void pi_request_corners(const float* __restrict__ V, 
         vp[m | kNear] = *reinterpret_cast<const PiPairU*>(p + (long)PI_GRID.stride[PI_D - 2] * 4);
     }
 }
+// The same corners from the PAIR TABLE of the improvement sweeps (PI_PAIR_TABLE below): P[2 s] = V[s], P[2 s + 1] =
+// V[s + stride of the second-to-last memory dimension], so the four corners of a cell along the last two memory
+// dimensions are 16 adjacent bytes, 8-byte aligned — {V[s], V[s + row], V[s + 1], V[s + 1 + row]} — and come as ONE
+// global_load_dwordx4 where pi_request_corners issues two dwordx2: the vector-memory path charges per instruction.
+// They land in the slots pi_request_corners fills, so everything behind the loads is the same code on the same values.
+typedef float PiFloat4 __attribute__((ext_vector_type(4)));
+typedef PiFloat4 PiFloat4U __attribute__((aligned(8)));
+constexpr bool PI_PAIR_OFF32 = PI_GRID.n * 8 < (1LL << 32);
+__device__ __forceinline__ void pi_request_corners_pairs(const float* __restrict__ P, unsigned int base,
+                                                         PiPair (&vp)[PI_NPAIR]) {
+    constexpr int kNear = 1 << (PI_D - 2);
+#pragma unroll
+    for (int m = 0; m < kNear; ++m) {
+        int far = 0;
+#pragma unroll
+        for (int d = 0; d < PI_D - 2; ++d) far += ((m >> d) & 1) * PI_GRID.stride[d];
+        const char* p;
+        if (PI_PAIR_OFF32) p = reinterpret_cast<const char*>(P) + (base * 8u + (unsigned int)far * 8u);
+        else p = reinterpret_cast<const char*>(P + 2ull * ((unsigned long long)base + (unsigned long long)far));
+        const PiFloat4 q = *reinterpret_cast<const PiFloat4U*>(p);
+        vp[m] = PiPair{q.x, q.z};
+        vp[m | kNear] = PiPair{q.y, q.w};
+    }
+}
+// PAIRS: `V` is the pair table of V, not V.
+template <bool PAIRS>
+__device__ __forceinline__ void pi_request(const float* __restrict__ V, unsigned int base, PiPair (&vp)[PI_NPAIR]) {
+    if (PAIRS) pi_request_corners_pairs(V, base, vp);
+    else pi_request_corners(V, base, vp);
+}
 __device__ __forceinline__ float pi_combine_corners(const PiPair (&vp)[PI_NPAIR], const float (&fr)[PI_D]) {
     constexpr int kLast = 1 << (PI_D - 1);
     float w[PI_C];
@@ -402,16 +432,18 @@ __device__ __forceinline__ float pi_combine_corners(const PiPair (&vp)[PI_NPAIR]
 // behind waves that are still in their arithmetic.  Pure scheduling, results unchanged; measured on one
 // box: 25^6 evaluation 4.65 -> 4.20 ms, improvement 9.25 -> 9.03 ms (swing-up 8.06 -> 7.90 / 37.6 -> 36.4),
 // 80^4 and 50^4 unchanged (profiles/r03/negative_results.txt (12) lists the variants that lose).
+template <bool PAIRS = false>
 __device__ __forceinline__ float pi_interpolate(const float* __restrict__ V, unsigned int base,
                                                 const float (&fr)[PI_D]) {
     PiPair vp[PI_NPAIR];
-    pi_request_corners(V, base, vp);
+    pi_request<PAIRS>(V, base, vp);
     __builtin_amdgcn_s_setprio(1);
     const float e = pi_combine_corners(vp, fr);
     __builtin_amdgcn_s_setprio(0);
     return e;
 }
 
+template <bool PAIRS = false>
 __device__ __forceinline__ float pi_backup(const float (&s)[PI_D], float a,
                                            const float* __restrict__ V, float gamma) {
     float ns[PI_D], reward;
@@ -422,11 +454,12 @@ __device__ __forceinline__ float pi_backup(const float (&s)[PI_D], float a,
         unsigned int base;
         float fr[PI_D];
         pi_locate(ns, base, fr);
-        e = pi_interpolate(V, base, fr);
+        e = pi_interpolate<PAIRS>(V, base, fr);
     }
     return reward + gamma * e;
 }
 // The same backup through the plugin's common-path instantiation; meaningful only where `rare` comes back clear.
+template <bool PAIRS = false>
 __device__ __forceinline__ float pi_backup_common(const float (&s)[PI_D], float a, const float* __restrict__ V,
                                                   float gamma, unsigned int& rare) {
     float ns[PI_D], reward;
@@ -437,7 +470,7 @@ __device__ __forceinline__ float pi_backup_common(const float (&s)[PI_D], float 
         unsigned int base;
         float fr[PI_D];
         pi_locate(ns, base, fr);                     // clamps: a flagged lane's garbage still names a cell of the grid
-        e = pi_interpolate(V, base, fr);
+        e = pi_interpolate<PAIRS>(V, base, fr);
     }
     return reward + gamma * e;
 }
@@ -881,7 +914,8 @@ __device__ __forceinline__ void pi_exact_coords(const float (&x)[PI_D], float (&
 }
 // COMMON: through the plugin's common-path instantiation, `rare` collecting the flag over ALL actions (the caller
 // redoes the whole argmax with COMMON == false when it is set); otherwise the exact instantiation, `rare` untouched.
-template <bool COMMON>
+// PAIRS: `V` is the pair table of V (pi_request_corners_pairs), in every branch below.
+template <bool COMMON, bool PAIRS = false>
 __device__ __forceinline__ void pi_argmax(const float (&x)[PI_D], const float* lds_tab,
                                           const float* __restrict__ V, float gamma, int& best_out,
                                           float& best_q_out, unsigned int& rare) {
@@ -912,7 +946,7 @@ __device__ __forceinline__ void pi_argmax(const float (&x)[PI_D], const float* l
             float fr[PI_D];
             pi_locate(ns, base, fr);                 // clamps: a flagged lane's garbage still names a cell of the grid
             if (base != held) {
-                pi_request_corners(V, base, vp);
+                pi_request<PAIRS>(V, base, vp);
                 held = base;
             }
             __builtin_amdgcn_s_setprio(1);
@@ -926,11 +960,11 @@ __device__ __forceinline__ void pi_argmax(const float (&x)[PI_D], const float* l
     for (int a = 0; a < PI_NA; ++a) {
         float q;
         if (COMMON) {
-            q = pi_backup_common(x, lds_tab[PI_TAB_ACT + a], V, gamma, rare);
+            q = pi_backup_common<PAIRS>(x, lds_tab[PI_TAB_ACT + a], V, gamma, rare);
         } else {
             float c[PI_D];
             pi_exact_coords(x, c);
-            q = pi_backup(c, lds_tab[PI_TAB_ACT + a], V, gamma);
+            q = pi_backup<PAIRS>(c, lds_tab[PI_TAB_ACT + a], V, gamma);
         }
         if (q > best_q) { best_q = q; best = a; }
     }
@@ -938,8 +972,10 @@ __device__ __forceinline__ void pi_argmax(const float (&x)[PI_D], const float* l
     best_out = best;
     best_q_out = best_q;
 }
-template <bool WRITE_V>
-__device__ __forceinline__ void pi_improve_body(const float* __restrict__ V, float* __restrict__ Vn,
+// PAIRS: the action loops gather from `P`, the pair table of V; `P` is not looked at otherwise.
+template <bool WRITE_V, bool PAIRS = false>
+__device__ __forceinline__ void pi_improve_body(const float* __restrict__ V, const float* __restrict__ P,
+                                                float* __restrict__ Vn,
                                                 int* __restrict__ policy,
                                                 const unsigned char* __restrict__ term,
                                                 const float* __restrict__ tab, long long s_begin,
@@ -989,7 +1025,7 @@ __device__ __forceinline__ void pi_improve_body(const float* __restrict__ V, flo
             float best_q;
             int best;
             unsigned int rare = 0u;
-            pi_argmax<true>(x, lds_tab, V, gamma, best, best_q, rare);
+            pi_argmax<true, PAIRS>(x, lds_tab, PAIRS ? P : V, gamma, best, best_q, rare);
             redo |= rare != 0u;
 #ifdef PI_FAST_FIRST
             // Nothing that is only needed after the action loop is held across it (80^4: 82 VGPRs with the lane held, 78
@@ -1037,7 +1073,7 @@ __device__ __forceinline__ void pi_improve_body(const float* __restrict__ V, flo
                 float best_q;
                 int best;
                 unsigned int unused = 0u;
-                pi_argmax<false>(x, lds_tab, V, gamma, best, best_q, unused);
+                pi_argmax<false, PAIRS>(x, lds_tab, PAIRS ? P : V, gamma, best, best_q, unused);
                 if (live) {
                     pi_store_lane(policy + sb_k, lane_k, best);
                     n_changed += (cur.action != best) ? 1u : 0u;
@@ -1061,15 +1097,20 @@ pi_improve_sweep_kernel(const float* __restrict__ V, int* __restrict__ policy,
                         const unsigned char* __restrict__ term, const float* __restrict__ tab,
                         long long s_begin, long long s_end, float gamma,
                         unsigned int* __restrict__ changed, PiSched sc) {
-    pi_improve_body<false>(V, nullptr, policy, term, tab, s_begin, s_end, gamma, nullptr, changed, sc);
+    pi_improve_body<false>(V, nullptr, nullptr, policy, term, tab, s_begin, s_end, gamma, nullptr, changed, sc);
 }
 
 // The improvement sweep over the LIVE states only (the list of pi_prepare_mask; see pi_eval_live_kernel): an
 // improvement sweep never touches terminal states (:253), so every whole-grid launch may take this form.
-extern "C" __global__ void __launch_bounds__(PI_BLOCK_IMPROVE)
-pi_improve_live_kernel(const float* __restrict__ V, int* __restrict__ policy, const int* __restrict__ live,
-                       const float* __restrict__ tab, long long n_live, float gamma,
-                       unsigned int* __restrict__ changed, PiSched sc) {
+// G: what the action loops gather from — V, or (PAIRS) its pair table.  This kernel keeps the next chunk's entry and the
+// state's old action in registers across the action loop (80^4: 87 VGPRs, five waves): the form of pi_improve_body that
+// holds nothing across it (79 VGPRs, six waves) was tried here and is SLOWER, cartpole 40^4 0.0276 -> 0.0304 ms
+// (profiles/r11/negative_results.txt (2)).
+template <bool PAIRS>
+__device__ __forceinline__ void pi_improve_live_body(const float* __restrict__ G, int* __restrict__ policy,
+                                                     const int* __restrict__ live, const float* __restrict__ tab,
+                                                     long long n_live, float gamma, unsigned int* __restrict__ changed,
+                                                     PiSched sc) {
     __shared__ float lds_tab[PI_GRID.tab_len];
     long long chunk0, n_chunks;
     if (!pi_first_chunk<PI_BLOCK_IMPROVE>(n_live, sc, chunk0, n_chunks)) return;
@@ -1100,7 +1141,7 @@ pi_improve_live_kernel(const float* __restrict__ V, int* __restrict__ policy, co
         float best_q;
         int best;
         unsigned int rare = 0u;
-        pi_argmax<true>(x, lds_tab, V, gamma, best, best_q, rare);
+        pi_argmax<true, PAIRS>(x, lds_tab, G, gamma, best, best_q, rare);
         redo |= rare != 0u;
         if (tid == lane_c && rare == 0u) {
             policy[s] = best;
@@ -1117,7 +1158,7 @@ pi_improve_live_kernel(const float* __restrict__ V, int* __restrict__ policy, co
             float best_q;
             int best;
             unsigned int unused = 0u;
-            pi_argmax<false>(x, lds_tab, V, gamma, best, best_q, unused);
+            pi_argmax<false, PAIRS>(x, lds_tab, G, gamma, best, best_q, unused);
             if (tid == lane_k) {
                 policy[s] = best;
                 n_changed += (old_action != best) ? 1u : 0u;
@@ -1126,6 +1167,53 @@ pi_improve_live_kernel(const float* __restrict__ V, int* __restrict__ policy, co
     }
     if (changed != nullptr) pi_wave_sum_to<PI_BLOCK_IMPROVE>(n_changed, changed);
 }
+extern "C" __global__ void __launch_bounds__(PI_BLOCK_IMPROVE)
+pi_improve_live_kernel(const float* __restrict__ V, int* __restrict__ policy, const int* __restrict__ live,
+                       const float* __restrict__ tab, long long n_live, float gamma,
+                       unsigned int* __restrict__ changed, PiSched sc) {
+    pi_improve_live_body<false>(V, policy, live, tab, n_live, gamma, changed, sc);
+}
+
+// ---- the improvement sweeps on the pair table (PI_PAIR_TABLE: 4-D units the host chose, pi_compile.cpp) -------------
+// An improvement sweep gathers 2^D values per action and state and never writes V, so it pays to lay V out for the
+// gather once per sweep: pi_pack_pairs_kernel streams V into the pair table (pi_request_corners_pairs; 8 bytes per
+// state, the handle's buffer), and the two kernels below are the improvement kernels above with the table pointer
+// beside V and 2^(D-2) 16-byte loads per backup instead of 2^(D-1) 8-byte ones.  The evaluation sweeps write V every
+// sweep and would have to write the table too (profiles/r02, r03: slower), the value sweep likewise; they keep V.
+// The plain kernels stay in the unit: sub-range launches (sharded ranks) and a handle without the buffer take them.
+// Measured on MI355X (profiles/r11/pair_table_ab.txt): 80^4 x 11 actions, pack included, 2.07 -> 1.89 ms per improvement
+// sweep, 64^4 0.98 -> 0.90 ms; the ten evaluation sweeps that follow take 0.055 ms longer although their kernels are
+// unchanged (presumably the first of them no longer finds V in the Infinity Cache, through which the 328 MB table has
+// just been streamed), so the step gains 2.0 %.  50^4 x 5 actions LOSES (0.149 -> 0.158 ms: one pack per 5 gathers
+// instead of 11), which is why the host builds these kernels for big grids only.
+#ifdef PI_PAIR_TABLE
+// Thread s: P[2 s] = V[s], P[2 s + 1] = V[s + row] (0 past the end: the cell search never names such a corner), as one
+// 8-byte store.  64-bit indexing; both reads and the store are coalesced.
+extern "C" __global__ void __launch_bounds__(PI_BLOCK)
+pi_pack_pairs_kernel(const float* __restrict__ V, float* __restrict__ P) {
+    const long long s = (long long)blockIdx.x * PI_BLOCK + threadIdx.x;
+    if (s >= PI_GRID.n) return;
+    constexpr long long row = PI_GRID.stride[PI_D - 2];
+    PiPair v;
+    v.x = V[s];
+    v.y = s + row < PI_GRID.n ? V[s + row] : 0.0f;
+    reinterpret_cast<PiPair*>(P)[s] = v;
+}
+extern "C" __global__ void __launch_bounds__(PI_BLOCK_IMPROVE)
+pi_improve_sweep_pairs_kernel(const float* __restrict__ V, const float* __restrict__ P, int* __restrict__ policy,
+                              const unsigned char* __restrict__ term, const float* __restrict__ tab,
+                              long long s_begin, long long s_end, float gamma,
+                              unsigned int* __restrict__ changed, PiSched sc) {
+    pi_improve_body<false, true>(V, P, nullptr, policy, term, tab, s_begin, s_end, gamma, nullptr, changed, sc);
+}
+extern "C" __global__ void __launch_bounds__(PI_BLOCK_IMPROVE)
+pi_improve_live_pairs_kernel(const float* __restrict__ V, const float* __restrict__ P, int* __restrict__ policy,
+                             const int* __restrict__ live, const float* __restrict__ tab, long long n_live, float gamma,
+                             unsigned int* __restrict__ changed, PiSched sc) {
+    (void)V;
+    pi_improve_live_body<true>(P, policy, live, tab, n_live, gamma, changed, sc);
+}
+#endif
 
 extern "C" __global__ void __launch_bounds__(PI_BLOCK_IMPROVE)
 pi_value_sweep_kernel(const float* __restrict__ V, float* __restrict__ Vn, int* __restrict__ policy,
@@ -1133,7 +1221,7 @@ pi_value_sweep_kernel(const float* __restrict__ V, float* __restrict__ Vn, int* 
                       long long s_begin, long long s_end, float gamma,
                       unsigned int* __restrict__ delta_bits, unsigned int* __restrict__ changed,
                       PiSched sc) {
-    pi_improve_body<true>(V, Vn, policy, term, tab, s_begin, s_end, gamma, delta_bits, changed, sc);
+    pi_improve_body<true>(V, nullptr, Vn, policy, term, tab, s_begin, s_end, gamma, delta_bits, changed, sc);
 }
 
 // Fold the PI_NSLOT accumulator slots into the caller's scalars and clear them for the next

@@ -559,8 +559,14 @@ enum pi_option_code {
     PI_OPTION_STRIP_STATES = 7,      /* STRIP SCHEDULE of the sweeps: states per period (see pi_plan_schedule; -1 = the
                                         library's choice for the grid, the default; 0 = slab schedule; PI_MI355_STRIP in
                                         the environment at pi_create sets the same) */
-    PI_OPTION_XCD_RUN_FAILED = 8     /* the last pi_policy_iteration launch on the XCD-local kernel did not go through
+    PI_OPTION_XCD_RUN_FAILED = 8,    /* the last pi_policy_iteration launch on the XCD-local kernel did not go through
                                         (value: enum pi_xcd_failure) */
+    PI_OPTION_PAIR_TABLE = 9         /* PAIR TABLE of the improvement sweeps: whole-grid pi_improve_sweep calls on 4-D grids
+                                        with 8 n < 2^32 pack V into {V[s], V[s + row]} pairs (an 8 n-byte buffer of the
+                                        handle, packed on every call) and gather from those with half as many loads.
+                                        -1 = the library's choice for the grid, the default; 0 = off; 1 = on where the
+                                        grid admits it.  Switching it ON takes effect at pi_compile, which builds the
+                                        kernels; results do not depend on it */
 };
 /* The values PI_OPTION_XCD_RUN_FAILED takes. */
 enum pi_xcd_failure {
@@ -611,7 +617,9 @@ enum pi_info_code {
     PI_INFO_XCD_FALLBACKS = 32,               /* ... run again after a placement failure or a time-out */
     PI_INFO_WHOLE_RUNS = 33,                  /* whole runs launched (pi_policy_iteration) */
     PI_INFO_WHOLE_RUN_AVAILABLE = 34,         /* 1 if pi_policy_iteration serves this grid */
-    PI_INFO_STRIP_STATES = 35                 /* states per period of the strip schedule in use (0: slab schedule) */
+    PI_INFO_STRIP_STATES = 35,                /* states per period of the strip schedule in use (0: slab schedule) */
+    PI_INFO_PAIR_TABLE = 37                   /* 1 if the last pi_improve_sweep gathered from the pair table
+                                                 (PI_OPTION_PAIR_TABLE); 36 stays unassigned */
 };
 int64_t pi_info(pi_handle* h, int what);
 
