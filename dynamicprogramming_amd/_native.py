@@ -91,6 +91,12 @@ SIGNATURES = {
     "pi_infer_greedy": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
     "pi_infer_rollout_greedy": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                                _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "pi_infer_set_stochastic": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
+    "pi_infer_rollout_stochastic": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                                   ctypes.c_float, _f32p, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp,
+                                                   _vp, _vp, ctypes.c_int, _vp]),
+    "pi_infer_random_words": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32,
+                                             ctypes.c_uint32, _vp, _vp]),
     "pi_plan_schedule": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_uint64)]),
     "pi_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64]),
@@ -707,6 +713,42 @@ class InferenceEngine:
                                              float(lookahead_gamma), d_final or None, d_return or None, d_length or None,
                                              d_terminated or None, d_traj or None, int(traj_every), stream or None),
                "pi_infer_rollout_greedy")
+
+    def set_stochastic(self, action_space) -> str:
+        """Upload the action table exploring steps draw from and build the stochastic rollout kernels behind the plugin
+        of the last set_dynamics (a compile check on a host-only handle); needs set_dynamics, neither a policy nor
+        values; returns the compiler's log.  A later set_dynamics drops the module again."""
+        act = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        log = ctypes.create_string_buffer(1 << 16)
+        rc = lib().pi_infer_set_stochastic(self._h, None if act is None else act.ctypes.data_as(_f32p),
+                                           0 if act is None else len(act), log, len(log))
+        text = log.value.decode(errors="replace")
+        if rc != 0:
+            raise NativeError(f"pi_infer_set_stochastic failed:\n{last_error()}")
+        return text
+
+    def rollout_stochastic(self, d_start, m, n_steps, gamma=1.0, epsilon=0.0, action_noise=0.0, state_noise=None, seed=0,
+                           first_episode=0, d_final=0, d_return=0, d_length=0, d_terminated=0, d_traj=0, traj_every=0,
+                           stream=0) -> None:
+        """m episodes of n_steps closed-loop steps with epsilon-random actions, action noise and state noise from the
+        counter-based stream (seed, first_episode + row, step), in one launch (pi_infer_rollout_stochastic; raw device
+        pointers, `state_noise` a host array of D floats or None; asynchronous)."""
+        noise = None
+        if state_noise is not None:
+            noise = np.ascontiguousarray(state_noise, dtype=np.float32)
+            if noise.shape != (self.D,):
+                raise ValueError(f"state_noise must hold {self.D} values")
+        _check(lib().pi_infer_rollout_stochastic(self._h, d_start or None, int(m), int(n_steps), float(gamma), float(epsilon),
+                                                 float(action_noise), None if noise is None else noise.ctypes.data_as(_f32p),
+                                                 int(seed), int(first_episode), d_final or None, d_return or None,
+                                                 d_length or None, d_terminated or None, d_traj or None, int(traj_every),
+                                                 stream or None), "pi_infer_rollout_stochastic")
+
+    def random_words(self, seed, first_episode, m, step, block, d_words, stream=0) -> None:
+        """The four Philox words of (seed, first_episode + row, step, block) for rows 0 .. m into the (m, 4) uint32 device
+        buffer at `d_words` (pi_infer_random_words; asynchronous)."""
+        _check(lib().pi_infer_random_words(self._h, int(seed), int(first_episode), int(m), int(step), int(block),
+                                           d_words or None, stream or None), "pi_infer_random_words")
 
     def close(self) -> None:
         if getattr(self, "_h", None):

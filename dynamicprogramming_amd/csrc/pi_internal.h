@@ -10,6 +10,7 @@
 //   pi_infer.cpp, pi_rollout.cpp   the inference handle and its rollouts;  pi_hybrid.cpp  rollouts that switch between two handles
 //   pi_resample.cpp   the inference handle's solution interpolated onto another grid (grid continuation)
 //   pi_greedy.cpp     value-greedy control on the inference handle: one-step lookahead on V, queries and rollouts
+//   pi_stochastic.cpp stochastic rollouts on the inference handle: random baseline, epsilon-random actions, noise (Philox)
 #pragma once
 
 #include "pi_knobs.h"
@@ -283,6 +284,15 @@ struct pi_infer {
     bool has_greedy = false;             // pi_infer_set_greedy went through (host-only handles: it compiled)
     float* d_greedy_actions = nullptr;
     int n_greedy_actions = 0;
+    // sixth module (pi_infer_set_stochastic, pi_stochastic.cpp): this grid + pi_math.h + the env plugin + the helpers of
+    // csrc/pi_rollout_kernels.hip + csrc/pi_stochastic_kernels.hip.  d_stochastic_actions: the action table of that call
+    // (owned), the table exploring steps draw from; stochastic_a_min / _a_max: its extremes, the clamp of a noisy action
+    hipModule_t module_stochastic = nullptr;
+    hipFunction_t f_stochastic_rollout = nullptr, f_random_words = nullptr;
+    bool has_stochastic = false;         // pi_infer_set_stochastic went through (host-only handles: it compiled)
+    float* d_stochastic_actions = nullptr;
+    int n_stochastic_actions = 0;
+    float stochastic_a_min = 0.0f, stochastic_a_max = 0.0f;
 };
 
 namespace pi {
@@ -342,5 +352,6 @@ int check_rollout_args(int D, const float* d_start, int64_t m, int n_steps, cons
                        int traj_every, int64_t* blocks);
 int drop_hybrid(pi_infer* h);           // pi_hybrid.cpp: unloads the third module (after a device synchronisation)
 int drop_greedy(pi_infer* h);           // pi_greedy.cpp: unloads the fifth module (after a device synchronisation)
+int drop_stochastic(pi_infer* h);       // pi_stochastic.cpp: unloads the sixth module (after a device synchronisation)
 
 }  // namespace pi

@@ -120,8 +120,9 @@ __device__ __forceinline__ void pi_rollout_store_state(float* __restrict__ row, 
 #endif
 }
 
-// the hybrid module holds pi_hybrid_rollout_kernel instead, the greedy module (pi_greedy_kernels.hip) its own two
-#if !defined(PI_HYBRID) && !defined(PI_GREEDY)
+// the hybrid module holds pi_hybrid_rollout_kernel instead, the greedy module (pi_greedy_kernels.hip) and the stochastic
+// module (pi_stochastic_kernels.hip) their own two each
+#if !defined(PI_HYBRID) && !defined(PI_GREEDY) && !defined(PI_STOCHASTIC)
 extern "C" __global__ void __launch_bounds__(PI_RO_BLOCK)
 pi_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, float gamma,
                   const int* __restrict__ policy, const float* __restrict__ actions,
@@ -178,4 +179,4 @@ pi_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, flo
     if (out_length != nullptr) out_length[k] = length;
     if (out_terminated != nullptr) out_terminated[k] = terminated ? 1 : 0;
 }
-#endif  // PI_HYBRID, PI_GREEDY
+#endif  // PI_HYBRID, PI_GREEDY, PI_STOCHASTIC

@@ -996,29 +996,41 @@ class _CudaPolicyIterationBase(abc.ABC):
         logger.success("Device memory released. Results in host memory.")
 
     # ── closed-loop evaluation (the reference's per-runner evaluate(), e.g. pendulum_cuda.py:135-189) ─────────
-    def rollout(self, start_states, steps, gamma=1.0, record_every=0, device=None, controller="policy"):
+    def rollout(self, start_states, steps, gamma=1.0, record_every=0, device=None, controller="policy", *,
+                epsilon=0.0, action_noise=0.0, state_noise=None, seed=0, first_episode=0):
         """Roll the trained policy out on the env's own dynamics, every episode of the batch in ONE kernel launch
         (utils.barycentric.DevicePolicy.rollout; csrc/pi_rollout_kernels.hip): `start_states` (m, D) — numpy, or a
         float32 tensor on the device — for `steps` steps each.  Returns a RolloutResult (states, returns, lengths,
         terminated, trajectory).  Works on the host arrays, so after run() as well as on a load()ed instance.
         controller="greedy": act by the one-step lookahead on the VALUE function instead (csrc/pi_greedy_kernels.hip),
         with the config's gamma inside the lookahead — it needs no policy table, so it also works after
-        value_iteration()."""
+        value_iteration().
+        epsilon, action_noise, state_noise, seed, first_episode: stochastic rollouts (csrc/pi_stochastic_kernels.hip;
+        DevicePolicy.rollout documents them) — epsilon-random actions from this solver's action table, action noise and
+        state noise from a stream that depends on (seed, first_episode + row, step) only.  controller="random" is the
+        random-policy baseline (epsilon = 1): it reads no table, so it also works on an instance that has never run."""
         from utils.barycentric import DevicePolicy
-        if controller not in ("policy", "greedy"):
-            raise ValueError(f"controller must be 'policy' or 'greedy', not {controller!r}")
+        if controller not in ("policy", "greedy", "random"):
+            raise ValueError(f"controller must be 'policy', 'greedy' or 'random', not {controller!r}")
         greedy = controller == "greedy"
+        noisy = dict(epsilon=epsilon, action_noise=action_noise, state_noise=state_noise, seed=seed, first_episode=first_episode)
+        stochastic = controller == "random" or float(epsilon) != 0.0 or float(action_noise) != 0.0 or \
+            (state_noise is not None and bool(np.any(np.asarray(state_noise, dtype=np.float32) != 0)))
+        if greedy and stochastic:
+            raise ValueError("controller='greedy' takes no epsilon, action_noise or state_noise: a stochastic greedy "
+                             "controller does not exist")
+        no_policy = greedy or controller == "random" or float(epsilon) == 1.0
         values = getattr(self, "value_function", None)
         if greedy and values is None and hasattr(self, "d_value_function") and self._comm is None:
             # mid-run (value_iteration(), policy_evaluation()): the current iterate, in the user's order
             values = np.ascontiguousarray(self._to_user(self.d_value_function[:self.n_states].cpu().numpy()))
         if greedy and values is None:
             raise RuntimeError("a greedy rollout needs a value function: call run(), value_iteration() or load() first")
-        if not greedy and getattr(self, "policy", None) is None:
+        if not no_policy and getattr(self, "policy", None) is None:
             raise RuntimeError("rollout needs a trained policy in host memory: call run() or load() first")
         if device is None:                          # the device the solver trained on; a load()ed instance has none
             device = getattr(self, "_device_arg", None) or "cuda:0"
-        dp = DevicePolicy(None if greedy else self.policy, self.action_space, self.bounds_low, self.bounds_high,
+        dp = DevicePolicy(None if no_policy else self.policy, self.action_space, self.bounds_low, self.bounds_high,
                           self.grid_shape, self.strides, self.corner_bits, device=device)
         try:
             dp.set_dynamics(self._dynamics_cuda_src())
@@ -1027,6 +1039,9 @@ class _CudaPolicyIterationBase(abc.ABC):
                 dp.set_greedy()
                 out = dp.rollout(start_states, steps, gamma=gamma, record_every=record_every, controller="greedy",
                                  lookahead_gamma=self.config.gamma)
+            elif stochastic:
+                dp.set_stochastic()
+                out = dp.rollout(start_states, steps, gamma=gamma, record_every=record_every, controller=controller, **noisy)
             else:
                 out = dp.rollout(start_states, steps, gamma=gamma, record_every=record_every)
             dp._torch.cuda.synchronize(dp.device)

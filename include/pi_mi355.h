@@ -515,6 +515,40 @@ int pi_plan_schedule(pi_handle* h, int block, int64_t first, int64_t count, int6
  *                       `lookahead_gamma`, a property of the solution; `gamma` discounts the return as in pi_infer_rollout
  *                       (neither may be NaN).  The step taken is step_dynamics(s, actions[best]).  Outputs, trajectory
  *                       layout, alignment and argument rules are pi_infer_rollout's.  Needs no policy.  Asynchronous.
+ * Stochastic rollouts on the same handle (the reference's evaluate_random() behind --random, e.g. pendulum_cuda.py, as ONE
+ * launch for m episodes; epsilon-random actions and noise have no reference counterpart): pi_infer_rollout with a random
+ * stream inside the kernel.  The stream is Philox4x32-10 as published (multipliers 0xD2511F53, 0xCD9E8D57; Weyl key
+ * increments 0x9E3779B9, 0xBB67AE85; ten rounds), key = (low, high 32 bits of `seed`), counter = (low, high 32 bits of e,
+ * t, j) with e = first_episode + the episode's row in the batch (uint64), t the step, j the draw block: no state in
+ * memory, results independent of how a batch is cut into launches, reproduced bit for bit by utils/barycentric.py
+ * (philox4x32).  Of a block's words x0..x3, block 0 gives x0 the exploration coin, x1 the random action index, x2 the
+ * action noise; block 1 the state noise of dimensions 0..3; block 2 (6-D) that of dimensions 4, 5 in x0, x1.
+ * sym(x) = (float)((int)(x >> 8) - 8388608) * 2^-23, a value in [-1, 1).  Per step of a running episode, in this order:
+ *   1. a = the bits pi_infer_query returns for the state (skipped on a handle without a policy)
+ *   2. explore iff (x0 >> 8) < eps24, eps24 = (uint32) llrint((double)epsilon * 16777216.0): epsilon = 0 never explores,
+ *      epsilon = 1 always; then a = action_space[(uint32)(((uint64)x1 * n_actions) >> 32)], the table of
+ *      pi_infer_set_stochastic
+ *   3. action_noise != 0: a = a + action_noise * sym(x2), a float32 multiply, then an add; then
+ *      a = fminf(fmaxf(a, a_min), a_max), the extremes of that table.  No clamp when action_noise == 0
+ *   4. step_dynamics; ret, disc, length and the freeze exactly as in pi_infer_rollout
+ *   5. not `done`: for every d with state_noise[d] != 0, s'[d] = s'[d] + state_noise[d] * sym(word d); a dimension with
+ *      zero noise is not touched, the disturbed state is neither clamped nor wrapped, it is what the controller and the
+ *      plugin see next and what the trajectory records; a `done` step stores its successor undisturbed.
+ * With epsilon, action_noise and state_noise all zero the outputs are pi_infer_rollout's, bit for bit.
+ *   pi_infer_set_stochastic  host array: the action table (n_actions >= 1 finite float32), copied to the device — the
+ *                       handle's own copy; builds the handle's SIXTH module: its grid + the plugin last given to
+ *                       pi_infer_set_dynamics + csrc/pi_stochastic_kernels.hip.  Needs pi_infer_set_dynamics, neither a
+ *                       policy nor values.  Same cache, flags and log convention as pi_infer_set_dynamics; device = -1
+ *                       handles: compile check.  pi_infer_set_dynamics drops the module again (the next stochastic call
+ *                       then fails, naming pi_infer_set_stochastic)
+ *   pi_infer_rollout_stochastic  arguments and outputs of pi_infer_rollout (alignment, m == 0, n_steps == 0 and traj_every
+ *                       as there), plus: epsilon in [0, 1]; action_noise >= 0, finite; state_noise a HOST array of D
+ *                       floats >= 0, finite, or null = none; seed, first_episode as above; gamma not NaN.  A handle
+ *                       without a policy is served only when epsilon == 1 (the random-policy baseline); otherwise the
+ *                       call fails, naming pi_infer_set_policy.  Every refusal is an error code and pi_last_error, never
+ *                       a launch.  Asynchronous.
+ *   pi_infer_random_words  probe of the stream: for rows 0 .. m the four words of (seed, first_episode + row, step, block)
+ *                       into d_words, (m, 4) uint32 on the device.  m == 0 is a no-op.  Asynchronous.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pi_infer pi_infer;
 pi_infer* pi_infer_create(int device, int D, const float* lo, const float* hi, const int32_t* grid_shape,
@@ -544,6 +578,13 @@ int pi_infer_greedy(pi_infer* h, const float* d_points, int64_t m, float gamma, 
 int pi_infer_rollout_greedy(pi_infer* h, const float* d_start, int64_t m, int n_steps, float gamma, float lookahead_gamma,
                             float* d_final, float* d_return, int32_t* d_length, uint8_t* d_terminated, float* d_traj,
                             int traj_every, void* stream);
+int pi_infer_set_stochastic(pi_infer* h, const float* action_space, int n_actions, char* log, size_t log_len);
+int pi_infer_rollout_stochastic(pi_infer* h, const float* d_start, int64_t m, int n_steps, float gamma, float epsilon,
+                                float action_noise, const float* state_noise, uint64_t seed, uint64_t first_episode,
+                                float* d_final, float* d_return, int32_t* d_length, uint8_t* d_terminated, float* d_traj,
+                                int traj_every, void* stream);
+int pi_infer_random_words(pi_infer* h, uint64_t seed, uint64_t first_episode, int64_t m, uint32_t step, uint32_t block,
+                          uint32_t* d_words, void* stream);
 
 /* Tuning: the `what` of pi_set_option. */
 enum pi_option_code {

@@ -24,6 +24,17 @@ episode; those four flags are then honoured, not ignored.  The 6-D swing-up also
 or the greedy one-step lookahead on the interpolated value function (solver.rollout(controller="greedy")), which needs
 only V.  The printed lines and last_trajectory.npz keep their form.
 
+--epsilon E, --action-noise A and --state-noise X [X ...] (extensions, with --rollout, default 0) make those episodes
+stochastic (solver.rollout(epsilon=..., action_noise=..., state_noise=...); csrc/pi_stochastic_kernels.hip): a step takes
+a uniformly random action of the env's action set with probability E, every action gains A * u and is clamped to the
+set's range, every successor gains X * u per dimension (one X for all dimensions, or one per dimension), u uniform in
+[-1, 1).  --seed seeds the starts and this noise.  Without --rollout the three are listed as ignored.
+
+--rollout --random [N] runs the reference's random-policy baseline (evaluate_random(), e.g. pendulum_cuda.py:192-205) on
+the GPU: N episodes of --steps steps from the env's start states under uniformly random actions, no training and no
+archive, one "[random] Episode k: L steps | reward = R" line each.  Without --rollout, --random keeps skipping training
+and doing nothing else.
+
 A third extension flag, --coarse-bins N [N ...] (off by default), trains by grid continuation: the env is solved at
 each N in turn — each level started from the previous level's solution interpolated onto its grid
 (solver.continue_from) — and then at --bins; sweeps and seconds are printed per level.  Only the --bins solution is saved.
@@ -134,6 +145,14 @@ def build_parser(env_name: str, default_save: str) -> argparse.ArgumentParser:
     p.add_argument("--controller", choices=("policy", "greedy"), default="policy",
                    help="(extension, with --rollout) what acts in the episodes: the interpolated policy table, or the "
                         "greedy one-step lookahead on the interpolated value function")
+    p.add_argument("--epsilon", type=float, default=0.0, metavar="E",
+                   help="(extension, with --rollout) probability that a step takes a uniformly random action instead")
+    p.add_argument("--action-noise", type=float, default=0.0, metavar="A",
+                   help="(extension, with --rollout) actuator noise: A * u, u uniform in [-1, 1), added to every action, "
+                        "which is then clamped to the action set's range")
+    p.add_argument("--state-noise", type=float, nargs="+", default=None, metavar="X",
+                   help="(extension, with --rollout) state disturbance after every step: X * u per dimension (one value "
+                        "for every dimension, or one per dimension)")
     return p
 
 
@@ -141,18 +160,21 @@ STEADY_WINDOW = 100     # states per episode in results/last_trajectory.npz (the
 
 
 def evaluate(env_name: str, pi, episodes: int, steps: int, seed: int, start_x: float | None = None,
-             traj_path: Path | None = None, controller: str = "policy"):
+             traj_path: Path | None = None, controller: str = "policy", epsilon: float = 0.0, action_noise: float = 0.0,
+             state_noise=None):
     """--rollout: `episodes` closed-loop episodes of at most `steps` steps in one kernel launch (solver.rollout), one
     line each.  `traj_path`: also dump the last min(100, length + 1) states of every episode, concatenated, as the
     reference's evaluate() does for its scoring script (double_cartpole_swingup_cuda.py:583-592).  `controller`:
-    "policy" or "greedy" (--controller).  Returns the RolloutResult."""
+    "policy" or "greedy" (--controller).  `epsilon`, `action_noise`, `state_noise` (--epsilon, --action-noise,
+    --state-noise): a stochastic rollout, its stream seeded by `seed` like the starts.  Returns the RolloutResult."""
     import numpy as np
     from dynamicprogramming_amd import envs
     cls = envs.ENVS[env_name]
     rng = np.random.default_rng(seed)
     kw = {} if start_x is None else {"start_x": start_x}
     starts = cls.start_states(rng, episodes, **kw)
-    res = pi.rollout(starts, steps, gamma=1.0, record_every=1 if traj_path is not None else 0, controller=controller)
+    res = pi.rollout(starts, steps, gamma=1.0, record_every=1 if traj_path is not None else 0, controller=controller,
+                     epsilon=epsilon, action_noise=action_noise, state_noise=state_noise, seed=seed)
     for ep in range(episodes):
         outcome = "terminated" if res.terminated[ep] else f"{steps} steps"
         final = "  ".join(f"{v:+.4f}" for v in res.states[ep])
@@ -171,15 +193,35 @@ def evaluate(env_name: str, pi, episodes: int, steps: int, seed: int, start_x: f
     return res
 
 
+def evaluate_random(env_name: str, episodes: int, steps: int, seed: int, start_x: float | None = None, **kw):
+    """--rollout --random [N]: the reference's evaluate_random() (e.g. pendulum_cuda.py:192-205) — `episodes` episodes of
+    at most `steps` steps under uniformly random actions from the env's action set, from the env's start states — in
+    one kernel launch (solver.rollout(controller="random")), one line each in the reference's form.  No training and
+    no archive: a random rollout reads no table, so the env's smallest grid serves.  Returns the RolloutResult."""
+    import numpy as np
+    from dynamicprogramming_amd import envs
+    cls = envs.ENVS[env_name]
+    pi = envs.make(env_name, 2, **kw)
+    starts = cls.start_states(np.random.default_rng(seed), episodes, **({} if start_x is None else {"start_x": start_x}))
+    res = pi.rollout(starts, steps, gamma=1.0, controller="random", seed=seed)
+    for ep in range(episodes):
+        print(f"[random] Episode {ep + 1}: {int(res.lengths[ep])} steps | reward = {float(res.returns[ep]):.2f}")
+    return res
+
+
 def ignored_flags(args) -> list:
     """The flags of this command line that nothing here acts on.  --render, --record and --no-plot always; --episodes,
-    --steps, --seed, --start-x and --controller unless --rollout runs the evaluation they belong to."""
+    --steps, --seed, --start-x, --controller, --epsilon, --action-noise and --state-noise unless --rollout runs the
+    evaluation they belong to."""
     harness = not args.rollout
     return [f for f, on in (("--render", args.render), ("--record", args.record is not None),
                             ("--episodes", harness and args.episodes != 5), ("--steps", harness and args.steps != 1000),
                             ("--seed", harness and args.seed != 42), ("--no-plot", args.no_plot),
                             ("--start-x", harness and getattr(args, "start_x", 2.5) != 2.5),
-                            ("--controller", harness and args.controller != "policy")) if on]
+                            ("--controller", harness and args.controller != "policy"),
+                            ("--epsilon", harness and args.epsilon != 0.0),
+                            ("--action-noise", harness and args.action_noise != 0.0),
+                            ("--state-noise", harness and args.state_noise is not None)) if on]
 
 
 def main(env_name: str, default_save: str, argv=None):
@@ -193,10 +235,13 @@ def main(env_name: str, default_save: str, argv=None):
     if ignored:
         print(f"[{env_name}] note: {', '.join(ignored)} belong to the rollout / plot harness, which this "
               "package does not include; accepted and ignored")
+    kw = {"target_x": args.target_x} if env_name == "overhead_crane" else {}
+    if args.random is not None and args.rollout:
+        evaluate_random(env_name, args.random, args.steps, args.seed, start_x=getattr(args, "start_x", None), **kw)
+        return None
     if args.random is not None:
         print(f"[{env_name}] --random runs rollouts only (no training) in the reference; nothing to do here")
         return None
-    kw = {"target_x": args.target_x} if env_name == "overhead_crane" else {}
     path = Path(args.save_path).with_suffix(".npz")
     if path.exists() and not args.retrain:
         print(f"[+] Loading existing policy from {path}")
@@ -208,5 +253,6 @@ def main(env_name: str, default_save: str, argv=None):
     if args.rollout:
         evaluate(env_name, pi, args.episodes, args.steps, args.seed, start_x=getattr(args, "start_x", None),
                  traj_path=Path("results") / "last_trajectory.npz" if env_name == "double_cartpole_swingup" else None,
-                 controller=args.controller)
+                 controller=args.controller, epsilon=args.epsilon, action_noise=args.action_noise,
+                 state_noise=args.state_noise)
     return pi

@@ -22,7 +22,13 @@ m = 4 096 episodes of --steps steps; per config the fused greedy rollout, the lo
 one pi_probe_step launch per time step plus the bookkeeping as torch ops) and the fused interpolated-policy rollout of the
 same batch, then the registers and scratch of both greedy kernels (hipcc -Rpass-analysis=kernel-resource-usage on the
 translation unit pi_infer_set_greedy builds).  The table is written to --out.
-usage: python tools/rollout_bench.py [--hybrid | --greedy] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
+--stochastic: the stochastic rollout instead (pi_infer_rollout_stochastic, csrc/pi_stochastic_kernels.hip): C2, C3 and the
+25^6 double cart-pole with a seeded random policy, epsilon 0.3, action noise a tenth of the action range and state noise in
+every dimension, m = 4 096 episodes of --steps steps; per config the fused stochastic rollout, the loop it replaces (per
+step a query, the words of pi_infer_random_words, one pi_probe_step and the mixing as torch ops), the fused deterministic
+rollout of the same batch and the random-policy baseline, then the registers and scratch of both kernels.  The table is
+written to --out.
+usage: python tools/rollout_bench.py [--hybrid | --greedy | --stochastic] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
 """
 import argparse
 import json
@@ -288,9 +294,10 @@ def greedy_child(args):
     eng.close()
 
 
-def greedy_usage(env, bins):
+def greedy_usage(env, bins, define="PI_GREEDY", kernels="pi_greedy_kernels.hip"):
     """VGPRs and scratch bytes per lane of both greedy kernels for one grid: the translation unit pi_infer_set_greedy hands
-    to hipRTC, built ahead of time with the same flags."""
+    to hipRTC, built ahead of time with the same flags.  (`define`, `kernels`: the same for another module that sits
+    behind the rollout helpers — the stochastic one.)"""
     import tempfile
     import numpy as np
     from __graft_entry__ import HIPCC
@@ -307,13 +314,13 @@ def greedy_usage(env, bins):
     def hexf(x):
         return float(np.float32(x)).hex() + "f"
     csrc = ROOT / "dynamicprogramming_amd" / "csrc"
-    text = (f"#define PI_GREEDY 1\n#define PI_D {D}\n#define PI_LO_INIT {braces([t.min() for t in tabs], hexf)}\n"
+    text = (f"#define {define} 1\n#define PI_D {D}\n#define PI_LO_INIT {braces([t.min() for t in tabs], hexf)}\n"
             f"#define PI_HI_INIT {braces([t.max() for t in tabs], hexf)}\n#define PI_SHAPE_INIT {braces(shape, str)}\n"
             f"#define PI_STRIDES_INIT {braces(strides, str)}\n"
             f"#define PI_BITS_INIT {braces(list(product([0, 1], repeat=D)), lambda r: braces(r, str))}\n"
             f"{(ROOT / 'include' / 'pi_math.h').read_text()}\n#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n"
             f"{envs.dynamics_source(env)}\n{(csrc / 'pi_rollout_kernels.hip').read_text()}\n"
-            f"{(csrc / 'pi_greedy_kernels.hip').read_text()}\n")
+            f"{(csrc / kernels).read_text()}\n")
     usage, fn = {}, None
     with tempfile.TemporaryDirectory(prefix="pi_greedy_") as tmp:
         src = Path(tmp) / "greedy.hip"
@@ -322,7 +329,7 @@ def greedy_usage(env, bins):
                               "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src), "-o",
                               str(Path(tmp) / "greedy.hsaco")], capture_output=True, text=True)
     if res.returncode != 0:
-        sys.exit(f"hipcc failed on the greedy translation unit of {env} {bins}^{D}\n{res.stderr[-2000:]}")
+        sys.exit(f"hipcc failed on the {kernels} translation unit of {env} {bins}^{D}\n{res.stderr[-2000:]}")
     for line in res.stderr.splitlines():
         if "Function Name:" in line:
             fn = line.split("Function Name:")[1].split()[0]
@@ -367,6 +374,155 @@ def greedy_driver(args):
     for config, (env, bins) in CONFIGS.items():
         for fn, k in sorted(greedy_usage(env, bins).items()):
             lines.append(f"  {config} {env:24s} {fn:26s} VGPRs {k['vgpr']:4d}  scratch {k['scratch']} bytes/lane")
+    out.write_text("\n".join(lines) + "\n")
+    print(out.read_text())
+
+
+def stochastic_child(args):
+    import numpy as np
+    import torch
+    from dynamicprogramming_amd import _native, envs
+    from utils import barycentric as B
+    env, bins = CONFIGS[args.config]
+    cls = envs.ENVS[env]
+    tabs = [np.asarray(b, np.float32) for b in cls.bins_space(bins).values()]
+    D = len(tabs)
+    shape = np.array([len(t) for t in tabs], np.int32)
+    lo, hi = np.array([t.min() for t in tabs], np.float32), np.array([t.max() for t in tabs], np.float32)
+    strides = np.array([int(np.prod(shape[d + 1:])) for d in range(D)], np.int32)
+    bits = np.array(list(product([0, 1], repeat=D)), dtype=np.int32)
+    acts = np.asarray(cls.ACTIONS, np.float32)
+    rng = np.random.default_rng(0)
+    policy = rng.integers(0, len(acts), size=int(np.prod(shape.astype(np.int64))), dtype=np.int32)
+    m, steps, seed = args.m, args.steps, 20261019
+    epsilon, a_noise = 0.3, float(np.float32(0.1) * (acts.max() - acts.min()))
+    s_noise = (np.float32(0.002) * (hi - lo)).astype(np.float32)             # every dimension: all the draw blocks of D
+    dev = torch.device("cuda:0")
+    starts = torch.from_numpy((lo + (hi - lo) * rng.random((m, D), dtype=np.float32)).astype(np.float32)).to(dev)
+    dp = B.DevicePolicy(policy, acts, lo, hi, shape, strides, bits, device=dev)
+    dp.set_dynamics(envs.dynamics_source(env))
+    dp.set_stochastic()
+    eng = _native.Engine(D, shape, lo, hi, tabs, acts, device=0)
+    eng.compile(envs.dynamics_source(env))
+    st = torch.cuda.current_stream(dev).cuda_stream
+    noisy = dict(epsilon=epsilon, action_noise=a_noise, state_noise=s_noise, seed=seed)
+
+    def fused():
+        return dp.rollout(starts, steps, **noisy)
+
+    def baseline():                                       # uniformly random actions, nothing else: no table is read
+        return dp.rollout(starts, steps, controller="random", seed=seed)
+
+    def single():
+        return dp.rollout(starts, steps)
+    d_acts = torch.from_numpy(acts).to(dev)
+    eps24, n_act = B.explore_threshold(epsilon), len(acts)
+    amp = torch.tensor(a_noise, dtype=torch.float32, device=dev)
+    d_noise = torch.from_numpy(s_noise).to(dev)
+    a_lo, a_hi = d_acts.min(), d_acts.max()
+    blocks = (1, 2) if D > 4 else (1,)
+
+    def sym(x):                                           # int32 words holding uint32 bits -> [-1, 1), exact
+        return (((x >> 8) & 0xFFFFFF) - 8388608).to(torch.float32) * 2.0 ** -23
+
+    def loop():                                           # the words from the probe kernel, mixed in with torch float32 ops
+        states = starts.clone()
+        nxt = torch.empty_like(states)
+        rew = torch.empty(m, dtype=torch.float32, device=dev)
+        done = torch.empty(m, dtype=torch.uint8, device=dev)
+        ret = torch.zeros(m, dtype=torch.float32, device=dev)
+        length = torch.zeros(m, dtype=torch.int32, device=dev)
+        ended = torch.zeros(m, dtype=torch.bool, device=dev)
+        w0 = torch.empty((m, 4), dtype=torch.int32, device=dev)
+        w = torch.empty((len(blocks), m, 4), dtype=torch.int32, device=dev)
+        for t in range(steps):
+            act = dp(states)
+            dp._engine.random_words(seed, 0, m, t, 0, w0.data_ptr(), stream=st)
+            explore = ((w0[:, 0] >> 8) & 0xFFFFFF) < eps24
+            index = ((w0[:, 1].to(torch.int64) & 0xFFFFFFFF) * n_act) >> 32
+            act = torch.where(explore, d_acts[index], act)
+            push = amp * sym(w0[:, 2])
+            act = torch.fmin(torch.fmax(act + push, a_lo), a_hi).contiguous()
+            eng.probe_step(states.data_ptr(), act.data_ptr(), nxt.data_ptr(), rew.data_ptr(), done.data_ptr(), m, st)
+            for k, j in enumerate(blocks):
+                dp._engine.random_words(seed, 0, m, t, j, w[k].data_ptr(), stream=st)
+            words = torch.cat(list(w), dim=1)[:, :D]
+            push = d_noise * sym(words)
+            nxt2 = torch.where((done == 0)[:, None], nxt + push, nxt)
+            run = ~ended
+            ret = torch.where(run, ret + rew, ret)
+            states = torch.where(run[:, None], nxt2, states)
+            length = torch.where(run, torch.full_like(length, t + 1), length)
+            ended = ended | (run & (done != 0))
+        return B.RolloutResult(states, ret, length, ended, None)
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record()
+        out = fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1), out
+
+    a, b = fused(), loop()                                # warm-up of all paths, and: same results
+    c, r = single(), baseline()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(a.states.view(torch.int32), b.states.view(torch.int32)) and torch.equal(a.lengths, b.lengths)
+                and torch.equal(a.returns.view(torch.int32), b.returns.view(torch.int32)))
+    t_fused, t_loop, t_single, t_base = [], [], [], []
+    for _ in range(args.repeat):
+        t_fused.append(timed(fused)[0])
+        t_loop.append(timed(loop)[0])
+        t_single.append(timed(single)[0])
+        t_base.append(timed(baseline)[0])
+    print(json.dumps({"config": args.config, "env": env, "bins": bins, "D": D, "actions": len(acts), "m": m, "steps": steps,
+                      "same_bits": same, "fused_ms": min(t_fused), "loop_ms": min(t_loop), "single_ms": min(t_single),
+                      "random_ms": min(t_base), "fused_ms_all": t_fused, "single_ms_all": t_single,
+                      "episode_steps": int(a.lengths.sum().item()), "single_episode_steps": int(c.lengths.sum().item()),
+                      "random_episode_steps": int(r.lengths.sum().item()),
+                      "terminated_share": float(a.terminated.float().mean().item()),
+                      "launches_loop": (3 + len(blocks)) * steps}))
+    dp.close()
+    eng.close()
+
+
+def stochastic_driver(args):
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    me = [sys.executable, str(Path(__file__).resolve())]
+    rows = []
+    for config in CONFIGS:
+        res = subprocess.run(["timeout", "-k", "10", str(CHILD_SECONDS), *me, "--child", "--stochastic", "--config", config, "--m",
+                              str(args.m), "--steps", str(args.steps), "--repeat", str(args.repeat)], capture_output=True, text=True)
+        if res.returncode != 0:                           # a fault, an abort or a time limit: nothing more runs
+            sys.exit(f"stochastic {config} ended with status {res.returncode}; stopping\n{res.stdout[-2000:]}\n{res.stderr[-2000:]}")
+        rows.append(json.loads(res.stdout.strip().splitlines()[-1]))
+        print(rows[-1], flush=True)
+    lines = [f"stochastic rollouts (Philox4x32-10 in the kernel) vs the step-by-step loop, MI355X, commit {args.commit}",
+             f"{args.m} episodes of {args.steps} steps, the env plugins' action tables, a seeded random policy, epsilon 0.3, action "
+             "noise a tenth of the action range, state noise 0.2 % of the span in every dimension, starts uniform in the grid; "
+             f"times in ms: the better of {args.repeat} after one warm-up, device events around the whole call",
+             "loop: per step a query, the probe kernel's words, the plugin step and the mixing as torch ops; policy: the fused "
+             "deterministic rollout (pi_infer_rollout) of the same batch, policy ep-steps its steps; random: "
+             "controller='random' alone; ep-steps: steps actually taken by the stochastic rollout (episodes that ended stop)",
+             "",
+             f"{'config':30s} {'fused':>10s} {'loop':>10s} {'loop/fused':>10s} {'policy':>10s} {'random':>10s} {'ep-steps':>12s} "
+             f"{'policy ep-steps':>15s} {'ended':>6s} {'same bits':>9s}"]
+    for r in rows:
+        lines.append(f"{r['config'] + ' ' + r['env'] + ' ' + str(r['bins']) + '^' + str(r['D']):30s} "
+                     f"{r['fused_ms']:10.3f} {r['loop_ms']:10.3f} {r['loop_ms'] / r['fused_ms']:10.1f} {r['single_ms']:10.3f} "
+                     f"{r['random_ms']:10.3f} {r['episode_steps']:12d} {r['single_episode_steps']:15d} {r['terminated_share']:6.3f} "
+                     f"{str(r['same_bits']):>9s}")
+    lines += ["", "all timings per config (ms): " + "; ".join(
+        f"{r['config']} fused {[round(t, 3) for t in r['fused_ms_all']]} policy {[round(t, 3) for t in r['single_ms_all']]}" for r in rows)]
+    slower = [r["config"] for r in rows if r["fused_ms"] >= r["loop_ms"]]
+    lines += ["", "the fused kernel is faster than its own step-by-step loop on every config" if not slower else
+              f"the fused kernel is NOT faster than its own step-by-step loop on: {', '.join(slower)}", "",
+              "registers and scratch (hipcc -Rpass-analysis=kernel-resource-usage, the translation unit of pi_infer_set_stochastic):"]
+    for config, (env, bins) in CONFIGS.items():
+        for fn, k in sorted(greedy_usage(env, bins, "PI_STOCHASTIC", "pi_stochastic_kernels.hip").items()):
+            lines.append(f"  {config} {env:24s} {fn:30s} VGPRs {k['vgpr']:4d}  scratch {k['scratch']} bytes/lane")
     out.write_text("\n".join(lines) + "\n")
     print(out.read_text())
 
@@ -448,11 +604,14 @@ def main():
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--hybrid", action="store_true")
     ap.add_argument("--greedy", action="store_true")
+    ap.add_argument("--stochastic", action="store_true")
     ap.add_argument("--config", choices=list(CONFIGS), default="c3")
     ap.add_argument("--m", type=int, default=4096)
     args = ap.parse_args()
     if args.greedy:
         (greedy_child if args.child else greedy_driver)(args)
+    elif args.stochastic:
+        (stochastic_child if args.child else stochastic_driver)(args)
     elif args.hybrid:
         (hybrid_child if args.child else hybrid_driver)(args)
     else:

@@ -24,6 +24,13 @@ arbitrary continuous state, in their arithmetic, not this helper's — and ``gre
 ``DevicePolicy.set_greedy`` + ``DevicePolicy.greedy`` / ``DevicePolicy.rollout(controller="greedy")`` are their device
 twins, one HIP kernel launch each (``pi_infer_greedy``, ``pi_infer_rollout_greedy``), same bits.  It needs only V.
 
+Stochastic rollouts (the reference's ``evaluate_random()`` baseline, and beyond it): ``stochastic_rollout`` is the closed
+loop with epsilon-random actions, action noise and state noise drawn from Philox4x32-10 (``philox4x32``) keyed by
+(seed; episode, step, draw block) — ``random_words`` — so the draws need no state and do not depend on how a batch is
+cut; ``DevicePolicy.set_stochastic`` + ``DevicePolicy.rollout(epsilon=..., action_noise=..., state_noise=..., seed=...,
+first_episode=...)`` / ``rollout(controller="random")`` / ``DevicePolicy.random_words`` are the device twins, one HIP
+kernel launch each (``pi_infer_rollout_stochastic``, ``pi_infer_random_words``), same bits.
+
 Semantics kept from the reference helper (they differ slightly from the training kernels):
 the POINT is clamped to the bounds (not the cell coordinate), cell widths are float64
 ``(hi - lo) / (shape - 1)``, corners follow the rows of ``corner_bits`` (MSB-first
@@ -70,6 +77,7 @@ class DevicePolicy:
         # the action table on its own: the value-greedy controller needs no policy (set_greedy)
         self._action_space = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
         self._greedy_actions = None                # the table of the last set_greedy; None: no greedy module
+        self._stochastic_actions = None            # the table of the last set_stochastic; None: no stochastic module
         if self._has_policy:
             self._engine.set_policy(policy, action_space)
             self._n_actions = len(np.asarray(action_space))
@@ -113,6 +121,7 @@ class DevicePolicy:
         self._has_dynamics = True
         self._dynamics_serial = getattr(self, "_dynamics_serial", 0) + 1      # HybridPolicy rebuilds its module after this
         self._greedy_actions = None                                           # the library dropped the greedy module
+        self._stochastic_actions = None                                       # ... and the stochastic one
         return log
 
     def _rollout_buffers(self, states, steps, record_every, need_policy=True):
@@ -141,7 +150,8 @@ class DevicePolicy:
         traj = torch.empty((steps // every + 1, m, self.D), dtype=torch.float32, device=self.device) if every else None
         return on_device, d_start, m, steps, every, final, ret, length, term, traj
 
-    def rollout(self, states, steps, gamma=1.0, record_every=0, controller="policy", lookahead_gamma=None):
+    def rollout(self, states, steps, gamma=1.0, record_every=0, controller="policy", lookahead_gamma=None, *,
+                epsilon=0.0, action_noise=0.0, state_noise=None, seed=0, first_episode=0):
         """Closed-loop episodes from ``states`` (m, D) in ONE kernel launch: per step the interpolated action (what
         calling this object returns for the state, same bits) and the plugin's ``step_dynamics``; an episode whose
         step reports `done` keeps the state it reached.  ``returns`` accumulates ``ret + disc * r`` in float32,
@@ -150,21 +160,47 @@ class DevicePolicy:
         A float32 tensor on this device in -> torch tensors on the device out; a numpy array in -> numpy out.
         ``controller="greedy"``: per step the action ``greedy`` returns for the state with the discount
         ``lookahead_gamma`` (required; a property of the solution, not the ``gamma`` the return is summed with) instead
-        of the interpolated one — after ``set_greedy``, no policy table needed; everything else is the same."""
-        if controller not in ("policy", "greedy"):
-            raise ValueError(f"controller must be 'policy' or 'greedy', not {controller!r}")
+        of the interpolated one — after ``set_greedy``, no policy table needed; everything else is the same.
+        Stochastic rollouts (after ``set_stochastic``; the device twin of the module's ``stochastic_rollout``, same bits):
+        ``epsilon`` in [0, 1] is the probability that a step takes a uniformly random action of the table instead of the
+        policy's; ``action_noise >= 0`` adds ``action_noise * u``, u in [-1, 1), to the action and clamps it to the
+        table's extremes; ``state_noise`` (one value or D, >= 0) adds ``state_noise[d] * u_d`` to the successor of every
+        step that is not `done`.  The draws are a function of (``seed``, ``first_episode`` + the episode's row, step)
+        alone: the same arguments give the same bits, and a batch cut into several calls with the matching
+        ``first_episode`` gives the results of one.  ``controller="random"`` is ``epsilon = 1``, the random-policy
+        baseline; it needs no policy table.  With all five at their defaults this is the deterministic rollout."""
+        if controller not in ("policy", "greedy", "random"):
+            raise ValueError(f"controller must be 'policy', 'greedy' or 'random', not {controller!r}")
         greedy = controller == "greedy"
+        if controller == "random":
+            if float(epsilon) not in (0.0, 1.0):
+                raise ValueError("controller='random' is epsilon = 1: give no other epsilon with it")
+            epsilon = 1.0
+        explore_threshold(epsilon)                  # raises outside [0, 1]
+        a_noise = float(_checked_action_noise(action_noise))
+        s_noise = _noise_vector(state_noise, self.D) if state_noise is not None else None
+        stochastic = controller == "random" or float(epsilon) != 0.0 or a_noise != 0.0 or \
+            (s_noise is not None and bool(s_noise.any()))
+        if greedy and stochastic:
+            raise ValueError("controller='greedy' takes no epsilon, action_noise or state_noise: a stochastic greedy "
+                             "controller does not exist")
         if greedy and lookahead_gamma is None:
             raise ValueError("controller='greedy' needs lookahead_gamma, the discount the value function was solved with")
         if greedy and getattr(self, "_greedy_actions", None) is None:
             raise RuntimeError("the greedy controller needs set_greedy() (again after every set_dynamics)")
+        if stochastic and getattr(self, "_stochastic_actions", None) is None:
+            raise RuntimeError("a stochastic rollout needs set_stochastic() (again after every set_dynamics)")
         on_device, d_start, m, steps, every, final, ret, length, term, traj = \
-            self._rollout_buffers(states, steps, record_every, need_policy=not greedy)
+            self._rollout_buffers(states, steps, record_every, need_policy=not greedy and float(epsilon) != 1.0)
         outs = dict(d_final=final.data_ptr(), d_return=ret.data_ptr(), d_length=length.data_ptr(),
                     d_terminated=term.data_ptr(), d_traj=traj.data_ptr() if every else 0, traj_every=every,
                     stream=self._stream())
         if greedy:
             self._engine.rollout_greedy(d_start.data_ptr(), m, steps, lookahead_gamma, gamma, **outs)
+        elif stochastic:
+            self._engine.rollout_stochastic(d_start.data_ptr(), m, steps, gamma, epsilon=epsilon, action_noise=a_noise,
+                                            state_noise=s_noise, seed=int(seed) & (2 ** 64 - 1),
+                                            first_episode=int(first_episode) & (2 ** 64 - 1), **outs)
         else:
             self._engine.rollout(d_start.data_ptr(), m, steps, gamma, **outs)
         term = term != 0
@@ -195,6 +231,33 @@ class DevicePolicy:
         log = self._engine.set_greedy(acts)
         self._greedy_actions = acts
         return log
+
+    def set_stochastic(self, action_space=None) -> str:
+        """Build the stochastic rollout kernels — ``rollout(epsilon=..., action_noise=..., state_noise=...)`` and
+        ``controller="random"`` — through the plugin of ``set_dynamics``; exploring steps draw from ``action_space``
+        (default: the table the constructor was given), whose extremes clamp a noisy action.  Returns the compiler's
+        log.  Needs neither a policy table nor values.  ``set_dynamics`` drops it again."""
+        acts = self._action_space if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        if acts is None:
+            raise ValueError("set_stochastic needs an action table: this DevicePolicy was built without one")
+        if not getattr(self, "_has_dynamics", False):
+            raise RuntimeError("a stochastic rollout needs the env's dynamics: call set_dynamics(dynamics_src) first")
+        log = self._engine.set_stochastic(acts)
+        self._stochastic_actions = acts
+        return log
+
+    def random_words(self, seed, first_episode, m, step, block):
+        """The random stream the stochastic rollouts draw from, read on the device: the (m, 4) uint32 words of draw
+        block ``block`` at step ``step`` of the episodes ``first_episode + 0 .. m`` under ``seed`` (numpy) — the device
+        twin of the module's ``random_words``, same bits.  After ``set_stochastic``."""
+        if getattr(self, "_stochastic_actions", None) is None:
+            raise RuntimeError("random_words needs set_stochastic() (again after every set_dynamics)")
+        torch = self._torch
+        m = int(m)
+        out = torch.empty((m, 4), dtype=torch.int32, device=self.device)
+        self._engine.random_words(int(seed) & (2 ** 64 - 1), int(first_episode) & (2 ** 64 - 1), m, step, block,
+                                  out.data_ptr(), stream=self._stream())
+        return out.cpu().numpy().view(np.uint32)
 
     def greedy(self, states, gamma, q_values=False):
         """The greedy one-step lookahead at ``states`` (m, D) in ONE kernel launch — the device twin of the module's
@@ -578,3 +641,147 @@ def greedy_rollout(step, states, steps, value_function, action_space, bounds_low
     tables = (value_function, action_space, bounds_low, bounds_high, grid_shape, strides, lookahead_gamma)
     return RolloutResult(*_closed_loop(step, states, steps, gamma, record_every,
                                        lambda live, pts: greedy_action(step, pts, *tables)[1]))
+
+
+# ── the random stream of the stochastic rollouts (csrc/pi_stochastic_kernels.hip), same bits ──────────────────────────
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 as published (Salmon et al., SC'11), vectorised: ``counter`` (..., 4) and ``key`` (..., 2) uint32
+    words (broadcast against each other) -> (..., 4) uint32 words."""
+    c = np.asarray(counter, dtype=np.uint32)
+    k = np.asarray(key, dtype=np.uint32)
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).astype(np.uint64) for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape).astype(np.uint64) for i in range(2))
+    for r in range(10):
+        p0, p1 = _PHILOX_M0 * c0, _PHILOX_M1 * c2             # 32 x 32 -> 64 bits: exact in uint64
+        kr0 = (k0 + np.uint64((_PHILOX_W0 * r) & 0xFFFFFFFF)) & _U32
+        kr1 = (k1 + np.uint64((_PHILOX_W1 * r) & 0xFFFFFFFF)) & _U32
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ kr0, p1 & _U32, (p0 >> np.uint64(32)) ^ c3 ^ kr1, p0 & _U32
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def random_words(seed, first_episode, m, step, block):
+    """The stream of the stochastic rollouts: the (m, 4) uint32 words of draw block ``block`` at step ``step`` for the
+    episodes ``first_episode + 0 .. m`` under ``seed`` — key = (low, high 32 bits of the uint64 seed), counter = (low,
+    high 32 bits of the uint64 episode number, step, block).  The twin of ``DevicePolicy.random_words``."""
+    return _episode_words(seed, _episode_numbers(first_episode, np.arange(int(m))), step, block)
+
+
+def _episode_numbers(first_episode, rows):
+    """first_episode + rows as uint64 (wrapping at 2^64, as the kernel's addition does)."""
+    with np.errstate(over="ignore"):
+        return np.uint64(int(first_episode) & (2 ** 64 - 1)) + np.asarray(rows).astype(np.uint64)
+
+
+def _episode_words(seed, episodes, step, block):
+    seed = int(seed) & (2 ** 64 - 1)
+    e = np.asarray(episodes, dtype=np.uint64)
+    counter = np.empty(e.shape + (4,), np.uint32)
+    counter[..., 0] = (e & _U32).astype(np.uint32)
+    counter[..., 1] = (e >> np.uint64(32)).astype(np.uint32)
+    counter[..., 2] = np.uint32(int(step) & 0xFFFFFFFF)
+    counter[..., 3] = np.uint32(int(block) & 0xFFFFFFFF)
+    return philox4x32(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32))
+
+
+def sym(words):
+    """A uint32 word as a float32 in [-1, 1): ``(float)((int)(x >> 8) - 8388608) * 2^-23``, every value exact."""
+    x = np.asarray(words, dtype=np.uint32)
+    return ((x >> np.uint32(8)).astype(np.int32) - np.int32(8388608)).astype(np.float32) * np.float32(2.0 ** -23)
+
+
+def explore_threshold(epsilon) -> int:
+    """eps24 of the exploration coin — a step explores iff ``(x0 >> 8) < eps24`` — from the float32 ``epsilon`` as the
+    library computes it: ``llrint((double)epsilon * 2^24)``.  0 never explores, 2^24 always does."""
+    eps = np.float32(epsilon)
+    if not (eps >= 0.0 and eps <= 1.0):
+        raise ValueError("epsilon must lie in [0, 1]")
+    return int(np.rint(np.float64(eps) * 16777216.0))
+
+
+def random_action_index(words, n_actions):
+    """The exploring step's action index: ``(uint32)(((uint64)x1 * n_actions) >> 32)``."""
+    return ((np.asarray(words, dtype=np.uint32).astype(np.uint64) * np.uint64(int(n_actions))) >> np.uint64(32)).astype(np.int64)
+
+
+def _noise_vector(state_noise, D):
+    """state_noise as D float32 values: None = none, one value = every dimension, or D values; finite, not negative."""
+    if state_noise is None:
+        return np.zeros(D, np.float32)
+    v = np.atleast_1d(np.asarray(state_noise, dtype=np.float32)).ravel()
+    if len(v) == 1:
+        v = np.repeat(v, D)
+    if len(v) != D:
+        raise ValueError(f"state_noise must hold one value or {D}")
+    if not (np.isfinite(v).all() and (v >= 0).all()):
+        raise ValueError("state_noise must be finite and not negative")
+    return np.ascontiguousarray(v)
+
+
+def _checked_action_noise(action_noise) -> np.float32:
+    a = np.float32(action_noise)
+    if not (np.isfinite(a) and a >= 0):
+        raise ValueError("action_noise must be finite and not negative")
+    return a
+
+
+def stochastic_rollout(step, states, steps, policy, action_space, bounds_low, bounds_high, grid_shape, strides,
+                       corner_bits, epsilon, action_noise, state_noise, seed, first_episode=0, gamma=1.0, record_every=0):
+    """Closed-loop episodes with epsilon-random actions, action noise and state noise on the CPU (numpy): the twin of
+    ``DevicePolicy.rollout(epsilon=..., action_noise=..., state_noise=..., seed=..., first_episode=...)``, same bits.
+    Episode ``i`` of the batch draws from the stream of episode number ``first_episode + i`` (``random_words``), so a
+    batch cut into several calls gives the results of one.  Per step of a running episode, in this order: the
+    interpolated action of ``rollout`` (``policy`` may be None when ``epsilon == 1``, the random-policy baseline); an
+    exploring step (block 0: ``(x0 >> 8) < explore_threshold(epsilon)``) takes ``action_space[random_action_index(x1)]``
+    instead; ``action_noise != 0`` adds ``action_noise * sym(x2)`` (multiply, then add) and clamps to the extremes of
+    ``action_space`` (no clamp otherwise); ``step``; then, unless the step was `done`, every dimension d with
+    ``state_noise[d] != 0`` of the successor gains ``state_noise[d] * sym(word d)`` (block 1 for d < 4, block 2 for
+    d = 4, 5) — not clamped, not wrapped, and it is the state the next step starts from and the trajectory records.
+    The bookkeeping, ``gamma`` and ``record_every`` are ``rollout``'s.  Returns a ``RolloutResult`` of numpy arrays."""
+    acts = np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+    if len(acts) < 1 or not np.isfinite(acts).all():
+        raise ValueError("action_space needs at least one action, all finite")
+    eps24 = explore_threshold(epsilon)
+    if policy is None and eps24 != 1 << 24:
+        raise ValueError("epsilon < 1 acts on the policy: a rollout without one needs epsilon = 1")
+    a_noise = _checked_action_noise(action_noise)
+    D = np.atleast_2d(states).shape[1]
+    s_noise = _noise_vector(state_noise, D)
+    a_min, a_max = acts.min(), acts.max()
+    tables = (policy, acts, bounds_low, bounds_high, grid_shape, strides, corner_bits)
+    now = {"t": -1, "episodes": None}                 # _closed_loop asks act() once per step, then steps those episodes
+
+    def act(live, pts):
+        now["t"] += 1
+        now["episodes"] = _episode_numbers(first_episode, live)
+        w = _episode_words(seed, now["episodes"], now["t"], 0)
+        explore = (w[:, 0] >> np.uint32(8)) < eps24
+        if policy is None:
+            a = np.zeros(len(live), np.float32)
+        else:
+            a = _interpolated_actions(pts, *tables)
+        a = np.where(explore, acts[random_action_index(w[:, 1], len(acts))], a).astype(np.float32)
+        if a_noise != 0:
+            with np.errstate(invalid="ignore"):
+                a = a + a_noise * sym(w[:, 2])
+                a = np.fmin(np.fmax(a, a_min), a_max)
+        return a
+
+    def noisy_step(pts, a):
+        nxt, rew, done = step(pts, a)
+        nxt, done = np.array(nxt, dtype=np.float32), np.asarray(done, bool)
+        if s_noise.any():
+            words = _episode_words(seed, now["episodes"], now["t"], 1)
+            if D > 4:
+                words = np.concatenate([words, _episode_words(seed, now["episodes"], now["t"], 2)], axis=1)
+            go = ~done
+            for d in range(D):
+                if s_noise[d] != 0:
+                    nxt[go, d] = nxt[go, d] + s_noise[d] * sym(words[go, d])
+        return nxt, rew, done
+    return RolloutResult(*_closed_loop(noisy_step, states, steps, gamma, record_every, act))
