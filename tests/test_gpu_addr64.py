@@ -68,18 +68,23 @@ def _assert_64_bit_form(eng, name):
     assert "PI_OFF32" in eng.kernel_source(envs.dynamics_source(name))
 
 
-def _grid(name, shape, order, cuda_device):
-    """Engine + what the oracle needs of the grid.  `order` None: the env's own (identity) order."""
+def _grid(name, shape, order, cuda_device, form64=True, options=()):
+    """Engine + what the oracle needs of the grid.  `order` None: the env's own (identity) order.  `form64`: the grid
+    must take the 64-bit addressing form (this module's grids; tests/test_gpu_offsets32.py passes False and states its
+    own band).  `options`: (selector, value) pairs set before pi_compile."""
     cls = envs.ENVS[name]
     D = cls._D
     bins = H.env_bins(name, shape)
     acts = np.asarray(cls.ACTIONS, np.float32)
     eng = _native.Engine(D, list(shape), [b.min() for b in bins], [b.max() for b in bins], bins, acts,
                          device=cuda_device.index or 0, order=order)
+    for what, value in options:
+        eng.set_option(what, value)
     eng.compile(envs.dynamics_source(name))
     ordr = tuple(range(D)) if order is None else tuple(order)
     assert eng.order == ordr
-    _assert_64_bit_form(eng, name)
+    if form64:
+        _assert_64_bit_form(eng, name)
     return SimpleNamespace(name=name, shape=tuple(shape), D=D, n=int(np.prod(shape, dtype=np.int64)), bins=bins, acts=acts,
                            eng=eng, order=order, ordr=ordr, mem_shape=[shape[d] for d in ordr],
                            gamma=float(np.float32(cls.CONFIG["gamma"])), chk=H.oracle_for(name), meta=oracle.grid_metadata(bins))
@@ -272,6 +277,9 @@ def test_4d_sweeps_beyond_2_pow_30_states_on_a_ragged_grid(order, cuda_device):
     n, eng = g.n, g.eng
     assert n == 1_079_081_094 and n % 256 != 0
     s = _single_sweeps_and_samples(g, 7, None, cuda_device)
+    # 8 n >= 2^32: the whole-grid improvement sweep above read V, and the unit holds no table kernels to read anything else
+    assert eng.info(Info.PAIR_TABLE) == 0
+    assert "#define PI_PAIR_TABLE" not in eng.kernel_source(envs.dynamics_source(g.name))
     what = f"{g.name} {g.shape} order {g.ordr}"
     # a batch of 3 sweeps, residual asked of the last one only: sweeps 0 and 1 read no old value (need_old == false)
     d_A, d_B = s.d_V, s.d_Vn
