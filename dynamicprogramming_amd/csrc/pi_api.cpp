@@ -501,7 +501,8 @@ int pi_value_sweep(pi_handle* h, const float* V, float* Vnew, int32_t* policy, c
 int pi_plan_schedule(pi_handle* h, int block, int64_t first, int64_t count, int64_t total, int chunks_per_workgroup,
                      uint64_t* out6) {
     if (!h || !out6) return fail("null argument");
-    if (block < 64 || block > 1024 || (block & (block - 1)) || chunks_per_workgroup < 1 || chunks_per_workgroup > 64 ||
+    // block: any whole number of waves, like the sizes the knobs accept for the sweeps
+    if (block < 64 || block > 1024 || block % 64 != 0 || chunks_per_workgroup < 1 || chunks_per_workgroup > 64 ||
         first < 0 || count < 1 || total < 0)
         return fail("pi_plan_schedule: bad launch shape");
     Sched sc;

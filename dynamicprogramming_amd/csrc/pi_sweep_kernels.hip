@@ -61,7 +61,7 @@
 // ties, NaN never wins).
 
 #define PI_C (1 << PI_D)
-// Threads per workgroup = states per chunk, per kernel family (generated: 256, 512 or 1024).
+// Threads per workgroup = states per chunk, per kernel family (generated: 256, 512 or 1024; the knobs: any multiple of 64 in 256..1024).
 // Big workgroups put the gathers of 4-16 adjacent waves behind ONE vector L1: their corner rows
 // overlap, which is worth 8 % on the 80^4 evaluation sweep (profiles/r02/block_cpw_sweep.txt).
 #ifndef PI_BLOCK_EVAL
@@ -492,7 +492,7 @@ __device__ __forceinline__ void pi_state_coords(unsigned int s, const float* lds
 }
 
 // ---- workgroup -> chunk schedule ---------------------------------------------------
-// A workgroup sweeps `cpw` consecutive 256-state chunks (a "group").  Workgroups are dealt
+// A workgroup sweeps `cpw` consecutive chunks of BLOCK states (a "group").  Workgroups are dealt
 // round-robin over the 8 XCDs (blockIdx % 8 shares an L2: tools/xcc_probe.hip), so XCD x is given
 // the contiguous run of groups [x * span, (x + 1) * span): every private L2 sees one slab of V,
 // and because the dispatcher starts workgroups in index order the states in flight on an XCD
@@ -507,8 +507,8 @@ __device__ __forceinline__ void pi_state_coords(unsigned int s, const float* lds
 template <int BLOCK>
 __device__ __forceinline__ bool pi_first_chunk(long long count, int cpw, long long& chunk0,
                                                long long& n_chunks) {
-    static_assert((BLOCK & (BLOCK - 1)) == 0, "chunk size must be a power of two (shift, not divide)");
-    n_chunks = (count + BLOCK - 1) / BLOCK;
+    static_assert(BLOCK % 64 == 0 && BLOCK >= 64, "chunk size must be a whole number of waves");
+    n_chunks = (count + BLOCK - 1) / BLOCK;             // by a compile-time constant: a shift where BLOCK is a power of two
     const unsigned int span = gridDim.x / PI_NXCD;
     const unsigned int x = blockIdx.x % PI_NXCD, j = blockIdx.x / PI_NXCD;
     const unsigned int g = x * span + j;

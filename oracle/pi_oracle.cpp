@@ -92,7 +92,10 @@ inline void interp(const float* s, const float* lo, const float* hi,
     float frac[PI_D];
     for (int d = 0; d < PI_D; ++d) {
         float n = (s[d] - lo[d]) / (hi[d] - lo[d]) * (float)(g[d] - 1);
-        n = fmaxf(0.0f, fminf(n, (float)(g[d] - 1)));
+        /* fmaxf(0.0f, fminf(n, g - 1)) with the zero's sign pinned: for n == -0.0f C lets fmaxf return either zero (x86-64
+         * gives -0.0f here), the devices' max returns +0.0f (-0 < +0) and so does this.  fminf has dropped a NaN already. */
+        n = fminf(n, (float)(g[d] - 1));
+        n = n > 0.0f ? n : 0.0f;
         i[d] = min((int)n, g[d] - 2);
         frac[d] = n - (float)i[d];
     }

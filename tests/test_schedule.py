@@ -84,7 +84,7 @@ def test_every_group_is_taken_exactly_once_whatever_the_period_and_the_range(see
     eng = _engine("cartpole", (31, 23, 29, 19))
     n = eng.info(Info.N_STATES)
     for _ in range(40):
-        block = int(rng.choice([64, 256, 512, 1024]))
+        block = int(rng.choice([64, 256, 320, 448, 512, 768, 960, 1024]))    # every whole number of waves is a chunk size
         cpw = int(rng.integers(1, 5))
         period_states = int(rng.integers(block * cpw * 16, n // 2))
         eng.set_option(Option.STRIP_STATES, period_states)
