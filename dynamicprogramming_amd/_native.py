@@ -46,6 +46,13 @@ SIGNATURES = {
                                         ctypes.c_float, _vp, _vp]),
     "pi_value_sweep": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
                                       ctypes.c_float, _vp, _vp, _vp]),
+    "pi_set_disturbances": (ctypes.c_int, [_vp, ctypes.c_int, _f32p, _f32p, _f32p]),
+    "pi_expect_eval_sweeps": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_float, ctypes.c_int, _vp, _vp]),
+    "pi_expect_improve_sweep": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_float, _vp, _vp]),
+    "pi_expect_value_sweep": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_float, _vp, _vp, _vp]),
     "pi_reach_planes": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
     "pi_reach_depth_max": (ctypes.c_int, [_vp]),
     "pi_reach_units": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
@@ -146,6 +153,7 @@ class Info(enum.IntEnum):
     WHOLE_RUN_AVAILABLE = 34
     STRIP_STATES = 35
     PAIR_TABLE = 37
+    DISTURBANCES = 38
 
 
 class Option(enum.IntEnum):
@@ -436,6 +444,38 @@ class Engine:
     def value_sweep(self, V, Vnew, policy, term, s_begin, s_end, gamma, d_delta=0, d_changed=0, stream=0):
         _check(lib().pi_value_sweep(self._h, V, Vnew, policy, term, s_begin, s_end, gamma,
                                     d_delta or None, d_changed or None, stream or None), "pi_value_sweep")
+
+    # -- noise-aware solving: the expected backup over a disturbance set -------
+    def set_disturbances(self, action_offsets, state_offsets, weights) -> int:
+        """Install the disturbance set of the expectation sweeps (pi_set_disturbances; host arrays): K weights, K action
+        offsets or None (zeros), (K, D) state offsets in the order of step_dynamics' arguments or None (zeros).
+        `weights=None` drops the set.  The first call after compile() builds the expectation kernels (a compile check on
+        a host-only engine).  Returns K in use."""
+        if weights is None:
+            _check(lib().pi_set_disturbances(self._h, 0, None, None, None), "pi_set_disturbances")
+            return 0
+        w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+        K = len(w)
+        da = None if action_offsets is None else np.ascontiguousarray(action_offsets, dtype=np.float32).ravel()
+        dx = None if state_offsets is None else np.ascontiguousarray(state_offsets, dtype=np.float32).reshape(-1)
+        if K == 0 or (da is not None and len(da) != K) or (dx is not None and len(dx) != K * self.D):
+            raise ValueError(f"a disturbance set needs K >= 1 weights, K action offsets and (K, {self.D}) state offsets")
+        _check(lib().pi_set_disturbances(self._h, K, None if da is None else da.ctypes.data_as(_f32p),
+                                         None if dx is None else dx.ctypes.data_as(_f32p), w.ctypes.data_as(_f32p)),
+               "pi_set_disturbances")
+        return self.info(Info.DISTURBANCES)
+
+    def expect_eval_sweeps(self, Va, Vb, policy, term, s_begin, s_end, gamma, n_sweeps, d_delta=0, stream=0):
+        _check(lib().pi_expect_eval_sweeps(self._h, Va, Vb, policy, term, s_begin, s_end, gamma, n_sweeps,
+                                           d_delta or None, stream or None), "pi_expect_eval_sweeps")
+
+    def expect_improve_sweep(self, V, policy, term, s_begin, s_end, gamma, d_changed=0, stream=0):
+        _check(lib().pi_expect_improve_sweep(self._h, V, policy, term, s_begin, s_end, gamma,
+                                             d_changed or None, stream or None), "pi_expect_improve_sweep")
+
+    def expect_value_sweep(self, V, Vnew, policy, term, s_begin, s_end, gamma, d_delta=0, d_changed=0, stream=0):
+        _check(lib().pi_expect_value_sweep(self._h, V, Vnew, policy, term, s_begin, s_end, gamma,
+                                           d_delta or None, d_changed or None, stream or None), "pi_expect_value_sweep")
 
     def reach_planes(self, term, s_begin, s_end, d_bitmap, stream=0, dim=0):
         _check(lib().pi_reach_planes(self._h, term, s_begin, s_end, int(dim), d_bitmap, stream or None),

@@ -99,20 +99,14 @@ namespace {
 unsigned int* delta_slots(pi_handle* h) { return h->d_slots; }
 unsigned int* changed_slots(pi_handle* h) { return h->d_slots + kSlots; }
 
-// empty range: zero whichever of the outputs were given, nothing to launch
-int zero_outputs(float* d_delta, uint32_t* d_changed, hipStream_t st) {
-    if (d_delta) PI_HIP(hipMemsetAsync(d_delta, 0, sizeof(float), st));
-    if (d_changed) PI_HIP(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), st));
-    return 0;
-}
-
 // Everything the handle owns on its device (pi_destroy, and pi_create when an allocation fails)
 void free_device_state(pi_handle* h) {
     drop_graphs(h);
     if (h->module) (void)hipModuleUnload(h->module);
     if (h->module_push) (void)hipModuleUnload(h->module_push);
+    if (h->module_expect) (void)hipModuleUnload(h->module_expect);
     for (void* p : {(void*)h->d_tab, (void*)h->d_slots, (void*)h->d_live, (void*)h->d_eval_list, (void*)h->d_eval_cursor,
-                    h->d_flow, h->d_xcd, (void*)h->d_pairs})
+                    h->d_flow, h->d_xcd, (void*)h->d_pairs, (void*)h->d_dist})
         if (p) (void)hipFree(p);
 }
 
@@ -231,6 +225,13 @@ int pack_pair_table(pi_handle* h, const float* V, hipStream_t st, const float** 
 }
 
 }  // namespace
+
+// empty range: zero whichever of the outputs were given, nothing to launch
+int pi::zero_outputs(float* d_delta, uint32_t* d_changed, hipStream_t st) {
+    if (d_delta) PI_HIP(hipMemsetAsync(d_delta, 0, sizeof(float), st));
+    if (d_changed) PI_HIP(hipMemsetAsync(d_changed, 0, sizeof(uint32_t), st));
+    return 0;
+}
 
 int pi::check_ready(const pi_handle* h) {
     if (!h) return fail("null handle");
@@ -664,6 +665,7 @@ int64_t pi_info(pi_handle* h, int what) {
         case PI_INFO_WHOLE_RUN_AVAILABLE: return (h->f_run_resident && h->use_resident) || (h->f_xcd && !h->xcd_off) ? 1 : 0;
         case PI_INFO_STRIP_STATES: return h->strip_states;
         case PI_INFO_PAIR_TABLE: return h->pair_last ? 1 : 0;
+        case PI_INFO_DISTURBANCES: return h->dist_k;
         default:
             if (what >= PI_INFO_RECIPROCAL_DIV && what < PI_INFO_RECIPROCAL_DIV + h->D)
                 return h->fastdiv[what - PI_INFO_RECIPROCAL_DIV];

@@ -1,6 +1,6 @@
 // pi_compile.cpp — from a handle to loaded kernels: the embedded device sources, the exhaustive check of the reciprocal
 // division, the generated translation unit (build_source), hipRTC with the on-disk code-object cache, and the modules
-// of a handle (symbol lookups, residency checks of the one-launch kernels, the push module built on demand).
+// of a handle (symbol lookups, residency checks of the one-launch kernels, the push and expectation modules built on demand).
 
 #include "pi_internal.h"
 
@@ -37,6 +37,10 @@ asm(".section .rodata\n"
     ".global pi_embedded_push\n"
     "pi_embedded_push:\n"
     ".incbin \"" PI_CSRC_DIR "/pi_push_kernels.hip\"\n"
+    ".byte 0\n"
+    ".global pi_embedded_expect\n"
+    "pi_embedded_expect:\n"
+    ".incbin \"" PI_CSRC_DIR "/pi_expect_kernels.hip\"\n"
     ".byte 0\n"
     ".text\n");
 
@@ -188,6 +192,8 @@ std::string build_source(const pi_handle* h, const char* dynamics_src, bool fast
 }
 
 int load_module(pi_handle* h, const std::vector<char>& image) {
+    h->dist_k = 0;                 // a new unit: the expectation module and the disturbance set go with the old one
+    h->expect_built = false;
     if (h->device < 0) return 0;   // host-only handle: compile check only
     pi::DeviceGuard guard(h->device);
     pi::drop_graphs(h);
@@ -200,6 +206,11 @@ int load_module(pi_handle* h, const std::vector<char>& image) {
         h->module_push = nullptr;
         h->f_eval_push = nullptr;
         h->f_reach_pairs = nullptr;
+    }
+    if (h->module_expect) {
+        PI_HIP(hipModuleUnload(h->module_expect));
+        h->module_expect = nullptr;
+        h->f_expect_eval = h->f_expect_improve = h->f_expect_value = nullptr;
     }
     PI_HIP(hipModuleLoadData(&h->module, image.data()));
     PI_HIP(hipModuleGetFunction(&h->f_eval, h->module, "pi_eval_sweep_kernel"));
@@ -280,6 +291,25 @@ int ensure_push_module(pi_handle* h) {
     PI_HIP(hipModuleLoadData(&h->module_push, image.data()));
     PI_HIP(hipModuleGetFunction(&h->f_eval_push, h->module_push, "pi_eval_push_kernel"));
     if (h->D >= 3) PI_HIP(hipModuleGetFunction(&h->f_reach_pairs, h->module_push, "pi_reach_pairs_kernel"));
+    return 0;
+}
+
+// The handle's third module: the same translation unit + csrc/pi_expect_kernels.hip, built (hipRTC, same flags, same
+// cache) by the first pi_set_disturbances after pi_compile.  A handle that never plans for noise never pays for it.
+int ensure_expect_module(pi_handle* h) {
+    if (h->expect_built) return 0;
+    if (!h->compiled || h->dynamics_src.empty()) return fail("ensure_expect_module: pi_compile has not run on this handle");
+    std::vector<char> image;
+    const std::string src = build_source(h, h->dynamics_src.c_str(), h->fast_first) + "// ---- expected backup over a disturbance set ----\n" + pi_embedded_expect + "\n";
+    if (compile_image(src, h->has_cache_dir ? h->cache_dir.c_str() : nullptr, nullptr, 0, image, nullptr)) return 1;
+    if (h->device >= 0) {                  // host-only handle: compile check only
+        DeviceGuard guard(h->device);
+        PI_HIP(hipModuleLoadData(&h->module_expect, image.data()));
+        PI_HIP(hipModuleGetFunction(&h->f_expect_eval, h->module_expect, "pi_expect_eval_kernel"));
+        PI_HIP(hipModuleGetFunction(&h->f_expect_improve, h->module_expect, "pi_expect_improve_kernel"));
+        PI_HIP(hipModuleGetFunction(&h->f_expect_value, h->module_expect, "pi_expect_value_kernel"));
+    }
+    h->expect_built = true;
     return 0;
 }
 

@@ -11,6 +11,7 @@
 //   pi_resample.cpp   the inference handle's solution interpolated onto another grid (grid continuation)
 //   pi_greedy.cpp     value-greedy control on the inference handle: one-step lookahead on V, queries and rollouts
 //   pi_stochastic.cpp stochastic rollouts on the inference handle: random baseline, epsilon-random actions, noise (Philox)
+//   pi_expect.cpp     the expected backup over a disturbance set: pi_set_disturbances and the pi_expect_* sweeps
 #pragma once
 
 #include "pi_knobs.h"
@@ -144,6 +145,7 @@ extern "C" const char pi_embedded_kernels[];
 extern "C" const char pi_embedded_onelaunch[];
 extern "C" const char pi_embedded_math[];
 extern "C" const char pi_embedded_push[];
+extern "C" const char pi_embedded_expect[];
 extern "C" const char pi_embedded_rollout[];      // pi_rollout.cpp
 
 struct pi_handle {
@@ -167,6 +169,16 @@ struct pi_handle {
     hipModule_t module_push = nullptr;
     hipFunction_t f_eval_push = nullptr, f_reach_pairs = nullptr;
     std::string dynamics_src, cache_dir; // what pi_compile was given (for the second module)
+    // third module, built by the first pi_set_disturbances after pi_compile from the same translation unit +
+    // csrc/pi_expect_kernels.hip (ensure_expect_module); expect_built: that build went through (host-only handles: it
+    // compiled).  The disturbance set in use (pi_expect.cpp): dist_k points (0: none), d_dist their table, 64 rows of
+    // {da, dx_0 .. dx_{D-1}, p} (owned, allocated once), dist_a_min / _a_max the extremes of the action table
+    hipModule_t module_expect = nullptr;
+    hipFunction_t f_expect_eval = nullptr, f_expect_improve = nullptr, f_expect_value = nullptr;
+    bool expect_built = false;
+    int dist_k = 0;
+    float* d_dist = nullptr;
+    float dist_a_min = 0.0f, dist_a_max = 0.0f;
     bool has_cache_dir = false;
     bool fast_first = true;              // the unit holds the plugin's common-path instantiation too (pi_compile clears it for a plugin that cannot take that form)
     hipFunction_t f_eval = nullptr, f_eval_live = nullptr, f_policy_list = nullptr, f_scan_slots = nullptr, f_mask_list = nullptr, f_improve = nullptr, f_improve_live = nullptr, f_value = nullptr, f_finalize = nullptr,
@@ -308,6 +320,7 @@ int launch_eval(pi_handle* h, const float* V, float* Vnew, const int32_t* policy
                 int64_t s_begin, int64_t s_end, float gamma, bool want_delta, LaunchTo to,
                 bool keep_terminals = false);
 int finalize(pi_handle* h, float* d_delta, uint32_t* d_changed, LaunchTo to);
+int zero_outputs(float* d_delta, uint32_t* d_changed, hipStream_t st);   // a sweep over an empty range: zero the outputs given
 // The live-state list of pi_prepare_mask.  live_usable: a list is in use, `term` is the mask it was built from and
 // [s_begin, s_end) lies inside the range it covers.
 // live_span: the run of list entries whose states lie in [s_begin, s_end).  launch_eval_live: one evaluation sweep
@@ -328,6 +341,7 @@ Grid2 plan_launch(const pi_handle* h, int block, int64_t first, int64_t count, i
 // pi_eval_push_kernel over `count` entries of `list` with their destination masks: V'(s) goes to Vnew[s] and to
 // peers[j][s] for every bit j of dest[k] (ensure_push_module builds the kernel the first time)
 int ensure_push_module(pi_handle* h);                                      // pi_compile.cpp
+int ensure_expect_module(pi_handle* h);                                    // pi_compile.cpp: the module of pi_set_disturbances
 unsigned launch_blocks(int block, int64_t count, int cpw);                 // slab schedule: workgroups for `count` units
 int launch_eval_push(pi_handle* h, const float* V, float* Vnew, const int32_t* policy, const int32_t* list,
                      const uint8_t* dest, float* const* d_peers, int n_peers, int64_t count, float gamma, bool want_delta,

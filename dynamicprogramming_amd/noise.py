@@ -1,0 +1,208 @@
+"""
+Noise-aware solving: disturbance sets and the numpy twins of the expectation sweeps.
+
+The solvers back up the single deterministic successor, ``Q(s, a) = r + gamma * E[V](f(s, a))``.  With a
+``Disturbances`` set installed (``solver.set_disturbances``) every sweep takes the expectation over K points instead,
+
+    ``Q(s, a) = sum_k p_k * [ r_k + gamma * E[V](f(s, a (+) da_k) + dx_k) ]``
+
+on the device (csrc/pi_expect_kernels.hip; include/pi_mi355.h at ``pi_set_disturbances`` is the definition).  The
+functions below restate that definition in numpy, bit for bit, on any batched ``step`` callable — the one
+``utils.barycentric.rollout`` takes: ``step(states (m, D), actions (m,)) -> (next (m, D), reward (m,), done (m,))``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from utils.barycentric import _expected_value, _fmaf
+
+MAX_POINTS = 64
+
+
+class Disturbances:
+    """K disturbance points: ``action_offsets`` (K,) or None = zeros, ``state_offsets`` (K, D) in the order of
+    ``step_dynamics``' arguments, ``weights`` (K,).  float32 throughout.  Validated as the library validates them:
+    1 <= K <= 64, every value finite, weights >= 0 and ``|sum - 1| <= 1e-4`` with the sum in float64."""
+
+    def __init__(self, action_offsets, state_offsets, weights):
+        w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+        K = len(w)
+        if not 1 <= K <= MAX_POINTS:
+            raise ValueError(f"a disturbance set holds 1 to {MAX_POINTS} points, not {K}")
+        dx = np.ascontiguousarray(state_offsets, dtype=np.float32)
+        if dx.ndim != 2 or len(dx) != K:
+            raise ValueError(f"state_offsets must be (K, D) = ({K}, D), not {dx.shape}")
+        da = np.zeros(K, np.float32) if action_offsets is None else np.ascontiguousarray(action_offsets, dtype=np.float32).ravel()
+        if len(da) != K:
+            raise ValueError(f"action_offsets must hold K = {K} values, not {len(da)}")
+        if not (np.isfinite(w).all() and np.isfinite(dx).all() and np.isfinite(da).all()):
+            raise ValueError("disturbance offsets and weights must be finite")
+        if (w < 0).any():
+            raise ValueError("disturbance weights must be >= 0")
+        total = float(w.astype(np.float64).sum())
+        if not abs(total - 1.0) <= 1e-4:
+            raise ValueError(f"disturbance weights must sum to 1 within 1e-4, not to {total!r}")
+        self.action_offsets, self.state_offsets, self.weights = da, dx, w
+
+    @property
+    def K(self) -> int:
+        return len(self.weights)
+
+    @property
+    def D(self) -> int:
+        return self.state_offsets.shape[1]
+
+    def table(self) -> np.ndarray:
+        """(K, D + 2) float32: columns da, dx_0 .. dx_{D-1}, p — the form ``save()`` archives."""
+        return np.ascontiguousarray(np.column_stack([self.action_offsets, self.state_offsets, self.weights]), dtype=np.float32)
+
+    @classmethod
+    def from_table(cls, table) -> "Disturbances":
+        t = np.asarray(table, dtype=np.float32)
+        return cls(t[:, 0], t[:, 1:-1], t[:, -1])
+
+    @classmethod
+    def none(cls, D: int) -> "Disturbances":
+        """The one-point zero set: the expectation sweeps then compute the deterministic backup, bit for bit."""
+        return cls(None, np.zeros((1, int(D)), np.float32), [1.0])
+
+    @classmethod
+    def uniform(cls, D: int, state_noise=None, action_noise: float = 0.0, points: int = 3) -> "Disturbances":
+        """The tensor Gauss-Legendre rule for the noise model of the stochastic rollouts — ``X * u``, u uniform on
+        [-1, 1), per noisy dimension and for the action: ``points`` nodes ``X * x_i`` (ascending) with weights
+        ``w_i / 2`` per noisy quantity.  ``state_noise``: None, one value for every dimension, or D values; a zero takes no
+        part.  The action is the slowest index and the last noisy dimension the fastest, so points with equal action
+        offsets are contiguous (the kernels step the dynamics once for them).  Weights are float32 of the float64
+        product.  ValueError when the rule has more than 64 points."""
+        D, points = int(D), int(points)
+        if points < 1:
+            raise ValueError("points must be >= 1")
+        noise = np.zeros(1) if state_noise is None else np.asarray(state_noise, np.float64).ravel()
+        if len(noise) not in (1, D):
+            raise ValueError(f"state_noise must hold one value or D = {D} values")
+        noise = np.broadcast_to(noise, (D,))
+        A = float(action_noise)
+        if not (np.isfinite(noise).all() and (noise >= 0).all() and np.isfinite(A) and A >= 0):
+            raise ValueError("noise amplitudes must be finite and >= 0")
+        axes = ([("a", A)] if A != 0.0 else []) + [(d, float(noise[d])) for d in range(D) if noise[d] != 0.0]
+        K = points ** len(axes)
+        if K > MAX_POINTS:
+            raise ValueError(f"{points} points over {len(axes)} noisy quantities are {K} disturbance points: more than {MAX_POINTS}")
+        x, w = np.polynomial.legendre.leggauss(points)
+        da, dx, p = np.zeros(K, np.float64), np.zeros((K, D), np.float64), np.ones(K, np.float64)
+        idx = np.indices((points,) * len(axes)).reshape(len(axes), K) if axes else np.zeros((0, 1), int)
+        for j, (which, amp) in enumerate(axes):
+            if which == "a":
+                da = amp * x[idx[j]]
+            else:
+                dx[:, which] = amp * x[idx[j]]
+            p = p * (w[idx[j]] / 2.0)
+        return cls(da.astype(np.float32), dx.astype(np.float32), p.astype(np.float32))
+
+
+def _tables(action_space, bounds_low, bounds_high, grid_shape, strides):
+    acts = np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+    return acts, (np.asarray(bounds_low, np.float32), np.asarray(bounds_high, np.float32),
+                  np.asarray(grid_shape, np.int32), np.asarray(strides, np.int32))
+
+
+def expected_q(step, states, actions, disturbances, value_function, action_space, bounds_low, bounds_high, grid_shape,
+               strides, gamma):
+    """``Q(s, a)`` of the module docstring for ``states`` (m, D) and action VALUES ``actions`` (m,) or a scalar; float32
+    (m,).  Per point in ascending k: ``a_k = a`` when ``da_k == 0``, else ``fmin(fmax(a + da_k, a_min), a_max)`` with
+    the extremes of ``action_space``; ``(s', r, done) = step(s, a_k)``; ``E = 0`` where done, elsewhere ``dx_k`` is added
+    to ``s'`` in every dimension where it is not zero and ``E`` is ``utils.barycentric._expected_value`` there;
+    ``q = r + gamma * E``; ``Q = p_0 * q_0``, then ``Q = fmaf(p_k, q_k, Q)``."""
+    pts = np.ascontiguousarray(np.atleast_2d(states), dtype=np.float32)
+    m = len(pts)
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(actions, np.float32), (m,)))
+    acts, grid = _tables(action_space, bounds_low, bounds_high, grid_shape, strides)
+    a_min, a_max = acts.min(), acts.max()
+    g32 = np.float32(gamma)
+    Q = np.zeros(m, np.float32)
+    for k in range(disturbances.K):
+        da = disturbances.action_offsets[k]
+        ak = a if da == 0 else np.fmin(np.fmax(a + da, a_min), a_max)
+        nxt, rew, done = step(pts, ak)
+        nxt, done = np.asarray(nxt, np.float32), np.asarray(done, bool)
+        e = np.zeros(m, np.float32)
+        if not done.all():
+            p = nxt[~done].copy()
+            for d in range(pts.shape[1]):
+                dx = disturbances.state_offsets[k, d]
+                if dx != 0:
+                    p[:, d] = p[:, d] + dx
+            e[~done] = _expected_value(p, value_function, *grid)
+        with np.errstate(over="ignore", invalid="ignore"):
+            q = np.asarray(rew, np.float32) + g32 * e
+            Q = disturbances.weights[k] * q if k == 0 else _fmaf(disturbances.weights[k], q, Q)
+    return Q
+
+
+def _range(n, s_begin, s_end, term):
+    s_end = n if s_end is None else int(s_end)
+    live = np.arange(int(s_begin), s_end)
+    return live if term is None else live[~np.asarray(term, bool)[live]], s_end
+
+
+def _residual(new, old):
+    """max |new - old| as the kernels fold it: from 0, a NaN never raises it."""
+    with np.errstate(invalid="ignore"):
+        d = np.abs(new - old)
+    return np.float32(np.fmax.reduce(d, initial=np.float32(0.0))) if len(d) else np.float32(0.0)
+
+
+def expected_eval(step, states, policy, value_function, term, disturbances, action_space, bounds_low, bounds_high,
+                  grid_shape, strides, gamma, s_begin=0, s_end=None, out=None):
+    """One expectation evaluation sweep over the grid nodes ``states`` (n, D) in [s_begin, s_end):
+    ``V'(s) = Q(s, action_space[policy[s]])``, terminal states (``term``, or None for none) copy their value.  Returns
+    ``(V', residual)``: V' is ``out`` (or a copy of V) with the range written, the residual ``max |V' - V|`` over it."""
+    V = np.asarray(value_function, np.float32).ravel()
+    new = V.copy() if out is None else out
+    live, s_end = _range(len(V), s_begin, s_end, term)
+    acts = np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+    new[s_begin:s_end] = V[s_begin:s_end]
+    if len(live):
+        new[live] = expected_q(step, states[live], acts[np.asarray(policy)[live]], disturbances, V, acts, bounds_low,
+                               bounds_high, grid_shape, strides, gamma)
+    return new, _residual(new[s_begin:s_end], V[s_begin:s_end])
+
+
+def _argmax(step, states, live, disturbances, V, acts, grid, gamma):
+    best = np.zeros(len(live), np.int32)
+    best_q = np.full(len(live), np.float32(-1.0e30), np.float32)
+    for a, u in enumerate(acts):
+        q = expected_q(step, states[live], u, disturbances, V, acts, *grid, gamma)
+        with np.errstate(invalid="ignore"):
+            wins = q > best_q
+        best_q = np.where(wins, q, best_q)
+        best = np.where(wins, np.int32(a), best)
+    return best, best_q
+
+
+def expected_improve(step, states, policy, value_function, term, disturbances, action_space, bounds_low, bounds_high,
+                     grid_shape, strides, gamma, s_begin=0, s_end=None):
+    """One expectation improvement sweep over [s_begin, s_end): ``policy[s] = argmax_a Q(s, a)``, strict ``>`` from
+    -1e30 over ascending action indices; terminal states keep their entry.  Returns ``(policy', entries changed)``."""
+    V = np.asarray(value_function, np.float32).ravel()
+    new = np.array(policy, dtype=np.int32, copy=True)
+    live, _ = _range(len(V), s_begin, s_end, term)
+    acts, grid = _tables(action_space, bounds_low, bounds_high, grid_shape, strides)
+    if len(live):
+        new[live], _ = _argmax(step, states, live, disturbances, V, acts, grid, gamma)
+    return new, int((new != np.asarray(policy)).sum())
+
+
+def expected_value_sweep(step, states, policy, value_function, term, disturbances, action_space, bounds_low, bounds_high,
+                         grid_shape, strides, gamma, s_begin=0, s_end=None, out=None):
+    """One expectation value-iteration sweep over [s_begin, s_end): ``expected_improve`` and ``V'(s) = max_a Q(s, a)`` at
+    once (terminal states copy their value and keep their entry).  Returns ``(V', policy', residual, entries changed)``."""
+    V = np.asarray(value_function, np.float32).ravel()
+    new_v = V.copy() if out is None else out
+    new_p = np.array(policy, dtype=np.int32, copy=True)
+    live, s_end = _range(len(V), s_begin, s_end, term)
+    acts, grid = _tables(action_space, bounds_low, bounds_high, grid_shape, strides)
+    new_v[s_begin:s_end] = V[s_begin:s_end]
+    if len(live):
+        new_p[live], new_v[live] = _argmax(step, states, live, disturbances, V, acts, grid, gamma)
+    return new_v, new_p, _residual(new_v[s_begin:s_end], V[s_begin:s_end]), int((new_p != np.asarray(policy)).sum())

@@ -209,6 +209,28 @@ class HipSweepBackend:
                                 s_begin, s_end, gamma, 0 if d_delta is None else d_delta.data_ptr(),
                                 0 if d_changed is None else d_changed.data_ptr(), self._stream())
 
+    # -- noise-aware solving: the expected backup over a disturbance set (noise.Disturbances; csrc/pi_expect_kernels.hip) --
+    def set_disturbances(self, disturbances) -> int:
+        """Install the set the expect_* sweeps take their expectation over (None drops it); returns K in use."""
+        if disturbances is None:
+            return self.engine.set_disturbances(None, None, None)
+        return self.engine.set_disturbances(disturbances.action_offsets, disturbances.state_offsets, disturbances.weights)
+
+    def expect_eval_sweeps(self, Va, Vb, policy, term, s_begin, s_end, gamma, n_sweeps, d_delta):
+        self.engine.expect_eval_sweeps(Va.data_ptr(), Vb.data_ptr(), policy.data_ptr(), self._ptr(term),
+                                       s_begin, s_end, gamma, n_sweeps,
+                                       0 if d_delta is None else d_delta.data_ptr(), self._stream())
+
+    def expect_improve_sweep(self, V, policy, term, s_begin, s_end, gamma, d_changed):
+        self.engine.expect_improve_sweep(V.data_ptr(), policy.data_ptr(), self._ptr(term), s_begin, s_end,
+                                         gamma, 0 if d_changed is None else d_changed.data_ptr(),
+                                         self._stream())
+
+    def expect_value_sweep(self, V, Vnew, policy, term, s_begin, s_end, gamma, d_delta, d_changed):
+        self.engine.expect_value_sweep(V.data_ptr(), Vnew.data_ptr(), policy.data_ptr(), self._ptr(term),
+                                       s_begin, s_end, gamma, 0 if d_delta is None else d_delta.data_ptr(),
+                                       0 if d_changed is None else d_changed.data_ptr(), self._stream())
+
     def close(self):
         # what the XCD-local kernel did, kept past the handle: evaluations run in it, how many of those were run again
         # in the placement-independent kernel, whole runs launched in it
@@ -278,6 +300,8 @@ class _CudaPolicyIterationBase(abc.ABC):
         self._transport_arg = transport
         self.stats = {"eval_sweeps": 0, "improve_sweeps": 0, "pi_iterations": 0,
                       "sweeps_per_iter": [], "eval_seconds": 0.0, "improve_seconds": 0.0}
+
+        self.disturbances = None          # set_disturbances: the set every sweep takes its expectation over
 
         self._precompute_grid_metadata()
         self._order = self._choose_memory_order()
@@ -695,6 +719,25 @@ class _CudaPolicyIterationBase(abc.ABC):
             comm.attach(self)
             logger.info(f"rank {self._rank}/{self._world}: states [{self._s_begin:,}, {self._s_end:,})")
 
+    # ── noise-aware solving ─────────────────────────────────────────────────────────
+    def set_disturbances(self, disturbances) -> None:
+        """Plan for noise: with a ``noise.Disturbances`` set installed, every sweep of ``run()``, ``policy_evaluation()``,
+        ``policy_improvement()`` and ``value_iteration()`` backs up the EXPECTATION over its K points,
+        ``Q(s, a) = sum_k p_k [r_k + gamma E[V](f(s, a (+) da_k) + dx_k)]`` (csrc/pi_expect_kernels.hip), instead of the one
+        deterministic successor — the policy that is optimal under the noise ``rollout(action_noise=..., state_noise=...)``
+        injects, for ``Disturbances.uniform`` of the same amplitudes.  ``None`` restores the deterministic sweeps.  The
+        one-launch shortcuts and the per-evaluation state list are not used while a set is installed.  Call it after
+        construction, before or between runs; ``stats["disturbances"]`` = K, ``save()`` archives the set.
+        ``rollout(controller="greedy")`` keeps its deterministic one-step lookahead.  Single rank only."""
+        if self._comm is not None:
+            raise NotImplementedError("set_disturbances: the expectation sweeps are not sharded; use a single-rank solver")
+        self._backend.set_disturbances(disturbances)
+        self.disturbances = disturbances
+        self.stats["disturbances"] = 0 if disturbances is None else int(disturbances.K)
+
+    def _expects(self) -> bool:
+        return getattr(self, "disturbances", None) is not None
+
     # ── policy iteration ────────────────────────────────────────────────────────────
     def _evaluation_sweeps(self, n: int, gamma: float) -> None:
         """n Jacobi sweeps under the current policy; afterwards ``d_value_function`` is the
@@ -702,9 +745,10 @@ class _CudaPolicyIterationBase(abc.ABC):
         if self._comm is not None:
             self._comm.evaluation_sweeps(self, n, gamma)
             return
-        self._backend.eval_sweeps(self.d_value_function, self.d_new_value_function, self.d_policy,
-                                  self._mask_arg(), self._s_begin, self._s_end, gamma, n,
-                                  self._d_delta)
+        sweeps = self._backend.expect_eval_sweeps if self._expects() else self._backend.eval_sweeps
+        sweeps(self.d_value_function, self.d_new_value_function, self.d_policy,
+               self._mask_arg(), self._s_begin, self._s_end, gamma, n,
+               self._d_delta)
         if n & 1:
             self.d_value_function, self.d_new_value_function = (
                 self.d_new_value_function, self.d_value_function)
@@ -715,8 +759,9 @@ class _CudaPolicyIterationBase(abc.ABC):
         if self._comm is not None:
             self._comm.improvement_sweep(self, gamma)
             return
-        self._backend.improve_sweep(self.d_value_function, self.d_policy, self._mask_arg(),
-                                    self._s_begin, self._s_end, gamma, self._d_changed)
+        sweep = self._backend.expect_improve_sweep if self._expects() else self._backend.improve_sweep
+        sweep(self.d_value_function, self.d_policy, self._mask_arg(),
+              self._s_begin, self._s_end, gamma, self._d_changed)
 
     def policy_evaluation(self) -> float:
         """Jacobi sweeps under the current policy until the residual, looked at on sweeps
@@ -725,7 +770,8 @@ class _CudaPolicyIterationBase(abc.ABC):
         gamma = float(np.float32(cfg.gamma))
         delta = float("inf")
         t0 = time.perf_counter()
-        if self._comm is None and getattr(self._backend, "resident", False) and cfg.max_eval_iter >= 1:
+        if (self._comm is None and not self._expects() and getattr(self._backend, "resident", False)
+                and cfg.max_eval_iter >= 1):
             delta = self._policy_evaluation_resident(gamma, t0)
             if delta is not None:
                 return delta
@@ -734,7 +780,7 @@ class _CudaPolicyIterationBase(abc.ABC):
         sweeps = 0
         # the policy is fixed for the whole loop: the library may drop the states whose successor is terminal
         # from the later sweeps (single rank, grids with a live-state list; same results)
-        bracket = self._comm is None and hasattr(self._backend, "eval_begin")
+        bracket = self._comm is None and not self._expects() and hasattr(self._backend, "eval_begin")
         if bracket:
             self._backend.eval_begin(self.d_policy, self._mask_arg())
         try:
@@ -824,7 +870,7 @@ class _CudaPolicyIterationBase(abc.ABC):
         cls = type(self)
         own = (cls.policy_evaluation is _CudaPolicyIterationBase.policy_evaluation
                and cls.policy_improvement is _CudaPolicyIterationBase.policy_improvement)
-        if (self._comm is not None or not own or not getattr(self._backend, "whole_run", False)
+        if (self._comm is not None or not own or self._expects() or not getattr(self._backend, "whole_run", False)
                 or cfg.max_eval_iter < 1 or cfg.max_pi_iter < 1):
             return False
         t0 = time.perf_counter()
@@ -866,11 +912,12 @@ class _CudaPolicyIterationBase(abc.ABC):
         limit = cfg.max_eval_iter if max_iter is None else int(max_iter)
         delta = float("inf")
         sweeps = 0
+        sweep = self._backend.expect_value_sweep if self._expects() else self._backend.value_sweep
         for i in range(limit):
             check = i % SYNC_INTERVAL == 0 or i == limit - 1
-            self._backend.value_sweep(self.d_value_function, self.d_new_value_function, self.d_policy,
-                                      self._mask_arg(), self._s_begin, self._s_end, gamma,
-                                      self._d_delta if check else None, None)
+            sweep(self.d_value_function, self.d_new_value_function, self.d_policy,
+                  self._mask_arg(), self._s_begin, self._s_end, gamma,
+                  self._d_delta if check else None, None)
             if self._comm is not None:
                 self._comm.exchange(self, self.d_new_value_function)
             self.d_value_function, self.d_new_value_function = (
@@ -1004,7 +1051,7 @@ class _CudaPolicyIterationBase(abc.ABC):
         terminated, trajectory).  Works on the host arrays, so after run() as well as on a load()ed instance.
         controller="greedy": act by the one-step lookahead on the VALUE function instead (csrc/pi_greedy_kernels.hip),
         with the config's gamma inside the lookahead — it needs no policy table, so it also works after
-        value_iteration().
+        value_iteration().  The lookahead is the DETERMINISTIC backup even on a solver trained with set_disturbances.
         epsilon, action_noise, state_noise, seed, first_episode: stochastic rollouts (csrc/pi_stochastic_kernels.hip;
         DevicePolicy.rollout documents them) — epsilon-random actions from this solver's action table, action noise and
         state noise from a stream that depends on (seed, first_episode + row, step) only.  controller="random" is the
@@ -1053,10 +1100,12 @@ class _CudaPolicyIterationBase(abc.ABC):
     def save(self, filepath) -> None:
         filepath = Path(filepath).with_suffix(".npz")
         filepath.parent.mkdir(parents=True, exist_ok=True)
+        # the set a noise-aware run planned for (set_disturbances): (K, D + 2) float32, columns da, dx.., p
+        extra = {"disturbances": self.disturbances.table()} if self._expects() else {}
         np.savez(filepath, value_function=self.value_function, policy=self.policy,
                  bounds_low=self.bounds_low, bounds_high=self.bounds_high,
                  grid_shape=self.grid_shape, strides=self.strides, corner_bits=self.corner_bits,
-                 action_space=self.action_space, states_space=self.states_space)
+                 action_space=self.action_space, states_space=self.states_space, **extra)
         logger.success(f"Policy saved to {filepath.resolve()}")
 
     @classmethod
@@ -1070,6 +1119,10 @@ class _CudaPolicyIterationBase(abc.ABC):
                     "strides", "corner_bits", "action_space"):
             setattr(inst, key, data[key])
         inst.states_space = data["states_space"]
+        inst.disturbances = None
+        if "disturbances" in data.files:
+            from .noise import Disturbances
+            inst.disturbances = Disturbances.from_table(data["disturbances"])
         inst.n_actions = len(inst.action_space)
         inst.n_states = len(inst.states_space)
         inst.config = CudaPIConfig()

@@ -216,6 +216,48 @@ int pi_value_sweep(pi_handle* h, const float* V, float* Vnew, int32_t* policy, c
                    void* stream);
 
 /*
+ * Noise-aware solving: the EXPECTED backup over a disturbance set (csrc/pi_expect_kernels.hip, csrc/pi_expect.cpp).  No
+ * reference counterpart: the reference backs up the one deterministic successor, Q(s, a) = r + gamma * E[V](f(s, a))
+ * (:212-283).  With a set installed the pi_expect_* sweeps compute
+ *     Q(s, a) = sum_k p_k * [ r_k + gamma * E[V](f(s, a (+) da_k) + dx_k) ]
+ * over K points, 1 <= K <= 64, each an action offset da_k, D state offsets dx_k[d] in the order of step_dynamics'
+ * arguments, and a weight p_k — the noise model of pi_infer_rollout_stochastic as a quadrature.  For a grid node s
+ * (coordinates from the bin tables, as the sweeps compute them) and an action value a, per point in ascending k:
+ *   1. a_k = a when da_k == 0.0f; otherwise a_k = fminf(fmaxf(a + da_k, a_min), a_max), a_min / a_max the extremes of the
+ *      handle's action table (the clamp of the stochastic rollouts);
+ *   2. (s', r_k, done_k) = step_dynamics(s, a_k), the exact instantiation with the functions of pi_math.h;
+ *   3. E_k = 0.0f when done_k.  Otherwise s'[d] = s'[d] + dx_k[d] for every d with dx_k[d] != 0 (one float32 add; the
+ *      disturbed successor is not wrapped, the interpolation clamps it) and E_k is the sweeps' interpolation at s';
+ *   4. q_k = r_k + gamma * E_k, a multiply then an add;
+ *   5. Q = p_0 * q_0 (a multiply), then Q = fmaf(p_k, q_k, Q) for k = 1 .. K - 1.
+ * With K = 1, da = dx = 0 and p = 1 this is the backup of pi_eval_sweep / pi_improve_sweep bit for bit, -0 and NaN
+ * included.  Points with equal da_k next to each other share one dynamics step (same function, same inputs, same bits).
+ *   pi_set_disturbances   HOST arrays: action_offsets (K floats) and state_offsets (K x D, row-major) may each be NULL =
+ *                       zeros; weights (K floats).  Every value finite, p_k >= 0, |sum p_k - 1| <= 1e-4 (summed in
+ *                       float64: the backup stays a gamma-contraction).  K = 0 drops the set.  Needs pi_compile; the first
+ *                       call after it builds the handle's expectation module — the same translation unit +
+ *                       csrc/pi_expect_kernels.hip, same flags and cache (a compile check on device = -1 handles) —,
+ *                       every call uploads the table (after a device synchronisation): K is run-time data, another set
+ *                       never builds anything.  A later pi_compile drops the module and the set.  Grids of 2^30 states or
+ *                       more are refused.  Every refusal is an error code and pi_last_error, never a launch.
+ *                       PI_INFO_DISTURBANCES = K in use.
+ *   pi_expect_eval_sweeps, pi_expect_improve_sweep, pi_expect_value_sweep
+ *                       pi_eval_sweeps, pi_improve_sweep and pi_value_sweep with Q as above: same arguments, same
+ *                       Va / Vb ping-pong, nullable d_delta / d_changed, term == NULL, terminal states, residual and
+ *                       changed count; strict > argmax from -1.0e30f over ascending action indices.  Asynchronous on
+ *                       `stream`.  Without a set they fail, naming pi_set_disturbances.  Every call launches the
+ *                       state-order kernels: they end a pi_eval_begin bracket and use neither the live-state list, graphs,
+ *                       the pair table nor the one-launch kernels.
+ */
+int pi_set_disturbances(pi_handle* h, int K, const float* action_offsets, const float* state_offsets, const float* weights);
+int pi_expect_eval_sweeps(pi_handle* h, float* Va, float* Vb, const int32_t* policy, const uint8_t* term, int64_t s_begin,
+                          int64_t s_end, float gamma, int n_sweeps, float* d_delta, void* stream);
+int pi_expect_improve_sweep(pi_handle* h, const float* V, int32_t* policy, const uint8_t* term, int64_t s_begin,
+                            int64_t s_end, float gamma, uint32_t* d_changed, void* stream);
+int pi_expect_value_sweep(pi_handle* h, const float* V, float* Vnew, int32_t* policy, const uint8_t* term, int64_t s_begin,
+                          int64_t s_end, float gamma, float* d_delta, uint32_t* d_changed, void* stream);
+
+/*
  * Which planes of V can the states of [s_begin, s_end) read, under ANY action?  Along dimension
  * `dim`: d_bitmap (device, ceil(grid_shape[dim] / 32) uint32 words, zeroed here) receives one bit
  * per index: that of every successor cell and the one above it.  No counterpart in the reference
@@ -659,8 +701,9 @@ enum pi_info_code {
     PI_INFO_WHOLE_RUNS = 33,                  /* whole runs launched (pi_policy_iteration) */
     PI_INFO_WHOLE_RUN_AVAILABLE = 34,         /* 1 if pi_policy_iteration serves this grid */
     PI_INFO_STRIP_STATES = 35,                /* states per period of the strip schedule in use (0: slab schedule) */
-    PI_INFO_PAIR_TABLE = 37                   /* 1 if the last pi_improve_sweep gathered from the pair table
+    PI_INFO_PAIR_TABLE = 37,                  /* 1 if the last pi_improve_sweep gathered from the pair table
                                                  (PI_OPTION_PAIR_TABLE); 36 stays unassigned */
+    PI_INFO_DISTURBANCES = 38                 /* points of the disturbance set in use (pi_set_disturbances; 0: none) */
 };
 int64_t pi_info(pi_handle* h, int what);
 

@@ -39,6 +39,13 @@ A third extension flag, --coarse-bins N [N ...] (off by default), trains by grid
 each N in turn — each level started from the previous level's solution interpolated onto its grid
 (solver.continue_from) — and then at --bins; sweeps and seconds are printed per level.  Only the --bins solution is saved.
 
+--train-action-noise A, --train-state-noise X [X ...] and --train-noise-points P (extensions, default 0 / none / 3) make
+TRAINING noise-aware: the solver plans for the noise model of --action-noise / --state-noise instead of the one
+deterministic successor — every sweep backs up the expectation over the tensor Gauss-Legendre rule with P nodes per noisy
+quantity (dynamicprogramming_amd.noise.Disturbances.uniform, solver.set_disturbances; csrc/pi_expect_kernels.hip), on
+every continuation level.  The set is saved with the policy.  They act on training only: when a saved policy is loaded
+instead, a note says that they had no effect.
+
 The ignored group drives the reference's gymnasium / pygame / matplotlib evaluation harness, which is
 outside the scope of this package: training, saving and loading behave as in
 the reference (train when the archive is missing or --retrain is given, otherwise load it), the
@@ -65,18 +72,36 @@ def bins_space_for(env_name: str, bins: int) -> dict:
     return envs.ENVS[env_name].bins_space(bins)
 
 
+def training_disturbances(env_name: str, action_noise: float = 0.0, state_noise=None, points: int = 3):
+    """The disturbance set --train-action-noise / --train-state-noise / --train-noise-points name for this env, or None
+    when both amplitudes are zero (deterministic training)."""
+    import numpy as np
+    from dynamicprogramming_amd import envs
+    from dynamicprogramming_amd.noise import Disturbances
+    if float(action_noise) == 0.0 and (state_noise is None or not np.any(np.asarray(state_noise, dtype=np.float64) != 0)):
+        return None
+    return Disturbances.uniform(envs.ENVS[env_name]._D, state_noise=state_noise, action_noise=action_noise, points=points)
+
+
 def train(env_name: str, bins: int | None = None, save_path: Path | str | None = None,
-          value_iteration: bool = False, coarse_bins=(), **kw):
+          value_iteration: bool = False, coarse_bins=(), train_action_noise: float = 0.0, train_state_noise=None,
+          train_noise_points: int = 3, **kw):
     """Build the env on its reference grid, run policy iteration on the GPU, save the .npz
     (reference: each runner's train(), e.g. pendulum_cuda.py:116-130).  value_iteration=True (extension):
     fused value-iteration sweeps to the same theta instead, at most max_pi_iter slices of max_eval_iter.
     coarse_bins (extension): grid continuation — solve at each of these bins per dimension first, every level
-    (the last one at `bins`) continued from the one before it."""
+    (the last one at `bins`) continued from the one before it.  train_action_noise / train_state_noise /
+    train_noise_points (extension): noise-aware training — every level plans for that noise (training_disturbances)."""
     from dynamicprogramming_amd import envs
+    noise = training_disturbances(env_name, train_action_noise, train_state_noise, train_noise_points)
+    if noise is not None:
+        print(f"[{env_name}] noise-aware training: expected backup over {noise.K} disturbance points")
     previous = None
     for level in coarse_bins:
         t0 = time.perf_counter()
         coarse = envs.make(env_name, int(level), **kw)
+        if noise is not None:
+            coarse.set_disturbances(noise)
         if previous is not None:
             coarse.continue_from(previous)
         coarse.run()
@@ -85,6 +110,8 @@ def train(env_name: str, bins: int | None = None, save_path: Path | str | None =
               f"{st['eval_sweeps']} eval sweeps in {time.perf_counter() - t0:.2f} s")
         previous = coarse
     solver = envs.make(env_name, bins, **kw)
+    if noise is not None:
+        solver.set_disturbances(noise)
     t0 = time.perf_counter()
     if previous is not None:
         solver.continue_from(previous)
@@ -153,7 +180,18 @@ def build_parser(env_name: str, default_save: str) -> argparse.ArgumentParser:
     p.add_argument("--state-noise", type=float, nargs="+", default=None, metavar="X",
                    help="(extension, with --rollout) state disturbance after every step: X * u per dimension (one value "
                         "for every dimension, or one per dimension)")
+    p.add_argument("--train-action-noise", type=float, default=0.0, metavar="A",
+                   help="(extension) noise-aware training: plan for actuator noise A * u, u uniform in [-1, 1)")
+    p.add_argument("--train-state-noise", type=float, nargs="+", default=None, metavar="X",
+                   help="(extension) noise-aware training: plan for a state disturbance X * u per dimension after every "
+                        "step (one value for every dimension, or one per dimension)")
+    p.add_argument("--train-noise-points", type=int, default=3, metavar="P",
+                   help="(extension) Gauss-Legendre nodes per noisy quantity of the training noise (default: 3)")
     return p
+
+
+def training_noise_requested(args) -> bool:
+    return args.train_action_noise != 0.0 or args.train_state_noise is not None or args.train_noise_points != 3
 
 
 STEADY_WINDOW = 100     # states per episode in results/last_trajectory.npz (the reference's STATS_WINDOW)
@@ -247,9 +285,14 @@ def main(env_name: str, default_save: str, argv=None):
         print(f"[+] Loading existing policy from {path}")
         pi = cls.load(path)
         print(f"[{env_name}] {pi.n_states:,} states, {pi.n_actions} actions; use --retrain to recompute")
+        if training_noise_requested(args):
+            print(f"[{env_name}] note: --train-action-noise, --train-state-noise and --train-noise-points act on training "
+                  "only; a saved policy was loaded, so they had no effect")
     else:
         print("[*] Training new policy...")
-        pi = train(env_name, args.bins, path, value_iteration=args.value_iteration, coarse_bins=args.coarse_bins, **kw)
+        pi = train(env_name, args.bins, path, value_iteration=args.value_iteration, coarse_bins=args.coarse_bins,
+                   train_action_noise=args.train_action_noise, train_state_noise=args.train_state_noise,
+                   train_noise_points=args.train_noise_points, **kw)
     if args.rollout:
         evaluate(env_name, pi, args.episodes, args.steps, args.seed, start_x=getattr(args, "start_x", None),
                  traj_path=Path("results") / "last_trajectory.npz" if env_name == "double_cartpole_swingup" else None,
