@@ -104,6 +104,12 @@ SIGNATURES = {
                                                    _vp, _vp, ctypes.c_int, _vp]),
     "pi_infer_random_words": (ctypes.c_int, [_vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64, ctypes.c_uint32,
                                              ctypes.c_uint32, _vp, _vp]),
+    "pi_infer_set_expect_greedy": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
+    "pi_infer_set_disturbances": (ctypes.c_int, [_vp, ctypes.c_int, _f32p, _f32p, _f32p]),
+    "pi_infer_expect_greedy": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "pi_infer_rollout_expect_greedy": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                                      ctypes.c_float, ctypes.c_float, _f32p, ctypes.c_uint64, ctypes.c_uint64,
+                                                      _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "pi_plan_schedule": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_uint64)]),
     "pi_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64]),
@@ -789,6 +795,64 @@ class InferenceEngine:
         buffer at `d_words` (pi_infer_random_words; asynchronous)."""
         _check(lib().pi_infer_random_words(self._h, int(seed), int(first_episode), int(m), int(step), int(block),
                                            d_words or None, stream or None), "pi_infer_random_words")
+
+    def set_expect_greedy(self, action_space) -> str:
+        """Upload the action table of the expected-value greedy controller and build its kernels behind the plugin of the
+        last set_dynamics (a compile check on a host-only handle); needs set_values and set_dynamics; returns the
+        compiler's log.  A later set_dynamics drops the module again."""
+        act = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        log = ctypes.create_string_buffer(1 << 16)
+        rc = lib().pi_infer_set_expect_greedy(self._h, None if act is None else act.ctypes.data_as(_f32p),
+                                              0 if act is None else len(act), log, len(log))
+        text = log.value.decode(errors="replace")
+        if rc != 0:
+            raise NativeError(f"pi_infer_set_expect_greedy failed:\n{last_error()}")
+        return text
+
+    def set_disturbances(self, action_offsets, state_offsets, weights) -> int:
+        """The disturbance set the expected-value greedy controller takes its expectation over
+        (pi_infer_set_disturbances; host arrays, the rules of Engine.set_disturbances): K weights, K action offsets or
+        None (zeros), (K, D) state offsets or None (zeros).  `weights=None` drops the set.  An upload, never a build.
+        Returns K."""
+        if weights is None:
+            _check(lib().pi_infer_set_disturbances(self._h, 0, None, None, None), "pi_infer_set_disturbances")
+            return 0
+        w = np.ascontiguousarray(weights, dtype=np.float32).ravel()
+        K = len(w)
+        da = None if action_offsets is None else np.ascontiguousarray(action_offsets, dtype=np.float32).ravel()
+        dx = None if state_offsets is None else np.ascontiguousarray(state_offsets, dtype=np.float32).reshape(-1)
+        if K == 0 or (da is not None and len(da) != K) or (dx is not None and len(dx) != K * self.D):
+            raise ValueError(f"a disturbance set needs K >= 1 weights, K action offsets and (K, {self.D}) state offsets")
+        _check(lib().pi_infer_set_disturbances(self._h, K, None if da is None else da.ctypes.data_as(_f32p),
+                                               None if dx is None else dx.ctypes.data_as(_f32p), w.ctypes.data_as(_f32p)),
+               "pi_infer_set_disturbances")
+        return K
+
+    def expect_greedy(self, d_points, m, gamma, d_best=0, d_action=0, d_q_best=0, d_q_all=0, stream=0) -> None:
+        """The one-step lookahead with the expectation over the disturbance set at m query points in one launch
+        (pi_infer_expect_greedy; raw device pointers, asynchronous): the outputs of `greedy`."""
+        _check(lib().pi_infer_expect_greedy(self._h, d_points or None, int(m), float(gamma), d_best or None,
+                                            d_action or None, d_q_best or None, d_q_all or None, stream or None),
+               "pi_infer_expect_greedy")
+
+    def rollout_expect_greedy(self, d_start, m, n_steps, lookahead_gamma, gamma=1.0, epsilon=0.0, action_noise=0.0,
+                              state_noise=None, seed=0, first_episode=0, d_final=0, d_return=0, d_length=0, d_terminated=0,
+                              d_traj=0, traj_every=0, stream=0) -> None:
+        """m episodes of n_steps closed-loop steps under the expected-value greedy controller, with the epsilon-random
+        actions, action noise and state noise of `rollout_stochastic` from the same stream, in one launch
+        (pi_infer_rollout_expect_greedy; raw device pointers, `state_noise` a host array of D floats or None;
+        asynchronous)."""
+        noise = None
+        if state_noise is not None:
+            noise = np.ascontiguousarray(state_noise, dtype=np.float32)
+            if noise.shape != (self.D,):
+                raise ValueError(f"state_noise must hold {self.D} values")
+        _check(lib().pi_infer_rollout_expect_greedy(self._h, d_start or None, int(m), int(n_steps), float(gamma),
+                                                    float(lookahead_gamma), float(epsilon), float(action_noise),
+                                                    None if noise is None else noise.ctypes.data_as(_f32p), int(seed),
+                                                    int(first_episode), d_final or None, d_return or None, d_length or None,
+                                                    d_terminated or None, d_traj or None, int(traj_every), stream or None),
+               "pi_infer_rollout_expect_greedy")
 
     def close(self) -> None:
         if getattr(self, "_h", None):

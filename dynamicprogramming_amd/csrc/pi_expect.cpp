@@ -10,7 +10,7 @@ using namespace pi;
 
 namespace {
 
-constexpr int kMaxPoints = 64;      // PI_NOISE_MAX
+constexpr int kMaxPoints = pi::kMaxDisturbances;
 constexpr int kBlock = 256;         // PI_BLOCK_EXPECT: one chunk per workgroup
 
 // What every expectation sweep checks before it looks at its own arguments.  The set comes first, so that a caller who
@@ -27,6 +27,31 @@ Grid2 blocks_for(int64_t count) { return {launch_blocks(kBlock, count, 1), 1u}; 
 
 }  // namespace
 
+int pi::build_disturbance_table(const char* who_c, int D, int K, const float* action_offsets, const float* state_offsets,
+                                const float* weights, std::vector<float>& table) {
+    const std::string who(who_c);
+    table.clear();
+    if (K < 0 || K > kMaxPoints) return fail(who + ": K must be in [0, " + std::to_string(kMaxPoints) + "]");
+    if (K == 0) return 0;
+    if (!weights) return fail(who + ": null weights");
+    const int row = D + 2;
+    table.assign((size_t)K * row, 0.0f);
+    double sum = 0.0;
+    for (int k = 0; k < K; ++k) {
+        float* r = &table[(size_t)k * row];
+        if (action_offsets) r[0] = action_offsets[k];
+        for (int d = 0; d < D && state_offsets; ++d) r[1 + d] = state_offsets[(size_t)k * D + d];
+        r[row - 1] = weights[k];
+        for (int j = 0; j < row; ++j)
+            if (!std::isfinite(r[j])) return fail(who + ": point " + std::to_string(k) + " holds a value that is not finite");
+        if (r[row - 1] < 0.0f) return fail(who + ": weight " + std::to_string(k) + " is negative");
+        sum += (double)r[row - 1];
+    }
+    if (!(std::fabs(sum - 1.0) <= 1e-4))
+        return fail(who + ": the weights sum to " + std::to_string(sum) + ", not to 1 within 1e-4");
+    return 0;
+}
+
 extern "C" {
 
 int pi_set_disturbances(pi_handle* h, int K, const float* action_offsets, const float* state_offsets, const float* weights) {
@@ -36,27 +61,13 @@ int pi_set_disturbances(pi_handle* h, int K, const float* action_offsets, const 
         return fail("pi_set_disturbances: grids of 2^30 states or more are not served (the expectation sweeps have no 64-bit "
                     "addressing path)");
     if (!h->compiled) return fail("pi_set_disturbances: pi_compile has not been called on this handle");
-    if (K < 0 || K > kMaxPoints) return fail("pi_set_disturbances: K must be in [0, " + std::to_string(kMaxPoints) + "]");
+    const int row = h->D + 2;
+    std::vector<float> table;
+    if (build_disturbance_table("pi_set_disturbances", h->D, K, action_offsets, state_offsets, weights, table)) return 1;
     if (K == 0) {
         h->dist_k = 0;
         return 0;
     }
-    if (!weights) return fail("pi_set_disturbances: null weights");
-    const int D = h->D, row = D + 2;
-    std::vector<float> table((size_t)K * row, 0.0f);
-    double sum = 0.0;
-    for (int k = 0; k < K; ++k) {
-        float* r = &table[(size_t)k * row];
-        if (action_offsets) r[0] = action_offsets[k];
-        for (int d = 0; d < D && state_offsets; ++d) r[1 + d] = state_offsets[(size_t)k * D + d];
-        r[row - 1] = weights[k];
-        for (int j = 0; j < row; ++j)
-            if (!std::isfinite(r[j])) return fail("pi_set_disturbances: point " + std::to_string(k) + " holds a value that is not finite");
-        if (r[row - 1] < 0.0f) return fail("pi_set_disturbances: weight " + std::to_string(k) + " is negative");
-        sum += (double)r[row - 1];
-    }
-    if (!(std::fabs(sum - 1.0) <= 1e-4))
-        return fail("pi_set_disturbances: the weights sum to " + std::to_string(sum) + ", not to 1 within 1e-4");
     if (ensure_expect_module(h)) return 1;
     const auto ends = std::minmax_element(h->tab.begin(), h->tab.begin() + h->n_actions);
     if (h->device >= 0) {

@@ -89,6 +89,8 @@ __device__ __forceinline__ float pi_greedy_q(const float (&s)[PI_D], float a, co
     return *reward + future;
 }
 
+// The expected-greedy module (pi_expect_greedy_kernels.hip) takes the functions above and leaves the two kernels out.
+#ifndef PI_EXPECT_GREEDY
 // Batched query.  Every output may be null: out_best (m) int32, out_action (m) = actions[best], out_qbest (m),
 // out_qall (m, n_actions) row-major.
 extern "C" __global__ void __launch_bounds__(PI_GR_BLOCK)
@@ -193,3 +195,4 @@ pi_greedy_rollout_kernel(const float* __restrict__ start, long long m, int n_ste
     if (out_length != nullptr) out_length[k] = length;
     if (out_terminated != nullptr) out_terminated[k] = terminated ? 1 : 0;
 }
+#endif  // PI_EXPECT_GREEDY

@@ -12,6 +12,7 @@
 //   pi_greedy.cpp     value-greedy control on the inference handle: one-step lookahead on V, queries and rollouts
 //   pi_stochastic.cpp stochastic rollouts on the inference handle: random baseline, epsilon-random actions, noise (Philox)
 //   pi_expect.cpp     the expected backup over a disturbance set: pi_set_disturbances and the pi_expect_* sweeps
+//   pi_expect_greedy.cpp  expected-value greedy control on the inference handle: the lookahead over a disturbance set
 #pragma once
 
 #include "pi_knobs.h"
@@ -147,6 +148,8 @@ extern "C" const char pi_embedded_math[];
 extern "C" const char pi_embedded_push[];
 extern "C" const char pi_embedded_expect[];
 extern "C" const char pi_embedded_rollout[];      // pi_rollout.cpp
+extern "C" const char pi_embedded_greedy[];       // pi_greedy.cpp
+extern "C" const char pi_embedded_stochastic[];   // pi_stochastic.cpp
 
 struct pi_handle {
     int device = -1;
@@ -305,6 +308,20 @@ struct pi_infer {
     float* d_stochastic_actions = nullptr;
     int n_stochastic_actions = 0;
     float stochastic_a_min = 0.0f, stochastic_a_max = 0.0f;
+    // seventh module (pi_infer_set_expect_greedy, pi_expect_greedy.cpp): this grid + pi_math.h + the env plugin + the
+    // helpers of csrc/pi_rollout_kernels.hip + the functions of csrc/pi_greedy_kernels.hip and
+    // csrc/pi_stochastic_kernels.hip + csrc/pi_expect_greedy_kernels.hip.  d_expect_greedy_actions: the action table of
+    // that call (owned), expect_greedy_a_min / _a_max its extremes: the clamp of a + da_k and of a noisy action
+    hipModule_t module_expect_greedy = nullptr;
+    hipFunction_t f_expect_greedy = nullptr, f_expect_greedy_rollout = nullptr;
+    bool has_expect_greedy = false;      // pi_infer_set_expect_greedy went through (host-only handles: it compiled)
+    float* d_expect_greedy_actions = nullptr;
+    int n_expect_greedy_actions = 0;
+    float expect_greedy_a_min = 0.0f, expect_greedy_a_max = 0.0f;
+    // the disturbance set of that controller (pi_infer_set_disturbances): K rows of {da, dx_0 .. dx_{D-1}, p} at d_dist,
+    // a buffer of 64 rows allocated by the first call; dist_k == 0: no set.  Independent of the module
+    float* d_dist = nullptr;
+    int dist_k = 0;
 };
 
 namespace pi {
@@ -367,5 +384,11 @@ int check_rollout_args(int D, const float* d_start, int64_t m, int n_steps, cons
 int drop_hybrid(pi_infer* h);           // pi_hybrid.cpp: unloads the third module (after a device synchronisation)
 int drop_greedy(pi_infer* h);           // pi_greedy.cpp: unloads the fifth module (after a device synchronisation)
 int drop_stochastic(pi_infer* h);       // pi_stochastic.cpp: unloads the sixth module (after a device synchronisation)
+int drop_expect_greedy(pi_infer* h);    // pi_expect_greedy.cpp: unloads the seventh module (after a device synchronisation)
+// pi_expect.cpp: the rules of a disturbance set, shared by pi_set_disturbances and pi_infer_set_disturbances (`who`).
+// 0: `table` holds K rows of {da, dx_0 .. dx_{D-1}, p}, null offsets as zeros (K == 0: empty); 1: refused (pi::fail was called)
+constexpr int kMaxDisturbances = 64;    // PI_NOISE_MAX
+int build_disturbance_table(const char* who, int D, int K, const float* action_offsets, const float* state_offsets,
+                            const float* weights, std::vector<float>& table);
 
 }  // namespace pi

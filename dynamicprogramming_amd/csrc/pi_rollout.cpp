@@ -63,6 +63,7 @@ int pi_infer_set_dynamics(pi_infer* h, const char* dynamics_src, char* log, size
     if (pi::drop_hybrid(h)) return 1;               // the hybrid module holds the previous plugin
     if (pi::drop_greedy(h)) return 1;               // ... and so does the greedy one
     if (pi::drop_stochastic(h)) return 1;           // ... and the stochastic one
+    if (pi::drop_expect_greedy(h)) return 1;        // ... and the expected-greedy one
     h->dynamics_src = dynamics_src;
     if (h->device < 0) {                            // host-only handle: compile check
         h->has_dynamics = true;

@@ -88,6 +88,8 @@ __device__ __forceinline__ float pi_stochastic_sym(unsigned int x) {
     return (float)((int)(x >> 8) - 8388608) * 0x1p-23f;
 }
 
+// The expected-greedy module (pi_expect_greedy_kernels.hip) takes the functions above and leaves the two kernels out.
+#ifndef PI_EXPECT_GREEDY
 // Probe: the four words of (seed, first_episode + row, step, block) for rows 0 .. m, out (m, 4) uint32.
 extern "C" __global__ void __launch_bounds__(PI_ST_BLOCK)
 pi_random_words_kernel(unsigned long long seed, unsigned long long first_episode, long long m, unsigned int step,
@@ -195,3 +197,4 @@ pi_stochastic_rollout_kernel(const float* __restrict__ start, long long m, int n
     if (out_length != nullptr) out_length[k] = length;
     if (out_terminated != nullptr) out_terminated[k] = terminated ? 1 : 0;
 }
+#endif  // PI_EXPECT_GREEDY

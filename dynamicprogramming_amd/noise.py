@@ -9,12 +9,17 @@ The solvers back up the single deterministic successor, ``Q(s, a) = r + gamma * 
 on the device (csrc/pi_expect_kernels.hip; include/pi_mi355.h at ``pi_set_disturbances`` is the definition).  The
 functions below restate that definition in numpy, bit for bit, on any batched ``step`` callable — the one
 ``utils.barycentric.rollout`` takes: ``step(states (m, D), actions (m,)) -> (next (m, D), reward (m,), done (m,))``.
+
+Expected-value greedy control closes the loop: ``expected_greedy_action`` is the one-step lookahead ``argmax_a Q(s, a)``
+with that expectation inside it at arbitrary continuous states, ``expected_greedy_rollout`` the closed loop under it with
+the noise of the stochastic rollouts — the twins of ``DevicePolicy.expected_greedy`` and
+``DevicePolicy.rollout(controller="expected")`` (csrc/pi_expect_greedy_kernels.hip), same bits.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from utils.barycentric import _expected_value, _fmaf
+from utils.barycentric import _expected_value, _fmaf, _noisy_closed_loop
 
 MAX_POINTS = 64
 
@@ -110,7 +115,8 @@ def expected_q(step, states, actions, disturbances, value_function, action_space
                strides, gamma):
     """``Q(s, a)`` of the module docstring for ``states`` (m, D) and action VALUES ``actions`` (m,) or a scalar; float32
     (m,).  Per point in ascending k: ``a_k = a`` when ``da_k == 0``, else ``fmin(fmax(a + da_k, a_min), a_max)`` with
-    the extremes of ``action_space``; ``(s', r, done) = step(s, a_k)``; ``E = 0`` where done, elsewhere ``dx_k`` is added
+    the extremes of ``action_space``; ``(s', r, done) = step(s, a_k)`` (a point with the ``da`` of the one before it keeps
+    that point's step, as on the device); ``E = 0`` where done, elsewhere ``dx_k`` is added
     to ``s'`` in every dimension where it is not zero and ``E`` is ``utils.barycentric._expected_value`` there;
     ``q = r + gamma * E``; ``Q = p_0 * q_0``, then ``Q = fmaf(p_k, q_k, Q)``."""
     pts = np.ascontiguousarray(np.atleast_2d(states), dtype=np.float32)
@@ -122,9 +128,10 @@ def expected_q(step, states, actions, disturbances, value_function, action_space
     Q = np.zeros(m, np.float32)
     for k in range(disturbances.K):
         da = disturbances.action_offsets[k]
-        ak = a if da == 0 else np.fmin(np.fmax(a + da, a_min), a_max)
-        nxt, rew, done = step(pts, ak)
-        nxt, done = np.asarray(nxt, np.float32), np.asarray(done, bool)
+        if k == 0 or da != disturbances.action_offsets[k - 1]:       # equal consecutive offsets share the step, as on the device
+            ak = a if da == 0 else np.fmin(np.fmax(a + da, a_min), a_max)
+            nxt, rew, done = step(pts, ak)
+            nxt, done = np.asarray(nxt, np.float32), np.asarray(done, bool)
         e = np.zeros(m, np.float32)
         if not done.all():
             p = nxt[~done].copy()
@@ -206,3 +213,53 @@ def expected_value_sweep(step, states, policy, value_function, term, disturbance
     if len(live):
         new_p[live], new_v[live] = _argmax(step, states, live, disturbances, V, acts, grid, gamma)
     return new_v, new_p, _residual(new_v[s_begin:s_end], V[s_begin:s_end]), int((new_p != np.asarray(policy)).sum())
+
+
+def expected_greedy_action(step, points, disturbances, value_function, action_space, bounds_low, bounds_high, grid_shape,
+                           strides, gamma, q_values=False):
+    """The greedy one-step lookahead with the expectation over ``disturbances`` inside it, at ``points`` (m, D) (numpy):
+    the twin of ``DevicePolicy.expected_greedy``, same bits.  For every action of ``action_space`` in ascending order
+    ``Q = expected_q(points, action)``; the argmax is ``utils.barycentric.greedy_action``'s — strict ``>`` from -1e30, the
+    lowest index wins ties, NaN never wins, index 0 with Q = -1e30 when nothing wins.  With ``Disturbances.none(D)`` it is
+    ``greedy_action``, bit for bit.  Returns ``(best_index int32, action float32, q_best float32)`` and, with
+    ``q_values=True``, ``Q (m, n_actions)`` float32."""
+    pts = np.ascontiguousarray(np.atleast_2d(points), dtype=np.float32)
+    acts, grid = _tables(action_space, bounds_low, bounds_high, grid_shape, strides)
+    m = len(pts)
+    best = np.zeros(m, np.int32)
+    best_q = np.full(m, np.float32(-1.0e30), np.float32)
+    Q = np.empty((m, len(acts)), np.float32)
+    for a, u in enumerate(acts):
+        q = expected_q(step, pts, u, disturbances, value_function, acts, *grid, gamma) if m else np.zeros(0, np.float32)
+        with np.errstate(invalid="ignore"):
+            wins = q > best_q
+        Q[:, a] = q
+        best_q = np.where(wins, q, best_q)
+        best = np.where(wins, np.int32(a), best)
+    out = (best, acts[best], best_q)
+    return out + (Q,) if q_values else out
+
+
+def expected_greedy_rollout(step, states, steps, disturbances, value_function, action_space, bounds_low, bounds_high,
+                            grid_shape, strides, lookahead_gamma, gamma=1.0, record_every=0, epsilon=0.0, action_noise=0.0,
+                            state_noise=None, seed=0, first_episode=0):
+    """Closed-loop episodes under the expected-value greedy controller on the CPU (numpy): the twin of
+    ``DevicePolicy.rollout(controller="expected")``, same bits.  It is ``utils.barycentric.stochastic_rollout`` with the
+    action value ``expected_greedy_action`` returns for the state (discount ``lookahead_gamma``) in place of the
+    interpolated one.  Per step of a running episode, in this order: the lookahead; an exploring step (block 0 of the
+    episode's stream: ``(x0 >> 8) < explore_threshold(epsilon)``) takes ``action_space[random_action_index(x1)]``
+    instead; ``action_noise != 0`` adds ``action_noise * sym(x2)`` and clamps to the extremes of ``action_space``;
+    ``step`` with the action finally taken; then, unless the step was `done`, every dimension with ``state_noise[d] !=
+    0`` of the successor gains ``state_noise[d] * sym(word d)`` (block 1 for d < 4, block 2 for d = 4, 5).  The draws are
+    ``stochastic_rollout``'s — the same counters — so both controllers can be run under common random numbers.  The
+    bookkeeping, ``gamma`` and ``record_every`` are ``rollout``'s.  Returns a ``RolloutResult`` of numpy arrays."""
+    acts = np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+    tables = (disturbances, value_function, acts, bounds_low, bounds_high, grid_shape, strides, lookahead_gamma)
+
+    def controller(pts, wanted):                      # an exploring episode is not looked ahead for
+        a = np.zeros(len(pts), np.float32)
+        if wanted.any():
+            a[wanted] = expected_greedy_action(step, pts[wanted], *tables)[1]
+        return a
+    return _noisy_closed_loop(step, states, steps, controller, acts, epsilon, action_noise, state_noise, seed,
+                              first_episode, gamma, record_every)

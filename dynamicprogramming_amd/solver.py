@@ -728,7 +728,8 @@ class _CudaPolicyIterationBase(abc.ABC):
         injects, for ``Disturbances.uniform`` of the same amplitudes.  ``None`` restores the deterministic sweeps.  The
         one-launch shortcuts and the per-evaluation state list are not used while a set is installed.  Call it after
         construction, before or between runs; ``stats["disturbances"]`` = K, ``save()`` archives the set.
-        ``rollout(controller="greedy")`` keeps its deterministic one-step lookahead.  Single rank only."""
+        ``rollout(controller="greedy")`` keeps its deterministic one-step lookahead; ``rollout(controller="expected")`` is
+        the lookahead that takes this expectation.  Single rank only."""
         if self._comm is not None:
             raise NotImplementedError("set_disturbances: the expectation sweeps are not sharded; use a single-rank solver")
         self._backend.set_disturbances(disturbances)
@@ -1044,7 +1045,7 @@ class _CudaPolicyIterationBase(abc.ABC):
 
     # ── closed-loop evaluation (the reference's per-runner evaluate(), e.g. pendulum_cuda.py:135-189) ─────────
     def rollout(self, start_states, steps, gamma=1.0, record_every=0, device=None, controller="policy", *,
-                epsilon=0.0, action_noise=0.0, state_noise=None, seed=0, first_episode=0):
+                epsilon=0.0, action_noise=0.0, state_noise=None, seed=0, first_episode=0, disturbances=None):
         """Roll the trained policy out on the env's own dynamics, every episode of the batch in ONE kernel launch
         (utils.barycentric.DevicePolicy.rollout; csrc/pi_rollout_kernels.hip): `start_states` (m, D) — numpy, or a
         float32 tensor on the device — for `steps` steps each.  Returns a RolloutResult (states, returns, lengths,
@@ -1052,26 +1053,39 @@ class _CudaPolicyIterationBase(abc.ABC):
         controller="greedy": act by the one-step lookahead on the VALUE function instead (csrc/pi_greedy_kernels.hip),
         with the config's gamma inside the lookahead — it needs no policy table, so it also works after
         value_iteration().  The lookahead is the DETERMINISTIC backup even on a solver trained with set_disturbances.
+        controller="expected": the lookahead with the EXPECTATION over a disturbance set inside it
+        (csrc/pi_expect_greedy_kernels.hip) — `disturbances` if given, else the solver's own set (set_disturbances, or the
+        one a load()ed archive carries); on a noise-aware solution it returns the solved policy at the grid nodes.  It
+        takes values the way "greedy" does and, unlike it, accepts the stochastic keywords below: with
+        ``Disturbances.none(D)`` it is the greedy lookahead in a noisy world.
         epsilon, action_noise, state_noise, seed, first_episode: stochastic rollouts (csrc/pi_stochastic_kernels.hip;
         DevicePolicy.rollout documents them) — epsilon-random actions from this solver's action table, action noise and
         state noise from a stream that depends on (seed, first_episode + row, step) only.  controller="random" is the
         random-policy baseline (epsilon = 1): it reads no table, so it also works on an instance that has never run."""
         from utils.barycentric import DevicePolicy
-        if controller not in ("policy", "greedy", "random"):
-            raise ValueError(f"controller must be 'policy', 'greedy' or 'random', not {controller!r}")
+        if controller not in ("policy", "greedy", "random", "expected"):
+            raise ValueError(f"controller must be 'policy', 'greedy', 'random' or 'expected', not {controller!r}")
         greedy = controller == "greedy"
+        expected = controller == "expected"
+        if disturbances is not None and not expected:
+            raise ValueError("disturbances= belongs to controller='expected'")
+        if expected and disturbances is None:
+            disturbances = getattr(self, "disturbances", None)
+            if disturbances is None:
+                raise RuntimeError("controller='expected' needs a disturbance set: pass disturbances=, or install one with "
+                                   "set_disturbances (a load()ed archive carries the set it was solved with)")
         noisy = dict(epsilon=epsilon, action_noise=action_noise, state_noise=state_noise, seed=seed, first_episode=first_episode)
         stochastic = controller == "random" or float(epsilon) != 0.0 or float(action_noise) != 0.0 or \
             (state_noise is not None and bool(np.any(np.asarray(state_noise, dtype=np.float32) != 0)))
         if greedy and stochastic:
             raise ValueError("controller='greedy' takes no epsilon, action_noise or state_noise: a stochastic greedy "
                              "controller does not exist")
-        no_policy = greedy or controller == "random" or float(epsilon) == 1.0
+        no_policy = greedy or expected or controller == "random" or float(epsilon) == 1.0
         values = getattr(self, "value_function", None)
-        if greedy and values is None and hasattr(self, "d_value_function") and self._comm is None:
+        if (greedy or expected) and values is None and hasattr(self, "d_value_function") and self._comm is None:
             # mid-run (value_iteration(), policy_evaluation()): the current iterate, in the user's order
             values = np.ascontiguousarray(self._to_user(self.d_value_function[:self.n_states].cpu().numpy()))
-        if greedy and values is None:
+        if (greedy or expected) and values is None:
             raise RuntimeError("a greedy rollout needs a value function: call run(), value_iteration() or load() first")
         if not no_policy and getattr(self, "policy", None) is None:
             raise RuntimeError("rollout needs a trained policy in host memory: call run() or load() first")
@@ -1086,6 +1100,12 @@ class _CudaPolicyIterationBase(abc.ABC):
                 dp.set_greedy()
                 out = dp.rollout(start_states, steps, gamma=gamma, record_every=record_every, controller="greedy",
                                  lookahead_gamma=self.config.gamma)
+            elif expected:
+                dp.set_values(values)
+                dp.set_expected_greedy()
+                dp.set_disturbances(disturbances)
+                out = dp.rollout(start_states, steps, gamma=gamma, record_every=record_every, controller="expected",
+                                 lookahead_gamma=self.config.gamma, **noisy)
             elif stochastic:
                 dp.set_stochastic()
                 out = dp.rollout(start_states, steps, gamma=gamma, record_every=record_every, controller=controller, **noisy)

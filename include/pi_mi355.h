@@ -591,6 +591,39 @@ int pi_plan_schedule(pi_handle* h, int block, int64_t first, int64_t count, int6
  *                       a launch.  Asynchronous.
  *   pi_infer_random_words  probe of the stream: for rows 0 .. m the four words of (seed, first_episode + row, step, block)
  *                       into d_words, (m, 4) uint32 on the device.  m == 0 is a no-op.  Asynchronous.
+ * Expected-value greedy control on the same handle (no reference counterpart): the greedy lookahead with the expectation
+ * of noise-aware solving inside it, a*(s) = argmax_a Q_K(s, a), and closed-loop rollouts under it that draw the
+ * stochastic rollouts' noise.  Q_K(s, a) is the definition at pi_set_disturbances, steps 1-5, evaluated at the point s
+ * instead of a grid node, with the interpolation of pi_infer_greedy: per point of the set in ascending k, a_k = a when
+ * da_k == 0, else fminf(fmaxf(a + da_k, a_min), a_max) with the extremes of the table of pi_infer_set_expect_greedy;
+ * (s', r_k, done_k) = step_dynamics(s, a_k) (consecutive points with equal da share the step); E_k = 0 when done_k, else
+ * every non-zero dx_k[d] is added to s'[d] with one float32 add (d in the handle's dimension order) and E_k is the
+ * interpolation there; q_k = r_k + gamma * E_k, a multiply then an add; Q = p_0 * q_0, then Q = fmaf(p_k, q_k, Q).  The
+ * argmax is pi_infer_greedy's.  With the one-point zero set (da = dx = 0, p = 1) every output is pi_infer_greedy's and
+ * pi_infer_rollout_greedy's, bit for bit; at a non-terminal node, with the set and the value function of a solver handle,
+ * the index is what pi_expect_improve_sweep writes there.
+ *   pi_infer_set_expect_greedy  host array: the action table (n_actions >= 1 finite float32), copied to the device — the
+ *                       handle's own copy; builds the handle's SEVENTH module: its grid + the plugin last given to
+ *                       pi_infer_set_dynamics + the functions of csrc/pi_greedy_kernels.hip and
+ *                       csrc/pi_stochastic_kernels.hip + csrc/pi_expect_greedy_kernels.hip.  Needs pi_infer_set_values
+ *                       and pi_infer_set_dynamics.  Same cache, flags and log convention as pi_infer_set_dynamics;
+ *                       device = -1 handles: compile check.  pi_infer_set_dynamics drops the module again (the next call
+ *                       then fails, naming pi_infer_set_expect_greedy)
+ *   pi_infer_set_disturbances  the set of that controller: arguments, validation and NULL-means-zeros rules of
+ *                       pi_set_disturbances (K <= 64, finite values, weights >= 0 summing to 1 within 1e-4; state_offsets
+ *                       (K, D) in the handle's dimension order); K = 0 drops the set.  Run-time data: an upload, never a
+ *                       build, and independent of the module (before or after it, kept across pi_infer_set_dynamics).
+ *                       Synchronises the device before it overwrites the table
+ *   pi_infer_expect_greedy  pi_infer_greedy with Q_K in place of Q: the same arguments, outputs and rules.  Refused
+ *                       without the module or without a set, naming the call that is missing.  Asynchronous.
+ *   pi_infer_rollout_expect_greedy  pi_infer_rollout_stochastic with the lookahead in place of the interpolated action.
+ *                       Per step of a running episode: best = argmax_a Q_K(s, a) with `lookahead_gamma`, a =
+ *                       action_space[best]; then steps 2-5 of the stochastic rollouts above with the same draws from the
+ *                       same counters (an exploring step takes its random action instead, from this module's table),
+ *                       step_dynamics running once more on the action finally taken.  epsilon, action_noise,
+ *                       state_noise, seed, first_episode, gamma and the outputs as in pi_infer_rollout_stochastic;
+ *                       neither gamma may be NaN.  Needs no policy.  Refused without the module or without a set; every
+ *                       refusal is an error code and pi_last_error, never a launch.  m == 0 is a no-op.  Asynchronous.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pi_infer pi_infer;
 pi_infer* pi_infer_create(int device, int D, const float* lo, const float* hi, const int32_t* grid_shape,
@@ -627,6 +660,15 @@ int pi_infer_rollout_stochastic(pi_infer* h, const float* d_start, int64_t m, in
                                 int traj_every, void* stream);
 int pi_infer_random_words(pi_infer* h, uint64_t seed, uint64_t first_episode, int64_t m, uint32_t step, uint32_t block,
                           uint32_t* d_words, void* stream);
+int pi_infer_set_expect_greedy(pi_infer* h, const float* action_space, int n_actions, char* log, size_t log_len);
+int pi_infer_set_disturbances(pi_infer* h, int K, const float* action_offsets, const float* state_offsets,
+                              const float* weights);
+int pi_infer_expect_greedy(pi_infer* h, const float* d_points, int64_t m, float gamma, int32_t* d_best, float* d_action,
+                           float* d_q_best, float* d_q_all, void* stream);
+int pi_infer_rollout_expect_greedy(pi_infer* h, const float* d_start, int64_t m, int n_steps, float gamma,
+                                   float lookahead_gamma, float epsilon, float action_noise, const float* state_noise,
+                                   uint64_t seed, uint64_t first_episode, float* d_final, float* d_return,
+                                   int32_t* d_length, uint8_t* d_terminated, float* d_traj, int traj_every, void* stream);
 
 /* Tuning: the `what` of pi_set_option. */
 enum pi_option_code {

@@ -20,9 +20,13 @@ the env's start distribution (envs.<Env>.start_states, seeded by --seed; crane: 
 episode; those four flags are then honoured, not ignored.  The 6-D swing-up also writes results/last_trajectory.npz
 (the last 100 states of every episode), the file the reference's scoring script reads.
 
---controller {policy,greedy} (extension, default policy) chooses what acts in those episodes: the interpolated policy table,
-or the greedy one-step lookahead on the interpolated value function (solver.rollout(controller="greedy")), which needs
-only V.  The printed lines and last_trajectory.npz keep their form.
+--controller {policy,greedy,expected} (extension, default policy) chooses what acts in those episodes: the interpolated
+policy table, the greedy one-step lookahead on the interpolated value function (solver.rollout(controller="greedy")), which
+needs only V, or that lookahead with the expectation over a disturbance set inside it (solver.rollout(controller=
+"expected"); csrc/pi_expect_greedy_kernels.hip).  The set is the solver's — trained with --train-*, or carried by the
+archive; failing that it is the rule --action-noise, --state-noise and --train-noise-points name (training_disturbances);
+with neither the runner exits with a message.  Unlike greedy, expected runs under --epsilon, --action-noise and
+--state-noise.  The printed lines and last_trajectory.npz keep their form.
 
 --epsilon E, --action-noise A and --state-noise X [X ...] (extensions, with --rollout, default 0) make those episodes
 stochastic (solver.rollout(epsilon=..., action_noise=..., state_noise=...); csrc/pi_stochastic_kernels.hip): a step takes
@@ -169,9 +173,11 @@ def build_parser(env_name: str, default_save: str) -> argparse.ArgumentParser:
     p.add_argument("--rollout", action="store_true",
                    help="(extension) after training / loading, roll the policy out on the GPU: --episodes episodes of "
                         "--steps steps from the env's start states (--seed; crane: --start-x), one line per episode")
-    p.add_argument("--controller", choices=("policy", "greedy"), default="policy",
-                   help="(extension, with --rollout) what acts in the episodes: the interpolated policy table, or the "
-                        "greedy one-step lookahead on the interpolated value function")
+    p.add_argument("--controller", choices=("policy", "greedy", "expected"), default="policy",
+                   help="(extension, with --rollout) what acts in the episodes: the interpolated policy table, the "
+                        "greedy one-step lookahead on the interpolated value function, or that lookahead with the "
+                        "expectation over the solver's disturbance set (else the rule --action-noise / --state-noise / "
+                        "--train-noise-points name) inside it")
     p.add_argument("--epsilon", type=float, default=0.0, metavar="E",
                    help="(extension, with --rollout) probability that a step takes a uniformly random action instead")
     p.add_argument("--action-noise", type=float, default=0.0, metavar="A",
@@ -199,11 +205,11 @@ STEADY_WINDOW = 100     # states per episode in results/last_trajectory.npz (the
 
 def evaluate(env_name: str, pi, episodes: int, steps: int, seed: int, start_x: float | None = None,
              traj_path: Path | None = None, controller: str = "policy", epsilon: float = 0.0, action_noise: float = 0.0,
-             state_noise=None):
+             state_noise=None, disturbances=None):
     """--rollout: `episodes` closed-loop episodes of at most `steps` steps in one kernel launch (solver.rollout), one
     line each.  `traj_path`: also dump the last min(100, length + 1) states of every episode, concatenated, as the
     reference's evaluate() does for its scoring script (double_cartpole_swingup_cuda.py:583-592).  `controller`:
-    "policy" or "greedy" (--controller).  `epsilon`, `action_noise`, `state_noise` (--epsilon, --action-noise,
+    "policy", "greedy" or "expected" (--controller; `disturbances`: the set of "expected" when the solver has none).  `epsilon`, `action_noise`, `state_noise` (--epsilon, --action-noise,
     --state-noise): a stochastic rollout, its stream seeded by `seed` like the starts.  Returns the RolloutResult."""
     import numpy as np
     from dynamicprogramming_amd import envs
@@ -211,8 +217,9 @@ def evaluate(env_name: str, pi, episodes: int, steps: int, seed: int, start_x: f
     rng = np.random.default_rng(seed)
     kw = {} if start_x is None else {"start_x": start_x}
     starts = cls.start_states(rng, episodes, **kw)
+    extra = {} if disturbances is None else {"disturbances": disturbances}
     res = pi.rollout(starts, steps, gamma=1.0, record_every=1 if traj_path is not None else 0, controller=controller,
-                     epsilon=epsilon, action_noise=action_noise, state_noise=state_noise, seed=seed)
+                     epsilon=epsilon, action_noise=action_noise, state_noise=state_noise, seed=seed, **extra)
     for ep in range(episodes):
         outcome = "terminated" if res.terminated[ep] else f"{steps} steps"
         final = "  ".join(f"{v:+.4f}" for v in res.states[ep])
@@ -293,9 +300,16 @@ def main(env_name: str, default_save: str, argv=None):
         pi = train(env_name, args.bins, path, value_iteration=args.value_iteration, coarse_bins=args.coarse_bins,
                    train_action_noise=args.train_action_noise, train_state_noise=args.train_state_noise,
                    train_noise_points=args.train_noise_points, **kw)
+    lookahead_set = None
+    if args.rollout and args.controller == "expected" and getattr(pi, "disturbances", None) is None:
+        lookahead_set = training_disturbances(env_name, args.action_noise, args.state_noise, args.train_noise_points)
+        if lookahead_set is None:
+            sys.exit(f"[{env_name}] --controller expected needs a disturbance set: train with --train-action-noise / "
+                     "--train-state-noise, load an archive that carries one, or give --action-noise / --state-noise")
+        print(f"[{env_name}] expected lookahead over {lookahead_set.K} disturbance points of the rollout's noise")
     if args.rollout:
         evaluate(env_name, pi, args.episodes, args.steps, args.seed, start_x=getattr(args, "start_x", None),
                  traj_path=Path("results") / "last_trajectory.npz" if env_name == "double_cartpole_swingup" else None,
                  controller=args.controller, epsilon=args.epsilon, action_noise=args.action_noise,
-                 state_noise=args.state_noise)
+                 state_noise=args.state_noise, disturbances=lookahead_set)
     return pi

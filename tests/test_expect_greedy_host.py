@@ -1,0 +1,399 @@
+"""
+Expected-value greedy control, the part that needs no GPU: the numpy twins (dynamicprogramming_amd.noise.
+expected_greedy_action, expected_greedy_rollout) reduce to the greedy twins with the one-point zero set, return the
+expectation improvement sweep's policy at the live grid nodes (where the deterministic lookahead does not), draw the
+stochastic rollouts' stream from the same counters, and apply explore, noise, clamp, step and state noise in the
+documented order; the kernels compile for gfx950 behind every D without scratch as one more cache object; the C ABI
+declares, exports and binds the four entry points and refuses what it must; the runners parse --controller expected.
+The device half is tests/test_gpu_expect_greedy.py.
+"""
+from __future__ import annotations
+
+import re
+import subprocess
+from itertools import product
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from dynamicprogramming_amd import _native, envs, noise
+from dynamicprogramming_amd.noise import Disturbances
+from tests import expect_greedy_cases as C
+from tests import helpers as H
+from utils import barycentric as B
+
+ROOT = Path(__file__).resolve().parents[1]
+SYMBOLS = ("pi_infer_set_expect_greedy", "pi_infer_set_disturbances", "pi_infer_expect_greedy",
+           "pi_infer_rollout_expect_greedy")
+
+
+def _host_engine(c, cache_dir):
+    return _native.InferenceEngine(*c["grid"], c["bits"], device=-1, cache_dir=cache_dir)
+
+
+# ── 1. the zero set is the greedy controller ──────────────────────────────────────────────────────────────────────────
+@pytest.mark.parametrize("name,shape", C.GRIDS, ids=C.IDS)
+def test_zero_set_twins_are_the_greedy_twins(name, shape):
+    c = C.case(name, shape)
+    none = Disturbances.none(c["D"])
+    pts = C.query_points(c, 300)
+    want = B.greedy_action(c["chk"].step, pts, c["V"], c["acts"], *c["grid"], c["gamma"], q_values=True)
+    got = noise.expected_greedy_action(c["chk"].step, pts, none, c["V"], c["acts"], *c["grid"], c["gamma"], q_values=True)
+    assert len(got) == 4 and got[0].dtype == np.int32 and np.array_equal(got[0], want[0])
+    for g, w, what in zip(got[1:3], want[1:3], ("action", "best Q")):
+        H.assert_bits_equal(g, w, f"{name}: {what}")
+    nan = np.isnan(want[3])
+    assert nan.any() and np.array_equal(np.isnan(got[3]), nan)                 # the NaN coordinate's row
+    H.assert_bits_equal(got[3][~nan], want[3][~nan], f"{name}: Q matrix")
+    assert len(noise.expected_greedy_action(c["chk"].step, pts, none, c["V"], c["acts"], *c["grid"], c["gamma"])) == 3
+    starts = H.sample_states(np.random.default_rng(2), c["bins"], 120)
+    for gamma, every in ((1.0, 0), (0.99, 7)):
+        want = B.greedy_rollout(c["chk"].step, starts, 25, c["V"], c["acts"], *c["grid"], c["gamma"], gamma=gamma,
+                                record_every=every)
+        got = noise.expected_greedy_rollout(c["chk"].step, starts, 25, none, c["V"], c["acts"], *c["grid"], c["gamma"],
+                                            gamma=gamma, record_every=every, state_noise=np.zeros(c["D"]), seed=9,
+                                            first_episode=77)
+        C.assert_same_rollout(got, want, f"{name} gamma={gamma} every={every}")
+
+
+# ── 2. the query at the nodes is the sweep ────────────────────────────────────────────────────────────────────────────
+@pytest.mark.parametrize("name,shape", C.GRIDS, ids=C.IDS)
+def test_query_at_the_live_nodes_is_the_expectation_improvement_sweep(name, shape):
+    c = C.case(name, shape)
+    dist = C.multi_point_set(name)
+    assert dist.K > 1
+    live = ~c["term"]
+    assert live.any()
+    nodes = np.ascontiguousarray(c["states"][live], np.float32)
+    pol0 = np.zeros(len(c["states"]), np.int32)
+    sweep, _ = noise.expected_improve(c["chk"].step, c["states"], pol0, c["V"], c["term"], dist, c["acts"], *c["grid"],
+                                      c["gamma"])
+    best, act, _ = noise.expected_greedy_action(c["chk"].step, nodes, dist, c["V"], c["acts"], *c["grid"], c["gamma"])
+    assert np.array_equal(best, sweep[live]), f"{int((best != sweep[live]).sum())} of {int(live.sum())} nodes differ"
+    H.assert_bits_equal(act, c["acts"][sweep[live]], "action values")
+    plain = B.greedy_action(c["chk"].step, nodes, c["V"], c["acts"], *c["grid"], c["gamma"])[0]
+    differ = int((plain != best).sum())
+    print(f"{name}: the deterministic lookahead differs on {differ} of {int(live.sum())} live nodes")
+    assert differ >= 1, "the guard: this set must tell the two controllers apart"
+
+
+# ── 3. the stream ─────────────────────────────────────────────────────────────────────────────────────────────────────
+def test_rollout_twin_draws_the_stochastic_stream_and_does_not_depend_on_the_cut():
+    name, shape = C.GRIDS[1]
+    c = C.case(name, shape)
+    dist = C.multi_point_set(name)
+    step, V, acts, grid, g = c["chk"].step, c["V"], c["acts"], c["grid"], c["gamma"]
+    starts = H.sample_states(np.random.default_rng(3), c["bins"], 200)
+    kw = dict(action_noise=2.0, state_noise=[0.01, 0.0, 0.02, 0.05], seed=2 ** 40 + 3)
+    # epsilon = 1: the controller plays no part, the random baseline's bits
+    want = B.stochastic_rollout(step, starts, 30, None, acts, *grid, c["bits"], 1.0, kw["action_noise"], kw["state_noise"],
+                                kw["seed"], first_episode=5, gamma=0.99, record_every=5)
+    got = noise.expected_greedy_rollout(step, starts, 30, dist, V, acts, *grid, g, gamma=0.99, record_every=5, epsilon=1.0,
+                                        first_episode=5, **kw)
+    C.assert_same_rollout(got, want, "epsilon = 1 against the random baseline")
+    # a batch cut in two with the matching first_episode
+    run = lambda s, first: noise.expected_greedy_rollout(step, s, 30, dist, V, acts, *grid, g, gamma=0.99,   # noqa: E731
+                                                         record_every=5, epsilon=0.3, first_episode=first, **kw)
+    whole, a, b = run(starts, 0), run(starts[:70], 0), run(starts[70:], 70)
+    joined = B.RolloutResult(*(np.concatenate([x, y], axis=1 if x.ndim == 3 else 0) for x, y in zip(a, b)))
+    C.assert_same_rollout(whole, joined, "200 episodes against 70 + 130")
+    assert not np.array_equal(run(starts[70:], 0).returns, b.returns), "first_episode must select the stream"
+
+
+# ── 4. a hand-computed case ───────────────────────────────────────────────────────────────────────────────────────────
+def test_hand_computed_case_on_a_stub_step():
+    """A 2 x 2 grid on [0, 1]^2 with V = 8 * x0 and a stub whose reward IS the action it was handed, whose successor
+    keeps x0 and which is `done` where x0 > 0.5.  Set: da = (0.5, 0.5, -0.5), dx = ((0, 0), (0.5, 0), (0, 0)), p = (1/4,
+    1/4, 1/2); actions (-1, 0.25, 1); gamma = 0.5.  At s = (0.25, 0), every figure exact in float32:
+      a = 1:    q = (1 + 0.5 * 2, 1 + 0.5 * 6, 0.5 + 0.5 * 2) = (2, 4, 1.5)           the first two clamped from 1.5 to 1
+      a = 0.25: q = (0.75 + 1, 0.75 + 3, -0.25 + 1) = (1.75, 3.75, 0.75)
+      a = -1:   q = (-0.5 + 1, -0.5 + 3, -1 + 1) = (0.5, 2.5, 0)                       the last clamped from -1.5 to -1
+    Q = (0.75, 1.75, 2.25) in table order; at the `done` state (0.75, 0) E = 0: Q = (-0.75, 0.25, 0.75)."""
+    acts = np.array([-1.0, 0.25, 1.0], np.float32)
+    grid = (np.zeros(2, np.float32), np.ones(2, np.float32), np.array([2, 2], np.int32), np.array([2, 1], np.int32))
+    V = np.array([0.0, 0.0, 8.0, 8.0], np.float32)
+    dist = Disturbances([0.5, 0.5, -0.5], [[0, 0], [0.5, 0], [0, 0]], [0.25, 0.25, 0.5])
+    calls = []
+
+    def step(states, a):
+        calls.append(len(states))
+        nxt = np.zeros_like(states)
+        nxt[:, 0] = states[:, 0]
+        return nxt, np.array(a, np.float32), states[:, 0] > 0.5
+    pts = np.array([[0.25, 0.0], [0.75, 0.0]], np.float32)
+    best, act, qb, Q = noise.expected_greedy_action(step, pts, dist, V, acts, *grid, 0.5, q_values=True)
+    assert Q.tolist() == [[0.75, 1.75, 2.25], [-0.75, 0.25, 0.75]]
+    assert best.tolist() == [2, 2] and act.tolist() == [1.0, 1.0] and qb.tolist() == [2.25, 0.75]
+    assert calls == [2] * 6, "points 0 and 1 share da: two steps per action, not three"
+    # the rollout, one step: the return IS the action the step was handed
+    m = 4096
+    starts = np.zeros((m, 2), np.float32)
+    starts[:, 0] = np.where(np.arange(m) % 2 == 0, 0.25, 0.75).astype(np.float32)
+    seed, first = 11, 2 ** 33
+    w0, w1 = B.random_words(seed, first, m, 0, 0), B.random_words(seed, first, m, 0, 1)
+    picked = acts[B.random_action_index(w0[:, 1], 3)]
+    run = lambda **kw: noise.expected_greedy_rollout(step, starts, 1, dist, V, acts, *grid, 0.5, seed=seed,   # noqa: E731
+                                                     first_episode=first, **kw)
+    res = run()
+    assert (res.returns == 1.0).all() and (res.lengths == 1).all()          # the lookahead's action everywhere
+    explore = (w0[:, 0] >> 8) < B.explore_threshold(0.5)
+    assert 0.4 < explore.mean() < 0.6
+    calls.clear()
+    res = run(epsilon=0.5)
+    H.assert_bits_equal(res.returns, np.where(explore, picked, np.float32(1.0)).astype(np.float32), "explore, else look ahead")
+    assert calls == [int((~explore).sum())] * 6 + [m], "an exploring episode is not looked ahead for"
+    res = run(epsilon=0.5, action_noise=0.5)                                  # noise after the choice, then the clamp
+    want = np.fmin(np.fmax(np.where(explore, picked, np.float32(1.0)).astype(np.float32) + np.float32(0.5) * B.sym(w0[:, 2]),
+                           np.float32(-1.0)), np.float32(1.0))
+    H.assert_bits_equal(res.returns, want, "noisy actions")
+    assert (res.returns == 1.0).sum() > 10 and (res.returns == -1.0).sum() > 10 and len(np.unique(res.returns)) > 1000
+    res = run(state_noise=[0.125, 0.0])                                       # after the step, not on a done step
+    done = starts[:, 0] > 0.5
+    assert np.array_equal(res.terminated, done)
+    H.assert_bits_equal(res.states[done, 0], starts[done, 0], "done successors are stored undisturbed")
+    H.assert_bits_equal(res.states[~done, 0], np.float32(0.25) + np.float32(0.125) * B.sym(w1[~done, 0]), "dimension 0 noise")
+    assert not res.states[:, 1].any()
+    assert (res.returns == 1.0).all()                                         # the lookahead saw the undisturbed state
+    for bad in (dict(epsilon=1.5), dict(action_noise=-1.0), dict(state_noise=[0.1, 0.1, 0.1]), dict(action_noise=float("nan"))):
+        with pytest.raises(ValueError):
+            run(**bad)
+
+
+# ── 5. the module ─────────────────────────────────────────────────────────────────────────────────────────────────────
+@pytest.mark.parametrize("name,shape", C.GRIDS, ids=C.IDS)
+def test_expect_greedy_kernels_compile_for_gfx950_without_a_gpu(name, shape, tmp_path):
+    c = C.case(name, shape)
+    eng = _host_engine(c, tmp_path)
+    eng.set_values(np.zeros(len(c["states"]), np.float32))
+    eng.set_dynamics(envs.dynamics_source(name))
+    before = set(tmp_path.glob("pi_*.hsaco"))
+    log = eng.set_expect_greedy(c["acts"])
+    assert isinstance(log, str) and "error" not in log.lower()
+    (obj,) = set(tmp_path.glob("pi_*.hsaco")) - before                      # one more cache object
+    blob = obj.read_bytes()
+    assert blob[:4] == b"\x7fELF" and b"pi_expect_greedy_kernel" in blob and b"pi_expect_greedy_rollout_kernel" in blob
+    for other in (b"pi_rollout_kernel", b"pi_greedy_kernel", b"pi_greedy_rollout_kernel", b"pi_stochastic_rollout_kernel",
+                  b"pi_random_words_kernel"):
+        assert other not in blob, other                                        # the shared functions only
+    eng.set_expect_greedy(c["acts"][:1])                                       # again: served from the cache, replaces
+    dist = C.multi_point_set(name)
+    assert eng.set_disturbances(dist.action_offsets, dist.state_offsets, dist.weights) == dist.K   # an upload: no build
+    assert len(list(tmp_path.glob("pi_*.hsaco"))) == len(before) + 1
+    with pytest.raises(_native.NativeError, match="host-only"):
+        eng.expect_greedy(4096, 4, 0.99, d_best=4096)
+    with pytest.raises(_native.NativeError, match="host-only"):
+        eng.rollout_expect_greedy(4096, 4, 10, 0.99)
+    # the greedy and the stochastic module still build from the files the new unit shares with them
+    eng.set_greedy(c["acts"])
+    eng.set_stochastic(c["acts"])
+    assert len(list(tmp_path.glob("pi_*.hsaco"))) == len(before) + 3
+    eng.close()
+
+
+def test_expect_greedy_kernels_do_not_spill(tmp_path):
+    """Both kernels without scratch in every D, on the ahead-of-time build of the translation unit
+    pi_infer_set_expect_greedy hands to hipRTC (restated here from the kernel file's header), the method of
+    tests/test_stochastic_host.py.  The register counts are printed: the kernel file's header quotes them."""
+    import __graft_entry__ as G
+    csrc = ROOT / "dynamicprogramming_amd" / "csrc"
+    parts = [(csrc / f).read_text() for f in ("pi_rollout_kernels.hip", "pi_greedy_kernels.hip", "pi_stochastic_kernels.hip",
+                                              "pi_expect_greedy_kernels.hip")]
+    pi_math = (ROOT / "include" / "pi_math.h").read_text()
+    for name, bins in (("pendulum", 200), ("cartpole_swingup", 50), ("double_cartpole", 25), ("double_cartpole_swingup", 25)):
+        D = envs.ENVS[name]._D
+        c = C.case(name, (2,) * D)
+        tabs = H.env_bins(name, (bins,) * D)
+        import oracle
+        lo, hi, gshape, strides = oracle.grid_metadata(tabs)
+
+        def braces(v, fmt):
+            return "{" + ",".join(fmt(x) for x in v) + "}"
+
+        def hexf(x):
+            return float(np.float32(x)).hex() + "f"
+        text = (f"#define PI_EXPECT_GREEDY 1\n#define PI_GREEDY 1\n#define PI_STOCHASTIC 1\n#define PI_D {D}\n"
+                f"#define PI_LO_INIT {braces(lo, hexf)}\n#define PI_HI_INIT {braces(hi, hexf)}\n"
+                f"#define PI_SHAPE_INIT {braces(gshape, str)}\n#define PI_STRIDES_INIT {braces(strides, str)}\n"
+                f"#define PI_BITS_INIT {braces(c['bits'], lambda r: braces(r, str))}\n"
+                f"{pi_math}\n#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n"
+                f"{envs.dynamics_source(name)}\n" + "\n".join(parts) + "\n")
+        src = tmp_path / f"{name}.hip"
+        src.write_text(text)
+        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
+                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
+                              "-o", str(tmp_path / f"{name}.hsaco")], capture_output=True, text=True)
+        assert res.returncode == 0, res.stderr[-2000:]
+        usage, fn = {}, None
+        for line in res.stderr.splitlines():
+            if "Function Name:" in line:
+                fn = line.split("Function Name:")[1].split()[0]
+                usage[fn] = {}
+            elif fn and " VGPRs:" in line:
+                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
+            elif fn and "ScratchSize" in line:
+                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+        assert set(usage) == {"pi_expect_greedy_kernel", "pi_expect_greedy_rollout_kernel"}
+        for fn, k in usage.items():
+            print(f"{fn} {name} {bins}^{D}: {k}")
+            assert k["scratch"] == 0 and k["vgpr"] <= 512, (name, fn, k)
+
+
+# ── 6. symbols and refusals ───────────────────────────────────────────────────────────────────────────────────────────
+def test_new_symbols_are_declared_exported_and_bound():
+    header = (ROOT / "include" / "pi_mi355.h").read_text()
+    lib = _native.lib()
+    for sym in SYMBOLS:
+        assert re.search(rf"^int {sym}\(pi_infer\* h,", header, re.M), sym
+        assert header.count(sym) >= 2, f"{sym} has no comment in the header"
+        assert hasattr(lib, sym) and sym in _native.SIGNATURES
+    for method in ("set_expect_greedy", "set_disturbances", "expect_greedy", "rollout_expect_greedy"):
+        assert callable(getattr(_native.InferenceEngine, method))
+    for method in ("set_expected_greedy", "set_disturbances", "expected_greedy"):
+        assert callable(getattr(B.DevicePolicy, method))
+    assert callable(noise.expected_greedy_action) and callable(noise.expected_greedy_rollout)
+    assert lib.pi_abi_version() == _native.ABI_VERSION == 12
+    assert re.search(r"#define PI_MI355_ABI_VERSION 12\b", header)
+    csrc = ROOT / "dynamicprogramming_amd" / "csrc"
+    assert "pi_expect_greedy.cpp" in (csrc / "Makefile").read_text()
+    assert "pi_expect_greedy.cpp" in (csrc / "pi_internal.h").read_text()
+    assert "set_expect_greedy" in (ROOT / "__graft_entry__.py").read_text()
+
+
+def test_refusals_are_error_codes(tmp_path):
+    c = C.case("pendulum", (12, 9))
+    acts, dyn, Err = c["acts"], envs.dynamics_source("pendulum"), _native.NativeError
+    eng = _host_engine(c, tmp_path)
+    launches = (lambda **kw: eng.expect_greedy(4096, 4, kw.pop("gamma", 0.99), d_best=4096),
+                lambda **kw: eng.rollout_expect_greedy(4096, 4, 10, kw.pop("lookahead_gamma", 0.99), **kw))
+    for launch in launches:
+        with pytest.raises(Err, match="no expected-greedy module.*pi_infer_set_expect_greedy"):
+            launch()
+    with pytest.raises(Err, match="pi_infer_set_values was never called"):
+        eng.set_expect_greedy(acts)
+    eng.set_values(c["V"])
+    with pytest.raises(Err, match="pi_infer_set_dynamics was never called"):
+        eng.set_expect_greedy(acts)
+    eng.set_dynamics(dyn)
+    with pytest.raises(Err, match="at least one action"):
+        eng.set_expect_greedy(np.zeros(0, np.float32))
+    with pytest.raises(Err, match="action_space"):
+        eng.set_expect_greedy(None)
+    with pytest.raises(Err, match=r"action_space\[1\] is not finite"):
+        eng.set_expect_greedy(np.array([0.0, np.nan, 1.0], np.float32))
+    eng.set_expect_greedy(acts)
+    for launch in launches:                                                   # the module, but no set
+        with pytest.raises(Err, match="no disturbance set.*pi_infer_set_disturbances"):
+            launch()
+    # the set: the rules of pi_set_disturbances
+    with pytest.raises(Err, match=r"pi_infer_set_disturbances: K must be in \[0, 64\]"):
+        eng.set_disturbances(None, None, np.full(65, 1 / 65, np.float32))
+    for w, why in (([0.5, 0.6], "weights sum"), ([1.5, -0.5], "weight 1 is negative"), ([np.nan, 1.0], "not finite")):
+        with pytest.raises(Err, match=why):
+            eng.set_disturbances(None, None, w)
+    with pytest.raises(Err, match="point 1 holds a value that is not finite"):
+        eng.set_disturbances([0.0, np.inf], None, [0.5, 0.5])
+    with pytest.raises(ValueError):
+        eng.set_disturbances(None, np.zeros((2, 3), np.float32), [0.5, 0.5])
+    assert eng.set_disturbances(None, None, [0.25, 0.75]) == 2                # NULL offsets are zeros
+    assert eng.set_disturbances(None, None, None) == 0                        # K = 0 drops the set
+    with pytest.raises(Err, match="no disturbance set"):
+        launches[0]()
+    eng.set_disturbances(None, None, np.full(64, 1 / 64, np.float32))         # K = 64 is served
+    ok = dict(epsilon=0.0, action_noise=0.0, state_noise=None)
+    for kw, why in ((dict(epsilon=-0.01), "epsilon"), (dict(epsilon=1.01), "epsilon"), (dict(epsilon=float("nan")), "epsilon"),
+                    (dict(action_noise=-1.0), "action_noise"), (dict(action_noise=float("inf")), "action_noise"),
+                    (dict(state_noise=[0.0, -0.5]), r"state_noise\[1\]"), (dict(state_noise=[float("nan"), 0.0]), r"state_noise\[0\]"),
+                    (dict(gamma=float("nan")), "pi_infer_rollout_expect_greedy: gamma is NaN"),
+                    (dict(lookahead_gamma=float("nan")), "lookahead_gamma is NaN")):
+        with pytest.raises(Err, match=why):
+            launches[1](**{**ok, **kw})
+    with pytest.raises(Err, match="pi_infer_expect_greedy: gamma is NaN"):
+        launches[0](gamma=float("nan"))
+    with pytest.raises(Err, match="m < 0"):
+        eng.expect_greedy(4096, -1, 0.99, d_best=4096)
+    for launch in launches:                                                   # everything valid: only the handle is in the way
+        with pytest.raises(Err, match="host-only"):
+            launch()
+    eng.set_dynamics(dyn)                                                     # a new plugin drops the module, not the set
+    for launch in launches:
+        with pytest.raises(Err, match="no expected-greedy module"):
+            launch()
+    eng.set_expect_greedy(acts)
+    with pytest.raises(Err, match="host-only"):
+        launches[0]()
+    eng.close()
+    lib = _native.lib()
+    assert lib.pi_infer_set_expect_greedy(None, None, 0, None, 0) == 1        # a null handle
+    assert lib.pi_infer_set_disturbances(None, 0, None, None, None) == 1
+    assert lib.pi_infer_expect_greedy(None, None, 0, 0.9, None, None, None, None, None) == 1
+    assert lib.pi_infer_rollout_expect_greedy(None, None, 0, 0, 1.0, 0.9, 0.0, 0.0, None, 0, 0, None, None, None, None, None,
+                                              0, None) == 1
+
+
+def test_front_end_refusals_need_no_gpu(tmp_path):
+    dp = object.__new__(B.DevicePolicy)
+    dp.D = 2
+    pts = np.zeros((2, 2), np.float32)
+    with pytest.raises(ValueError, match="lookahead_gamma"):
+        dp.rollout(pts, 5, controller="expected")
+    with pytest.raises(RuntimeError, match="set_expected_greedy"):
+        dp.rollout(pts, 5, controller="expected", lookahead_gamma=0.99, epsilon=0.3, action_noise=0.5, state_noise=0.1)
+    with pytest.raises(RuntimeError, match="set_expected_greedy"):
+        dp.expected_greedy(pts, 0.99)
+    dp._expected_actions = np.zeros(3, np.float32)
+    with pytest.raises(RuntimeError, match="set_disturbances"):
+        dp.rollout(pts, 5, controller="expected", lookahead_gamma=0.99)
+    with pytest.raises(RuntimeError, match="set_disturbances"):
+        dp.expected_greedy(pts, 0.99)
+    for kw in (dict(epsilon=1.5), dict(action_noise=-1.0), dict(state_noise=[0.1, 0.2, 0.3])):
+        with pytest.raises(ValueError, match=next(iter(kw))):
+            dp.rollout(pts, 5, controller="expected", lookahead_gamma=0.99, **kw)
+    for kw in (dict(epsilon=0.1), dict(action_noise=0.5), dict(state_noise=0.1)):     # the greedy controller still refuses noise
+        with pytest.raises(ValueError, match="stochastic greedy controller does not exist"):
+            dp.rollout(pts, 5, controller="greedy", lookahead_gamma=0.99, **kw)
+    with pytest.raises(ValueError, match="controller"):
+        dp.rollout(pts, 5, controller="expectation")
+    # a load()ed archive without a set, and one that carries its set
+    g = H.golden("reference_results")
+    shape = tuple(int(x) for x in g["mountain_car_grid_shape"])
+    import oracle
+    bins = H.env_bins("mountain_car", shape)
+    lo, hi, gshape, strides = oracle.grid_metadata(bins)
+    bits = np.array(list(product([0, 1], repeat=2)), dtype=np.int32)
+    fields = dict(value_function=g["mountain_car_value_function"], policy=g["mountain_car_policy"], bounds_low=lo,
+                  bounds_high=hi, grid_shape=gshape, strides=strides, corner_bits=bits,
+                  action_space=g["mountain_car_action_space"], states_space=oracle.states_from_bins(bins))
+    np.savez(tmp_path / "plain.npz", **fields)
+    np.savez(tmp_path / "noisy.npz", disturbances=Disturbances.uniform(2, action_noise=0.5).table(), **fields)
+    starts = envs.MountainCarCuda.start_states(np.random.default_rng(0), 4)
+    plain = envs.MountainCarCuda.load(tmp_path / "plain.npz")
+    with pytest.raises(RuntimeError, match="set_disturbances"):
+        plain.rollout(starts, 10, controller="expected")
+    with pytest.raises(ValueError, match="disturbances="):
+        plain.rollout(starts, 10, controller="greedy", disturbances=Disturbances.none(2))
+    with pytest.raises(ValueError, match="stochastic greedy controller does not exist"):
+        plain.rollout(starts, 10, controller="greedy", action_noise=0.2)
+    from dynamicprogramming_amd import solver as S
+    if not S.GPU_AVAILABLE:                                 # past every front-end check: only the GPU is missing
+        noisy = envs.MountainCarCuda.load(tmp_path / "noisy.npz")
+        assert noisy.disturbances.K == 3
+        for pi, kw in ((noisy, {}), (plain, dict(disturbances=Disturbances.none(2)))):
+            with pytest.raises(RuntimeError, match="GPU"):
+                pi.rollout(starts, 10, controller="expected", action_noise=0.2, **kw)
+
+
+@pytest.mark.parametrize("name", H.ENV_NAMES)
+def test_controller_expected_parses(name):
+    from runners import _cli
+    p = _cli.build_parser(name, f"results/{name}_cuda_policy.npz")
+    a = p.parse_args(["--rollout", "--controller", "expected", "--action-noise", "0.5", "--state-noise", "0.01",
+                      "--epsilon", "0.1"])
+    assert a.controller == "expected" and _cli.ignored_flags(a) == []
+    assert _cli.ignored_flags(p.parse_args(["--controller", "expected"])) == ["--controller"]
+    assert p.parse_args([]).controller == "policy"
+    # the set the runner builds when the solver has none: the rule of the rollout's noise
+    D = envs.ENVS[name]._D
+    dist = _cli.training_disturbances(name, a.action_noise, [0.01] + [0.0] * (D - 1), a.train_noise_points)
+    assert dist.D == D and dist.K == 9
+    assert _cli.training_disturbances(name, 0.0, None, 3) is None            # neither: the runner exits with a message

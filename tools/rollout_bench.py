@@ -28,7 +28,16 @@ every dimension, m = 4 096 episodes of --steps steps; per config the fused stoch
 step a query, the words of pi_infer_random_words, one pi_probe_step and the mixing as torch ops), the fused deterministic
 rollout of the same batch and the random-policy baseline, then the registers and scratch of both kernels.  The table is
 written to --out.
-usage: python tools/rollout_bench.py [--hybrid | --greedy | --stochastic] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
+--expected: the expected-value greedy controller instead (pi_infer_rollout_expect_greedy, csrc/pi_expect_greedy_kernels.hip):
+C2, C3 and the 25^6 double cart-pole with V ~ 30 N(0, 1) and a random policy (seeded), the noise of --stochastic, m = 4 096
+episodes of --steps steps; per config the fused expected rollout over K = 1 (the zero set), 9 (action x one velocity) and
+27 (action x two state dimensions) disturbance points, the loop it replaces at K = 9 (per step one pi_infer_expect_greedy
+launch, the words of pi_infer_random_words, one pi_probe_step and the mixing as torch ops) and the fused greedy and
+interpolated-policy rollouts of the same batch, then the registers and scratch of both kernels; then the closed loop under
+the noise planned for, on the two settings of tools/expect_bench.py with common seeds: nominal and noise-aware training,
+each under its policy table and under the lookahead (zero set on the nominal V, the training set on the noise-aware V).
+The table is written to --out.
+usage: python tools/rollout_bench.py [--hybrid | --greedy | --stochastic | --expected] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
 """
 import argparse
 import json
@@ -297,7 +306,7 @@ def greedy_child(args):
 def greedy_usage(env, bins, define="PI_GREEDY", kernels="pi_greedy_kernels.hip"):
     """VGPRs and scratch bytes per lane of both greedy kernels for one grid: the translation unit pi_infer_set_greedy hands
     to hipRTC, built ahead of time with the same flags.  (`define`, `kernels`: the same for another module that sits
-    behind the rollout helpers — the stochastic one.)"""
+    behind the rollout helpers — the stochastic one; several defines as a tuple, `kernels` as a Path: a file elsewhere.)"""
     import tempfile
     import numpy as np
     from __graft_entry__ import HIPCC
@@ -314,13 +323,14 @@ def greedy_usage(env, bins, define="PI_GREEDY", kernels="pi_greedy_kernels.hip")
     def hexf(x):
         return float(np.float32(x)).hex() + "f"
     csrc = ROOT / "dynamicprogramming_amd" / "csrc"
-    text = (f"#define {define} 1\n#define PI_D {D}\n#define PI_LO_INIT {braces([t.min() for t in tabs], hexf)}\n"
+    defines = "".join(f"#define {d} 1\n" for d in ([define] if isinstance(define, str) else define))
+    text = (f"{defines}#define PI_D {D}\n#define PI_LO_INIT {braces([t.min() for t in tabs], hexf)}\n"
             f"#define PI_HI_INIT {braces([t.max() for t in tabs], hexf)}\n#define PI_SHAPE_INIT {braces(shape, str)}\n"
             f"#define PI_STRIDES_INIT {braces(strides, str)}\n"
             f"#define PI_BITS_INIT {braces(list(product([0, 1], repeat=D)), lambda r: braces(r, str))}\n"
             f"{(ROOT / 'include' / 'pi_math.h').read_text()}\n#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n"
             f"{envs.dynamics_source(env)}\n{(csrc / 'pi_rollout_kernels.hip').read_text()}\n"
-            f"{(csrc / kernels).read_text()}\n")
+            f"{(csrc / kernels).read_text() if isinstance(kernels, str) else Path(kernels).read_text()}\n")
     usage, fn = {}, None
     with tempfile.TemporaryDirectory(prefix="pi_greedy_") as tmp:
         src = Path(tmp) / "greedy.hip"
@@ -527,6 +537,233 @@ def stochastic_driver(args):
     print(out.read_text())
 
 
+def expected_child(args):
+    import numpy as np
+    import torch
+    from dynamicprogramming_amd import _native, envs
+    from dynamicprogramming_amd.noise import Disturbances
+    from utils import barycentric as B
+    env, bins = CONFIGS[args.config]
+    cls = envs.ENVS[env]
+    tabs = [np.asarray(b, np.float32) for b in cls.bins_space(bins).values()]
+    D = len(tabs)
+    shape = np.array([len(t) for t in tabs], np.int32)
+    lo, hi = np.array([t.min() for t in tabs], np.float32), np.array([t.max() for t in tabs], np.float32)
+    strides = np.array([int(np.prod(shape[d + 1:])) for d in range(D)], np.int32)
+    bits = np.array(list(product([0, 1], repeat=D)), dtype=np.int32)
+    acts = np.asarray(cls.ACTIONS, np.float32)
+    rng = np.random.default_rng(0)
+    n = int(np.prod(shape.astype(np.int64)))
+    policy = rng.integers(0, len(acts), size=n, dtype=np.int32)
+    V = (30.0 * rng.standard_normal(n, dtype=np.float32)).astype(np.float32)
+    m, steps, seed, lookahead = args.m, args.steps, 20261019, 0.99
+    epsilon, a_noise = 0.3, float(np.float32(0.1) * (acts.max() - acts.min()))
+    s_noise = (np.float32(0.002) * (hi - lo)).astype(np.float32)
+    one, two = np.zeros(D), np.zeros(D)
+    one[1] = two[0] = two[1] = 1.0
+    sets = {1: Disturbances.none(D), 9: Disturbances.uniform(D, state_noise=one * s_noise, action_noise=a_noise),
+            27: Disturbances.uniform(D, state_noise=two * s_noise, action_noise=a_noise)}
+    assert [d.K for d in sets.values()] == list(sets)
+    dev = torch.device("cuda:0")
+    starts = torch.from_numpy((lo + (hi - lo) * rng.random((m, D), dtype=np.float32)).astype(np.float32)).to(dev)
+    dp = B.DevicePolicy(policy, acts, lo, hi, shape, strides, bits, device=dev)
+    dp.set_dynamics(envs.dynamics_source(env))
+    dp.set_values(V)
+    dp.set_greedy()
+    dp.set_stochastic()
+    dp.set_expected_greedy()
+    eng = _native.Engine(D, shape, lo, hi, tabs, acts, device=0)
+    eng.compile(envs.dynamics_source(env))
+    st = torch.cuda.current_stream(dev).cuda_stream
+    noisy = dict(epsilon=epsilon, action_noise=a_noise, state_noise=s_noise, seed=seed)
+
+    def fused():
+        return dp.rollout(starts, steps, controller="expected", lookahead_gamma=lookahead, **noisy)
+
+    def greedy():
+        return dp.rollout(starts, steps, controller="greedy", lookahead_gamma=lookahead)
+
+    def single():
+        return dp.rollout(starts, steps, **noisy)
+    d_acts = torch.from_numpy(acts).to(dev)
+    eps24, n_act = B.explore_threshold(epsilon), len(acts)
+    amp = torch.tensor(a_noise, dtype=torch.float32, device=dev)
+    d_noise = torch.from_numpy(s_noise).to(dev)
+    a_lo, a_hi = d_acts.min(), d_acts.max()
+    blocks = (1, 2) if D > 4 else (1,)
+
+    def sym(x):                                           # int32 words holding uint32 bits -> [-1, 1), exact
+        return (((x >> 8) & 0xFFFFFF) - 8388608).to(torch.float32) * 2.0 ** -23
+
+    def loop():                                           # stochastic_child's loop with the lookahead as the controller
+        states = starts.clone()
+        nxt = torch.empty_like(states)
+        rew = torch.empty(m, dtype=torch.float32, device=dev)
+        done = torch.empty(m, dtype=torch.uint8, device=dev)
+        ret = torch.zeros(m, dtype=torch.float32, device=dev)
+        length = torch.zeros(m, dtype=torch.int32, device=dev)
+        ended = torch.zeros(m, dtype=torch.bool, device=dev)
+        w0 = torch.empty((m, 4), dtype=torch.int32, device=dev)
+        w = torch.empty((len(blocks), m, 4), dtype=torch.int32, device=dev)
+        for t in range(steps):
+            act = dp.expected_greedy(states, lookahead)[1]
+            dp._engine.random_words(seed, 0, m, t, 0, w0.data_ptr(), stream=st)
+            explore = ((w0[:, 0] >> 8) & 0xFFFFFF) < eps24
+            index = ((w0[:, 1].to(torch.int64) & 0xFFFFFFFF) * n_act) >> 32
+            act = torch.where(explore, d_acts[index], act)
+            push = amp * sym(w0[:, 2])
+            act = torch.fmin(torch.fmax(act + push, a_lo), a_hi).contiguous()
+            eng.probe_step(states.data_ptr(), act.data_ptr(), nxt.data_ptr(), rew.data_ptr(), done.data_ptr(), m, st)
+            for k, j in enumerate(blocks):
+                dp._engine.random_words(seed, 0, m, t, j, w[k].data_ptr(), stream=st)
+            words = torch.cat(list(w), dim=1)[:, :D]
+            push = d_noise * sym(words)
+            nxt2 = torch.where((done == 0)[:, None], nxt + push, nxt)
+            run = ~ended
+            ret = torch.where(run, ret + rew, ret)
+            states = torch.where(run[:, None], nxt2, states)
+            length = torch.where(run, torch.full_like(length, t + 1), length)
+            ended = ended | (run & (done != 0))
+        return B.RolloutResult(states, ret, length, ended, None)
+
+    def timed(fn):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record()
+        out = fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1), out
+
+    dp.set_disturbances(sets[9])
+    a, b = fused(), loop()                                # warm-up of all paths, and: same results
+    greedy(), single()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(a.states.view(torch.int32), b.states.view(torch.int32)) and torch.equal(a.lengths, b.lengths)
+                and torch.equal(a.returns.view(torch.int32), b.returns.view(torch.int32)))
+    t_fused, t_loop, t_greedy, t_single = {K: [] for K in sets}, [], [], []
+    taken = {}
+    for _ in range(args.repeat):
+        for K, d in sets.items():
+            dp.set_disturbances(d)
+            ms, out = timed(fused)
+            t_fused[K].append(ms)
+            taken[K] = int(out.lengths.sum().item())
+        dp.set_disturbances(sets[9])
+        t_loop.append(timed(loop)[0])
+        t_greedy.append(timed(greedy)[0])
+        t_single.append(timed(single)[0])
+    print(json.dumps({"config": args.config, "env": env, "bins": bins, "D": D, "actions": len(acts), "m": m, "steps": steps,
+                      "same_bits": same, "fused_ms": {K: min(v) for K, v in t_fused.items()}, "fused_ms_all": t_fused,
+                      "loop_ms": min(t_loop), "greedy_ms": min(t_greedy), "single_ms": min(t_single), "episode_steps": taken,
+                      "terminated_share": float(a.terminated.float().mean().item()),
+                      "launches_loop": (3 + len(blocks)) * steps}))
+    dp.close()
+    eng.close()
+
+
+def expected_loop_child(args):
+    """The closed loop under the noise planned for: nominal and noise-aware training of one setting of
+    tools/expect_bench.py, each under its policy table and under the lookahead, common seeds."""
+    import numpy as np
+    from dynamicprogramming_amd import envs
+    from dynamicprogramming_amd.noise import Disturbances
+    from dynamicprogramming_amd.solver import CudaPIConfig
+    sys.path.insert(0, str(ROOT / "tools"))
+    from expect_bench import LOOPS
+    env = args.env
+    bins, a_share, x_cells, caps = LOOPS[env]
+    cls = envs.ENVS[env]
+    tabs = [np.asarray(b, np.float64) for b in cls.bins_space(bins).values()]
+    cell = np.array([(t.max() - t.min()) / (len(t) - 1) for t in tabs])
+    acts = np.asarray(cls.ACTIONS, np.float64)
+    a_noise = a_share * float(acts.max() - acts.min())
+    x_noise = [float(c * w) for c, w in zip(x_cells, cell)]
+    planned = Disturbances.uniform(len(tabs), state_noise=x_noise, action_noise=a_noise)
+    starts = cls.start_states(np.random.default_rng(args.seed), args.m)
+    world = dict(action_noise=a_noise, state_noise=x_noise, seed=args.seed)
+    out = {"env": env, "bins": bins, "action_noise": a_noise, "state_noise": x_noise, "caps": caps, "steps": args.steps,
+           "m": args.m, "K": planned.K, "rows": []}
+    for label, d, look in (("nominal", None, Disturbances.none(len(tabs))), ("noise-aware", planned, planned)):
+        solver = envs.make(env, bins, CudaPIConfig(**{**cls.CONFIG, **caps}), device="cuda:0", transport=False)
+        if d is not None:
+            solver.set_disturbances(d)
+        solver.run()
+        for controller, kw in (("policy table", {}), ("lookahead", dict(controller="expected", disturbances=look))):
+            res = solver.rollout(starts, args.steps, gamma=1.0, **world, **kw)
+            out["rows"].append({"trained": label, "controller": controller + (f" K={look.K}" if kw else ""),
+                                "mean_return": float(np.mean(res.returns)), "terminated_share": float(np.mean(res.terminated)),
+                                "mean_length": float(np.mean(res.lengths))})
+    print(json.dumps(out))
+
+
+def expected_usage(env, bins):
+    """greedy_usage for the unit pi_infer_set_expect_greedy builds: the greedy and the stochastic file ahead of the kernels."""
+    import tempfile
+    csrc = ROOT / "dynamicprogramming_amd" / "csrc"
+    with tempfile.TemporaryDirectory(prefix="pi_expect_greedy_") as tmp:
+        unit = Path(tmp) / "unit.hip"
+        unit.write_text("\n".join(
+            (csrc / f).read_text() for f in ("pi_greedy_kernels.hip", "pi_stochastic_kernels.hip", "pi_expect_greedy_kernels.hip")))
+        return greedy_usage(env, bins, ("PI_EXPECT_GREEDY", "PI_GREEDY", "PI_STOCHASTIC"), unit)
+
+
+def expected_driver(args):
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    me = [sys.executable, str(Path(__file__).resolve())]
+    rows, loops, failed = [], [], None
+    sys.path.insert(0, str(ROOT / "tools"))
+    from expect_bench import LOOPS
+    jobs = [("timing", ["--config", c, "--steps", str(args.steps)]) for c in CONFIGS] + \
+           [("loop", ["--env", e, "--steps", str(args.loop_steps)]) for e in LOOPS]
+    for kind, extra in jobs:
+        res = subprocess.run(["timeout", "-k", "10", str(CHILD_SECONDS), *me, "--child", "--expected", "--part", kind, *extra,
+                              "--m", str(args.m), "--repeat", str(args.repeat)], capture_output=True, text=True)
+        if res.returncode != 0:                           # a fault, an abort or a time limit: nothing more runs
+            failed = f"NOT MEASURED: {kind} {' '.join(extra)} ended with status {res.returncode}: {res.stderr.strip()[-400:]}"
+            break
+        (rows if kind == "timing" else loops).append(json.loads(res.stdout.strip().splitlines()[-1]))
+        print((rows if kind == "timing" else loops)[-1], flush=True)
+    lines = [f"expected-value greedy rollouts (lookahead over a disturbance set) vs the step-by-step loop, MI355X, commit {args.commit}",
+             f"{args.m} episodes of {args.steps} steps, the env plugins' action tables, V ~ 30 N(0, 1) and a random policy (seeded), "
+             "lookahead gamma 0.99, epsilon 0.3, action noise a tenth of the action range, state noise 0.2 % of the span in every "
+             f"dimension, starts uniform in the grid; times in ms: the better of {args.repeat} after one warm-up, device events "
+             "around the whole call",
+             "K=1: the zero set; K=9: action x one velocity; K=27: action x two state dimensions (3 Gauss-Legendre nodes each); "
+             "loop: at K=9, per step one expected_greedy launch, the probe kernel's words, the plugin step and the mixing as torch "
+             "ops; greedy: the fused deterministic greedy rollout without noise; policy: the fused stochastic policy-table rollout "
+             "under the same noise; ep-steps: steps taken at K=9",
+             "",
+             f"{'config':30s} {'actions':>7s} {'K=1':>9s} {'K=9':>9s} {'K=27':>9s} {'loop':>10s} {'loop/K=9':>9s} {'greedy':>9s} "
+             f"{'policy':>9s} {'ep-steps':>10s} {'ended':>6s} {'same bits':>9s}"]
+    for r in rows:
+        f = {int(k): v for k, v in r["fused_ms"].items()}
+        lines.append(f"{r['config'] + ' ' + r['env'] + ' ' + str(r['bins']) + '^' + str(r['D']):30s} {r['actions']:7d} "
+                     f"{f[1]:9.3f} {f[9]:9.3f} {f[27]:9.3f} {r['loop_ms']:10.3f} {r['loop_ms'] / f[9]:9.1f} {r['greedy_ms']:9.3f} "
+                     f"{r['single_ms']:9.3f} {r['episode_steps']['9']:10d} {r['terminated_share']:6.3f} {str(r['same_bits']):>9s}")
+    lines += ["", "all fused timings per config (ms): " + "; ".join(
+        f"{r['config']} " + " ".join(f"K={k} {[round(t, 3) for t in v]}" for k, v in r["fused_ms_all"].items()) for r in rows)]
+    lines += ["", "registers and scratch (hipcc -Rpass-analysis=kernel-resource-usage, the translation unit of "
+                  "pi_infer_set_expect_greedy):"]
+    for config, (env, bins) in CONFIGS.items():
+        for fn, k in sorted(expected_usage(env, bins).items()):
+            lines.append(f"  {config} {env:24s} {fn:34s} VGPRs {k['vgpr']:4d}  scratch {k['scratch']} bytes/lane")
+    for r in loops:
+        lines += ["", f"closed loop under the noise planned for: {r['env']} {r['bins']} bins, action noise {r['action_noise']:.4g}, "
+                      f"state noise {[round(x, 5) for x in r['state_noise']]}, caps {r['caps']}, {r['m']} episodes of {r['steps']} "
+                      f"steps, common seeds; the planned set has K = {r['K']}",
+                  f"{'trained':12s} {'controller':18s} {'mean return':>12s} {'terminated':>10s} {'mean length':>11s}"]
+        for row in r["rows"]:
+            lines.append(f"{row['trained']:12s} {row['controller']:18s} {row['mean_return']:12.3f} {row['terminated_share']:10.4f} "
+                         f"{row['mean_length']:11.1f}")
+    if failed:
+        lines += ["", failed]
+    lines += ["", "no counters were taken: which unit binds is not stated"]
+    out.write_text("\n".join(lines) + "\n")
+    print(out.read_text())
+
+
 def hybrid_driver(args):
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
@@ -605,6 +842,11 @@ def main():
     ap.add_argument("--hybrid", action="store_true")
     ap.add_argument("--greedy", action="store_true")
     ap.add_argument("--stochastic", action="store_true")
+    ap.add_argument("--expected", action="store_true")
+    ap.add_argument("--part", choices=("timing", "loop"), default="timing")
+    ap.add_argument("--env", default="pendulum")
+    ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--loop-steps", type=int, default=1000)
     ap.add_argument("--config", choices=list(CONFIGS), default="c3")
     ap.add_argument("--m", type=int, default=4096)
     args = ap.parse_args()
@@ -612,6 +854,8 @@ def main():
         (greedy_child if args.child else greedy_driver)(args)
     elif args.stochastic:
         (stochastic_child if args.child else stochastic_driver)(args)
+    elif args.expected:
+        ((expected_child if args.part == "timing" else expected_loop_child) if args.child else expected_driver)(args)
     elif args.hybrid:
         (hybrid_child if args.child else hybrid_driver)(args)
     else:

@@ -31,6 +31,14 @@ cut; ``DevicePolicy.set_stochastic`` + ``DevicePolicy.rollout(epsilon=..., actio
 first_episode=...)`` / ``rollout(controller="random")`` / ``DevicePolicy.random_words`` are the device twins, one HIP
 kernel launch each (``pi_infer_rollout_stochastic``, ``pi_infer_random_words``), same bits.
 
+Expected-value greedy control (no reference counterpart): the greedy lookahead with the expectation of noise-aware
+solving inside it, ``argmax_a sum_k p_k [r_k + gamma * E[V](f(s, a (+) da_k) + dx_k)]`` over a
+``dynamicprogramming_amd.noise.Disturbances`` set, and closed loops under it that draw the stochastic rollouts' noise from
+the same counters: ``DevicePolicy.set_expected_greedy`` + ``set_disturbances`` + ``expected_greedy`` /
+``rollout(controller="expected")``, one HIP kernel launch each (``pi_infer_expect_greedy``,
+``pi_infer_rollout_expect_greedy``); the numpy twins live beside the set, ``noise.expected_greedy_action`` /
+``noise.expected_greedy_rollout``, same bits.
+
 Semantics kept from the reference helper (they differ slightly from the training kernels):
 the POINT is clamped to the bounds (not the cell coordinate), cell widths are float64
 ``(hi - lo) / (shape - 1)``, corners follow the rows of ``corner_bits`` (MSB-first
@@ -78,6 +86,8 @@ class DevicePolicy:
         self._action_space = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
         self._greedy_actions = None                # the table of the last set_greedy; None: no greedy module
         self._stochastic_actions = None            # the table of the last set_stochastic; None: no stochastic module
+        self._expected_actions = None              # the table of the last set_expected_greedy; None: no such module
+        self._disturbances = None                  # the set of the last set_disturbances
         if self._has_policy:
             self._engine.set_policy(policy, action_space)
             self._n_actions = len(np.asarray(action_space))
@@ -122,6 +132,7 @@ class DevicePolicy:
         self._dynamics_serial = getattr(self, "_dynamics_serial", 0) + 1      # HybridPolicy rebuilds its module after this
         self._greedy_actions = None                                           # the library dropped the greedy module
         self._stochastic_actions = None                                       # ... and the stochastic one
+        self._expected_actions = None                                         # ... and the expected-greedy one
         return log
 
     def _rollout_buffers(self, states, steps, record_every, need_policy=True):
@@ -168,10 +179,17 @@ class DevicePolicy:
         step that is not `done`.  The draws are a function of (``seed``, ``first_episode`` + the episode's row, step)
         alone: the same arguments give the same bits, and a batch cut into several calls with the matching
         ``first_episode`` gives the results of one.  ``controller="random"`` is ``epsilon = 1``, the random-policy
-        baseline; it needs no policy table.  With all five at their defaults this is the deterministic rollout."""
-        if controller not in ("policy", "greedy", "random"):
-            raise ValueError(f"controller must be 'policy', 'greedy' or 'random', not {controller!r}")
+        baseline; it needs no policy table.  With all five at their defaults this is the deterministic rollout.
+        ``controller="expected"`` (after ``set_expected_greedy`` and ``set_disturbances``; the device twin of
+        ``dynamicprogramming_amd.noise.expected_greedy_rollout``, same bits): per step the action ``expected_greedy``
+        returns for the state with the discount ``lookahead_gamma`` (required) — the lookahead with the expectation over
+        the disturbance set inside it.  It accepts the five stochastic keywords, drawn from the same counters as the
+        policy-table controller's (an exploring step takes its random action instead of the lookahead's), so the two can
+        be compared under common random numbers; with ``Disturbances.none(D)`` it is the greedy lookahead under noise."""
+        if controller not in ("policy", "greedy", "random", "expected"):
+            raise ValueError(f"controller must be 'policy', 'greedy', 'random' or 'expected', not {controller!r}")
         greedy = controller == "greedy"
+        expected = controller == "expected"
         if controller == "random":
             if float(epsilon) not in (0.0, 1.0):
                 raise ValueError("controller='random' is epsilon = 1: give no other epsilon with it")
@@ -184,19 +202,27 @@ class DevicePolicy:
         if greedy and stochastic:
             raise ValueError("controller='greedy' takes no epsilon, action_noise or state_noise: a stochastic greedy "
                              "controller does not exist")
-        if greedy and lookahead_gamma is None:
-            raise ValueError("controller='greedy' needs lookahead_gamma, the discount the value function was solved with")
+        if (greedy or expected) and lookahead_gamma is None:
+            raise ValueError(f"controller={controller!r} needs lookahead_gamma, the discount the value function was solved with")
+        if expected and getattr(self, "_expected_actions", None) is None:
+            raise RuntimeError("the expected controller needs set_expected_greedy() (again after every set_dynamics)")
+        if expected and getattr(self, "_disturbances", None) is None:
+            raise RuntimeError("the expected controller needs a disturbance set: call set_disturbances(...) first")
         if greedy and getattr(self, "_greedy_actions", None) is None:
             raise RuntimeError("the greedy controller needs set_greedy() (again after every set_dynamics)")
-        if stochastic and getattr(self, "_stochastic_actions", None) is None:
+        if stochastic and not expected and getattr(self, "_stochastic_actions", None) is None:
             raise RuntimeError("a stochastic rollout needs set_stochastic() (again after every set_dynamics)")
         on_device, d_start, m, steps, every, final, ret, length, term, traj = \
-            self._rollout_buffers(states, steps, record_every, need_policy=not greedy and float(epsilon) != 1.0)
+            self._rollout_buffers(states, steps, record_every, need_policy=not greedy and not expected and float(epsilon) != 1.0)
         outs = dict(d_final=final.data_ptr(), d_return=ret.data_ptr(), d_length=length.data_ptr(),
                     d_terminated=term.data_ptr(), d_traj=traj.data_ptr() if every else 0, traj_every=every,
                     stream=self._stream())
         if greedy:
             self._engine.rollout_greedy(d_start.data_ptr(), m, steps, lookahead_gamma, gamma, **outs)
+        elif expected:
+            self._engine.rollout_expect_greedy(d_start.data_ptr(), m, steps, lookahead_gamma, gamma, epsilon=epsilon,
+                                               action_noise=a_noise, state_noise=s_noise, seed=int(seed) & (2 ** 64 - 1),
+                                               first_episode=int(first_episode) & (2 ** 64 - 1), **outs)
         elif stochastic:
             self._engine.rollout_stochastic(d_start.data_ptr(), m, steps, gamma, epsilon=epsilon, action_noise=a_noise,
                                             state_noise=s_noise, seed=int(seed) & (2 ** 64 - 1),
@@ -246,6 +272,45 @@ class DevicePolicy:
         self._stochastic_actions = acts
         return log
 
+    def set_expected_greedy(self, action_space=None) -> str:
+        """Build the expected-value greedy controller — the one-step lookahead on the value function of ``set_values``
+        through the plugin of ``set_dynamics`` with the expectation over the set of ``set_disturbances`` inside it — over
+        ``action_space`` (default: the table the constructor was given; finite values: its extremes clamp ``a + da_k`` and
+        a noisy action); returns the compiler's log.  Needs no policy table.  ``set_dynamics`` drops it again;
+        ``set_values`` and ``set_disturbances`` only replace what it reads."""
+        acts = self._action_space if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        if acts is None:
+            raise ValueError("set_expected_greedy needs an action table: this DevicePolicy was built without one")
+        if not getattr(self, "_has_values", False):
+            raise RuntimeError("the expected controller needs the value function: call set_values(V) first")
+        if not getattr(self, "_has_dynamics", False):
+            raise RuntimeError("the expected controller needs the env's dynamics: call set_dynamics(dynamics_src) first")
+        log = self._engine.set_expect_greedy(acts)
+        self._expected_actions = acts
+        return log
+
+    def set_disturbances(self, disturbances) -> None:
+        """The ``dynamicprogramming_amd.noise.Disturbances`` set the expected controller takes its expectation over
+        (``Disturbances.none(D)``: the deterministic lookahead); ``None`` drops it.  Run-time data: an upload, never a
+        build, before or after ``set_expected_greedy``."""
+        if disturbances is None:
+            self._engine.set_disturbances(None, None, None)
+        else:
+            if disturbances.D != self.D:
+                raise ValueError(f"the disturbance set is {disturbances.D}-D, this policy's grid {self.D}-D")
+            self._engine.set_disturbances(disturbances.action_offsets, disturbances.state_offsets, disturbances.weights)
+        self._disturbances = disturbances
+
+    def expected_greedy(self, states, gamma, q_values=False):
+        """``greedy`` with the expectation over the disturbance set inside Q, in ONE kernel launch — the device twin of
+        ``dynamicprogramming_amd.noise.expected_greedy_action``, same bits; the same outputs and in/out conventions.
+        After ``set_expected_greedy`` and ``set_disturbances``."""
+        if getattr(self, "_expected_actions", None) is None:
+            raise RuntimeError("the expected controller needs set_expected_greedy() (again after every set_dynamics)")
+        if getattr(self, "_disturbances", None) is None:
+            raise RuntimeError("the expected controller needs a disturbance set: call set_disturbances(...) first")
+        return self._lookahead(self._engine.expect_greedy, self._expected_actions, states, gamma, q_values)
+
     def random_words(self, seed, first_episode, m, step, block):
         """The random stream the stochastic rollouts draw from, read on the device: the (m, 4) uint32 words of draw
         block ``block`` at step ``step`` of the episodes ``first_episode + 0 .. m`` under ``seed`` (numpy) — the device
@@ -264,9 +329,13 @@ class DevicePolicy:
         ``greedy_action``, same bits: ``(best_index (m,) int32, action (m,) float32, q_best (m,) float32)`` and, with
         ``q_values=True``, the matrix ``Q (m, n_actions)`` float32 behind them.  A numpy array in -> numpy out, a float32
         tensor on this device in -> torch tensors on the device out, like calling this object."""
-        torch = self._torch
         if getattr(self, "_greedy_actions", None) is None:
             raise RuntimeError("the greedy controller needs set_greedy() (again after every set_dynamics)")
+        return self._lookahead(self._engine.greedy, self._greedy_actions, states, gamma, q_values)
+
+    def _lookahead(self, launch, actions, states, gamma, q_values):
+        """A lookahead query (``greedy``, ``expected_greedy``): the checked points, the output tensors, one launch."""
+        torch = self._torch
         on_device = torch.is_tensor(states)
         if on_device:
             if states.device != self.device or states.dtype != torch.float32 or states.dim() != 2 \
@@ -280,9 +349,9 @@ class DevicePolicy:
         qb = torch.empty(m, dtype=torch.float32, device=self.device)
         out = [best, act, qb]
         if q_values:
-            out.append(torch.empty((m, len(self._greedy_actions)), dtype=torch.float32, device=self.device))
-        self._engine.greedy(d_pts.data_ptr(), m, gamma, d_best=best.data_ptr(), d_action=act.data_ptr(),
-                            d_q_best=qb.data_ptr(), d_q_all=out[3].data_ptr() if q_values else 0, stream=self._stream())
+            out.append(torch.empty((m, len(actions)), dtype=torch.float32, device=self.device))
+        launch(d_pts.data_ptr(), m, gamma, d_best=best.data_ptr(), d_action=act.data_ptr(), d_q_best=qb.data_ptr(),
+               d_q_all=out[3].data_ptr() if q_values else 0, stream=self._stream())
         return tuple(out) if on_device else tuple(x.cpu().numpy() for x in out)
 
     def resample(self, bins, strides, term, out_values, out_policy, action_map=None, n_actions=None):
@@ -744,16 +813,29 @@ def stochastic_rollout(step, states, steps, policy, action_space, bounds_low, bo
     d = 4, 5) — not clamped, not wrapped, and it is the state the next step starts from and the trajectory records.
     The bookkeeping, ``gamma`` and ``record_every`` are ``rollout``'s.  Returns a ``RolloutResult`` of numpy arrays."""
     acts = np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+    if policy is None and explore_threshold(epsilon) != 1 << 24:
+        raise ValueError("epsilon < 1 acts on the policy: a rollout without one needs epsilon = 1")
+    tables = (policy, acts, bounds_low, bounds_high, grid_shape, strides, corner_bits)
+
+    def controller(pts, wanted):
+        return np.zeros(len(pts), np.float32) if policy is None else _interpolated_actions(pts, *tables)
+    return _noisy_closed_loop(step, states, steps, controller, acts, epsilon, action_noise, state_noise, seed,
+                              first_episode, gamma, record_every)
+
+
+def _noisy_closed_loop(step, states, steps, controller, action_space, epsilon, action_noise, state_noise, seed,
+                       first_episode, gamma, record_every):
+    """The loop ``stochastic_rollout`` documents, for any controller: ``controller(states (k, D), wanted (k,) bool) ->
+    actions (k,) float32`` is asked for the running episodes; only the entries where ``wanted`` (the episode does not
+    explore this step) are used.  Returns a ``RolloutResult``."""
+    acts = np.ascontiguousarray(action_space, dtype=np.float32).ravel()
     if len(acts) < 1 or not np.isfinite(acts).all():
         raise ValueError("action_space needs at least one action, all finite")
     eps24 = explore_threshold(epsilon)
-    if policy is None and eps24 != 1 << 24:
-        raise ValueError("epsilon < 1 acts on the policy: a rollout without one needs epsilon = 1")
     a_noise = _checked_action_noise(action_noise)
     D = np.atleast_2d(states).shape[1]
     s_noise = _noise_vector(state_noise, D)
     a_min, a_max = acts.min(), acts.max()
-    tables = (policy, acts, bounds_low, bounds_high, grid_shape, strides, corner_bits)
     now = {"t": -1, "episodes": None}                 # _closed_loop asks act() once per step, then steps those episodes
 
     def act(live, pts):
@@ -761,10 +843,7 @@ def stochastic_rollout(step, states, steps, policy, action_space, bounds_low, bo
         now["episodes"] = _episode_numbers(first_episode, live)
         w = _episode_words(seed, now["episodes"], now["t"], 0)
         explore = (w[:, 0] >> np.uint32(8)) < eps24
-        if policy is None:
-            a = np.zeros(len(live), np.float32)
-        else:
-            a = _interpolated_actions(pts, *tables)
+        a = np.asarray(controller(pts, ~explore), np.float32)
         a = np.where(explore, acts[random_action_index(w[:, 1], len(acts))], a).astype(np.float32)
         if a_noise != 0:
             with np.errstate(invalid="ignore"):
