@@ -620,13 +620,25 @@ int pi_debug_report(pi_handle* h, uint32_t* out4) {
     if (!out4) return fail("null argument");
     if (!h->debug_bounds) return fail("this handle's kernels were built without the checks: set PI_MI355_DEBUG=1 before pi_create");
     pi::DeviceGuard guard(h->device);
-    hipDeviceptr_t words = nullptr;
-    size_t bytes = 0;
-    PI_HIP(hipModuleGetGlobal(&words, &bytes, h->module, "pi_debug_words"));
-    if (bytes != 4 * sizeof(uint32_t)) return fail("pi_debug_words has an unexpected size");
     PI_HIP(hipDeviceSynchronize());                       // every sweep launched so far has reported
-    PI_HIP(hipMemcpy(out4, words, bytes, hipMemcpyDeviceToHost));
-    PI_HIP(hipMemset(words, 0, bytes));
+    // Every code object built from the sweep unit has its own copy of pi_debug_words: the sweeps' module, the push
+    // module of an exchange plan and the expectation module, the last two loaded on demand.
+    const hipModule_t modules[3] = {h->module, h->module_push, h->module_expect};
+    uint32_t total[4] = {0u, 0u, 0u, 0u};
+    for (hipModule_t m : modules) {
+        if (!m) continue;
+        hipDeviceptr_t words = nullptr;
+        size_t bytes = 0;
+        uint32_t got[4];
+        PI_HIP(hipModuleGetGlobal(&words, &bytes, m, "pi_debug_words"));
+        if (bytes != sizeof(got)) return fail("pi_debug_words has an unexpected size");
+        PI_HIP(hipMemcpy(got, words, bytes, hipMemcpyDeviceToHost));
+        PI_HIP(hipMemset(words, 0, bytes));
+        if (got[0] != 0u && total[0] == 0u)               // the first module, in that order, that recorded one
+            for (int i = 1; i < 4; ++i) total[i] = got[i];
+        total[0] += got[0];
+    }
+    for (int i = 0; i < 4; ++i) out4[i] = total[i];
     return 0;
 }
 

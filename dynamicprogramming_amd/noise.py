@@ -153,8 +153,8 @@ def _range(n, s_begin, s_end, term):
 
 
 def _residual(new, old):
-    """max |new - old| as the kernels fold it: from 0, a NaN never raises it."""
-    with np.errstate(invalid="ignore"):
+    """max |new - old| as the kernels fold it: from 0, a NaN never raises it; a difference beyond float32 is inf."""
+    with np.errstate(invalid="ignore", over="ignore"):
         d = np.abs(new - old)
     return np.float32(np.fmax.reduce(d, initial=np.float32(0.0))) if len(d) else np.float32(0.0)
 

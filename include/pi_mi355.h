@@ -758,6 +758,10 @@ int64_t pi_info(pi_handle* h, int what);
  * out of bounds.  pi_debug_report synchronises the device, copies {violations, kind, where, value} of the
  * sweeps launched since the last report to out4 (host) and clears them; it fails on a handle built
  * without the checks.  Results of a run without violations are those of the unchecked kernels.
+ * Every code object of the handle that is built from the sweep unit keeps a tally of its own: the sweeps'
+ * module, the push module of an exchange plan and the expectation module of pi_set_disturbances, as far as
+ * they are loaded.  The report covers all of them: violations is their sum, and kind / where / value are
+ * those of the first module in that order that recorded a violation; all of them are cleared.
  */
 int pi_debug_report(pi_handle* h, uint32_t* out4);
 

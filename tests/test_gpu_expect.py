@@ -74,33 +74,50 @@ def _make_set(which, D, cell, acts):
                         np.full(4, 0.25, np.float32))
 
 
-@lru_cache(maxsize=None)
-def _case(grid):
-    name, shape = GRIDS[grid]
-    shape = _golden_shape(name) if shape is None else shape
-    bins = H.env_bins(name, shape)
+_CASES = {}
+
+
+def _case(grid, actions=None, chk=None, plugin=None, bins=None, gamma=None):
+    """The case `grid`: a key of GRIDS, or (env, shape).  `actions`: the handle's action table instead of the env's own.
+    `chk`, `plugin`, `bins`, `gamma`: a synthetic grid — the checker whose step is the twin's, the plugin source the engine
+    compiles, its bin tables and its discount; such a grid has no terminal states.  Built once per distinct argument set."""
+    key = (grid, None if actions is None else np.asarray(actions, np.float32).tobytes(), None if chk is None else id(chk),
+           plugin, None if bins is None else tuple(np.asarray(b, np.float32).tobytes() for b in bins), gamma)
+    if key in _CASES:
+        return _CASES[key]
+    name, shape = GRIDS[grid] if isinstance(grid, str) else grid
+    if bins is None:
+        shape = _golden_shape(name) if shape is None else shape
+        bins = H.env_bins(name, shape)
+    else:
+        bins = [np.asarray(b, np.float32) for b in bins]
+        shape = tuple(len(b) for b in bins)
     lo, hi, gshape, strides = oracle.grid_metadata(bins)
     states = oracle.states_from_bins(bins)
-    term, tval = H.terminal_mask(name, states)
+    if plugin is None:
+        term, tval = H.terminal_mask(name, states)
+    else:
+        term, tval = np.zeros(len(states), dtype=bool), 0.0
     rng = np.random.default_rng(3)
     V = (rng.standard_normal(len(states)) * 30.0).astype(np.float32)
     V[term] = np.float32(tval)
-    acts = H.edge_actions(name)
+    acts = H.edge_actions(name, actions)
     pol = rng.integers(0, len(acts), size=len(states)).astype(np.int32)
     pol[term] = 0
     cell = (hi.astype(np.float64) - lo.astype(np.float64)) / (np.asarray(gshape, np.float64) - 1)
     for a in (V, pol, term):
         a.setflags(write=False)
-    return dict(name=name, shape=shape, bins=bins, grid=(lo, hi, gshape, strides), states=states, term=term, V=V, pol=pol,
-                acts=acts, cell=cell, D=len(shape), n=len(states), chk=H.oracle_for(name),
-                gamma=float(np.float32(envs.ENVS[name].CONFIG["gamma"])))
+    c = dict(name=name, shape=shape, bins=bins, grid=(lo, hi, gshape, strides), states=states, term=term, V=V, pol=pol,
+             acts=acts, cell=cell, D=len(shape), n=len(states), chk=H.oracle_for(name) if chk is None else chk,
+             src=envs.dynamics_source(name) if plugin is None else plugin,
+             gamma=float(np.float32(envs.ENVS[name].CONFIG["gamma"] if gamma is None else gamma)))
+    _CASES[key] = c
+    return c
 
 
-@lru_cache(maxsize=None)
-def _twin(grid, which):
-    """Whole-grid twin results for (grid, set): the set, V' of one evaluation sweep, V' and policy of one value sweep."""
-    c = _case(grid)
-    d = _make_set(which, c["D"], c["cell"], c["acts"])
+def _twin_of(c, d):
+    """Whole-grid twin results of the case `c` under the set `d`: the set, V' of one evaluation sweep, V' and policy of one
+    value sweep."""
     args = (c["term"], d, c["acts"], *c["grid"], c["gamma"])
     V_eval, _ = noise.expected_eval(c["chk"].step, c["states"], c["pol"], c["V"], *args)
     V_val, pol_val, _, _ = noise.expected_value_sweep(c["chk"].step, c["states"], c["pol"], c["V"], *args)
@@ -109,17 +126,27 @@ def _twin(grid, which):
     return d, V_eval, V_val, pol_val
 
 
+@lru_cache(maxsize=None)
+def _twin(grid, which):
+    """Whole-grid twin results for (grid, set): the set, V' of one evaluation sweep, V' and policy of one value sweep."""
+    c = _case(grid)
+    return _twin_of(c, _make_set(which, c["D"], c["cell"], c["acts"]))
+
+
 def _residual(new, old):
-    with np.errstate(invalid="ignore"):
+    with np.errstate(invalid="ignore", over="ignore"):
         d = np.abs(new - old)
     return np.float32(np.fmax.reduce(d, initial=np.float32(0.0))) if len(d) else np.float32(0.0)
 
 
-def _engine(c, dev, order=None, cache_dir=_native.KERNEL_CACHE):
+def _engine(c, dev, order=None, cache_dir=_native.KERNEL_CACHE, options=()):
+    """`options`: (selector, value) pairs set before pi_compile."""
     bins = c["bins"]
     eng = _native.Engine(c["D"], [len(b) for b in bins], [b.min() for b in bins], [b.max() for b in bins], bins, c["acts"],
                          device=dev.index or 0, order=order)
-    eng.compile(envs.dynamics_source(c["name"]), cache_dir=cache_dir)
+    for what, value in options:
+        eng.set_option(what, value)
+    eng.compile(c["src"], cache_dir=cache_dir)
     return eng
 
 
