@@ -6,12 +6,12 @@
 //     <PI_EXPECT_GREEDY + PI_GREEDY + PI_STOCHASTIC + PI_D + the inference grid: PI_LO_INIT .. PI_BITS_INIT>
 //     <include/pi_math.h>  + #define sinf/cosf/fmodf -> pi_*        (deterministic math, as in the sweeps)
 //     <the user's step_dynamics C string>                           (env plugin)
-//     <csrc/pi_rollout_kernels.hip>                                 (PI_RG, pi_rollout_dynamics, pi_rollout_store_state)
+//     <csrc/pi_rollout_kernels.hip>                                 (PI_RG, pi_rollout_dynamics, pi_rollout_episodes)
 //     <csrc/pi_greedy_kernels.hip>                                  (pi_greedy_expect; its kernels stay out: PI_EXPECT_GREEDY)
-//     <csrc/pi_stochastic_kernels.hip>                              (pi_stochastic_words, pi_stochastic_sym, PiStateNoise; likewise)
+//     <csrc/pi_stochastic_kernels.hip>                              (pi_stochastic_draw, _noisy_action, _disturb; likewise)
 //     <this file>
-// and hipRTC compiles it with the sweeps' flags (-O3 -ffp-contract=off).  Nothing of the interpolation or of Philox is
-// restated here.
+// and hipRTC compiles it with the sweeps' flags (-O3 -ffp-contract=off).  The interpolation, Philox, the stochastic step
+// and the episode loop are those files'.
 //
 // Q_K(s, a) is the definition at pi_set_disturbances (include/pi_mi355.h, steps 1-5) evaluated at the point s instead of a
 // grid node, per disturbance point in ascending k:
@@ -35,16 +35,15 @@
 // loop, the point loop and, in the rollout, the step loop — 64 in 6-D on top of the figures below — and the V tables the
 // controllers read sit in L2; the register budget went to occupancy instead.
 //
-// pi_expect_greedy_rollout_kernel is pi_stochastic_rollout_kernel (pi_stochastic_kernels.hip) with the lookahead in place
-// of pi_rollout_action.  Per step of a running episode, in this order:
+// pi_expect_greedy_rollout_kernel runs on the shared episode loop (pi_rollout_episodes) and calls the stochastic step's
+// functions (pi_stochastic_kernels.hip) around the lookahead.  Per step of a running episode, in this order:
 //   1. best = argmax_a Q_K(s, a) with lookahead_gamma; a = actions[best]   (skipped by a lane that explores)
 //   2. the exploration coin and the random action index of the stochastic kernel's steps 1-2: block j = 0, drawn only
 //      when eps24 != 0 or action_noise != 0
 //   3. its step 3: action noise, then the clamp to the table's extremes
-//   4. step_dynamics(s, a) once more with the action finally taken; ret, disc, length and the freeze as in
-//      pi_rollout_kernel.  With the zero set and no noise these are pi_greedy_rollout_kernel's bits
+//   4. step_dynamics(s, a) once more with the action finally taken; ret, disc, length and the freeze are the loop's.
+//      With the zero set and no noise these are pi_greedy_rollout_kernel's bits
 //   5. its step 5: state noise from blocks 1 and 2, the same words per dimension, not on a `done` step.
-// Return, discount, length, freezing, trajectory rows, the loop exit by vote and the output layout are pi_rollout_kernel's.
 //
 // Resource usage from the code objects (hipcc --offload-arch=gfx950 -O3, kernel-resource-usage;
 // tests/test_expect_greedy_host.py asserts the scratch): no scratch in any D.  VGPRs of pi_expect_greedy_kernel /
@@ -57,7 +56,7 @@
 #error "pi_expect_greedy_kernels.hip is built behind #define PI_EXPECT_GREEDY 1 (pi_expect_greedy.cpp)"
 #endif
 
-#define PI_EG_BLOCK 256
+#define PI_EG_BLOCK 256                      // the query kernel's; the rollout kernel runs PI_RO_BLOCK threads
 #define PI_EG_ROW (PI_D + 2)                 // da | dx_0 .. dx_{D-1} | p
 
 struct PiExpectSet {
@@ -113,7 +112,7 @@ __device__ __forceinline__ int pi_expect_greedy_argmax(const float (&s)[PI_D], c
     float best_q = -1.0e30f;
     int best = 0;
     for (int a = 0; a < n_actions; ++a) {
-        const float q = pi_expect_greedy_q(s, actions[a], set, V, gamma);
+        const float q = pi_expect_greedy_q(s, pi_rollout_table_entry(actions, a), set, V, gamma);
         if (q_row != nullptr) q_row[a] = q;
         if (q > best_q) {
             best_q = q;
@@ -145,7 +144,7 @@ pi_expect_greedy_kernel(const float* __restrict__ points, long long m, const flo
     if (out_qbest != nullptr) out_qbest[k] = best_q;
 }
 
-extern "C" __global__ void __launch_bounds__(PI_EG_BLOCK)
+extern "C" __global__ void __launch_bounds__(PI_RO_BLOCK)
 pi_expect_greedy_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, float gamma,
                                 float lookahead_gamma, const float* __restrict__ V, const float* __restrict__ actions,
                                 int n_actions, float a_min, float a_max, const float* __restrict__ dist, int K,
@@ -153,94 +152,22 @@ pi_expect_greedy_rollout_kernel(const float* __restrict__ start, long long m, in
                                 unsigned long long seed, unsigned long long first_episode,
                                 float* __restrict__ out_final, float* __restrict__ out_return, int* __restrict__ out_length,
                                 unsigned char* __restrict__ out_terminated, float* __restrict__ traj, int traj_every) {
-    const long long k = (long long)blockIdx.x * PI_EG_BLOCK + threadIdx.x;
-    const bool exists = k < m;                       // lanes past the batch are frozen from the start and store nothing
-    const unsigned long long episode = first_episode + (unsigned long long)k;
-    float s[PI_D];
-#pragma unroll
-    for (int d = 0; d < PI_D; ++d) s[d] = exists ? start[k * PI_D + d] : 0.0f;
-    const bool record = traj != nullptr && traj_every > 0;
-    float* row = traj + k * PI_D;                    // this lane's slot of the next trajectory row (used when exists)
-    const long long row_floats = m * PI_D;
-    int rows_left = 0, until_row = 0;
-    if (record) {
-        rows_left = n_steps / traj_every;
-        until_row = traj_every;
-        if (exists) pi_rollout_store_state(row, s);
-        row += row_floats;
-    }
     const PiExpectSet set = {dist, K, a_min, a_max};
     const bool draw_action = eps24 != 0u || action_noise != 0.0f;
-    float ret = 0.0f, disc = 1.0f;
-    int length = 0;
-    bool terminated = false, running = exists;
-    for (int t = 0; t < n_steps && __any(running); ++t) {
-        if (running) {
-            float a;
-            bool explore = false;
-            PiWords w0 = {{0u, 0u, 0u, 0u}};
-            if (draw_action) {
-                w0 = pi_stochastic_words(seed, episode, (unsigned int)t, 0u);
-                explore = (w0.x[0] >> 8) < eps24;
-            }
-            if (explore) {
-                a = actions[__umulhi(w0.x[1], (unsigned int)n_actions)];
-            } else {
-                float best_q;
-                a = actions[pi_expect_greedy_argmax(s, set, V, actions, n_actions, lookahead_gamma, nullptr, &best_q)];
-            }
-            if (action_noise != 0.0f) {
-                const float push = action_noise * pi_stochastic_sym(w0.x[2]);
-                a = a + push;
-                a = fminf(fmaxf(a, a_min), a_max);
-            }
-            float n[PI_D], r;
-            bool done;
-            pi_rollout_dynamics(s, a, n, &r, &done);
-            const float gain = disc * r;
-            ret = ret + gain;
-            disc = disc * gamma;
-            if (any_state_noise && !done) {
-                const PiWords w1 = pi_stochastic_words(seed, episode, (unsigned int)t, 1u);
-#pragma unroll
-                for (int d = 0; d < (PI_D < 4 ? PI_D : 4); ++d)
-                    if (state_noise.v[d] != 0.0f) {
-                        const float push = state_noise.v[d] * pi_stochastic_sym(w1.x[d]);
-                        n[d] = n[d] + push;
-                    }
-#if PI_D == 6
-                if (state_noise.v[4] != 0.0f || state_noise.v[5] != 0.0f) {
-                    const PiWords w2 = pi_stochastic_words(seed, episode, (unsigned int)t, 2u);
-#pragma unroll
-                    for (int d = 4; d < 6; ++d)
-                        if (state_noise.v[d] != 0.0f) {
-                            const float push = state_noise.v[d] * pi_stochastic_sym(w2.x[d - 4]);
-                            n[d] = n[d] + push;
-                        }
-                }
-#endif
-            }
-#pragma unroll
-            for (int d = 0; d < PI_D; ++d) s[d] = n[d];
-            length = t + 1;
-            if (done) {
-                terminated = true;
-                running = false;
-            }
-        }
-        if (record && --until_row == 0) {
-            if (exists) pi_rollout_store_state(row, s);
-            row += row_floats;
-            until_row = traj_every;
-            --rows_left;
-        }
-    }
-    // the wave left the loop early: every episode of it is frozen, the remaining rows repeat the last state
-    if (record && exists)
-        for (; rows_left > 0; --rows_left, row += row_floats) pi_rollout_store_state(row, s);
-    if (!exists) return;
-    if (out_final != nullptr) pi_rollout_store_state(out_final + k * PI_D, s);
-    if (out_return != nullptr) out_return[k] = ret;
-    if (out_length != nullptr) out_length[k] = length;
-    if (out_terminated != nullptr) out_terminated[k] = terminated ? 1 : 0;
+    pi_rollout_episodes(start, m, n_steps, gamma, out_final, out_return, out_length, out_terminated, traj, traj_every,
+                        [&](const float (&s)[PI_D], int t, long long k, float (&n)[PI_D], float& r, bool& done) {
+                            const unsigned long long episode = first_episode + (unsigned long long)k;
+                            const PiActionDraw draw = pi_stochastic_draw(draw_action, seed, episode, t, eps24, n_actions);
+                            float a;
+                            if (draw.explore) {
+                                a = actions[draw.index];
+                            } else {
+                                float best_q;
+                                a = actions[pi_expect_greedy_argmax(s, set, V, actions, n_actions, lookahead_gamma, nullptr,
+                                                                    &best_q)];
+                            }
+                            a = pi_stochastic_noisy_action(a, action_noise, draw.noise_word, a_min, a_max);
+                            pi_rollout_dynamics(s, a, n, &r, &done);
+                            if (any_state_noise && !done) pi_stochastic_disturb(n, state_noise, seed, episode, t);
+                        });
 }

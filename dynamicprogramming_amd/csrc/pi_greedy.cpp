@@ -1,6 +1,6 @@
 // pi_greedy.cpp — value-greedy control on the inference handle (include/pi_mi355.h, "Inference" block): the one-step
 // lookahead a*(s) = argmax_a [ r(s, a) + gamma * E[V](s') ] on the handle's value function at arbitrary states.
-// pi_infer_set_greedy uploads the action table and builds the handle's fifth module — its grid, pi_math.h, the plugin
+// pi_infer_set_greedy uploads the action table and builds the handle's greedy module — its grid, pi_math.h, the plugin
 // pi_infer_set_dynamics was given, the helpers of csrc/pi_rollout_kernels.hip and csrc/pi_greedy_kernels.hip in one
 // translation unit; pi_infer_greedy answers a batch of query points and pi_infer_rollout_greedy runs whole episodes of a
 // batch of start states under that controller, one launch each.
@@ -8,7 +8,6 @@
 #include "pi_internal.h"
 
 #include <cmath>
-#include <sstream>
 
 #ifndef PI_CSRC_DIR
 #error "build with -DPI_CSRC_DIR=\"...\""
@@ -25,29 +24,16 @@ using pi::fail;
 
 namespace {
 
-constexpr int kBlock = 256;               // PI_GR_BLOCK
+constexpr int kBlock = 256;               // PI_GR_BLOCK, PI_RO_BLOCK
 
 // what both launching entry points refuse about the handle
 int check_module(const char* who, const pi_infer* h) {
-    if (!h->has_greedy)
+    if (!h->greedy.ready)
         return fail(std::string(who) + ": no greedy module: call pi_infer_set_greedy (again after every pi_infer_set_dynamics)");
     return 0;
 }
 
 }  // namespace
-
-int pi::drop_greedy(pi_infer* h) {
-    if (h->module_greedy) {                         // launches already enqueued have to finish first
-        pi::DeviceGuard guard(h->device);
-        PI_HIP(hipDeviceSynchronize());
-        PI_HIP(hipModuleUnload(h->module_greedy));
-    }
-    h->module_greedy = nullptr;
-    h->f_greedy = nullptr;
-    h->f_greedy_rollout = nullptr;
-    h->has_greedy = false;
-    return 0;
-}
 
 extern "C" {
 
@@ -55,37 +41,16 @@ int pi_infer_set_greedy(pi_infer* h, const float* action_space, int n_actions, c
     pi::fail("");
     if (log && log_len) log[0] = 0;
     if (!h) return fail("null handle");
-    if (!action_space) return fail("null argument (action_space)");
-    if (n_actions < 1) return fail("need at least one action");
+    pi::ActionTable table;
+    // any value goes: the lookahead never clamps to the table's extremes, and a NaN or infinite entry never wins the argmax
+    if (pi::check_action_table("pi_infer_set_greedy", false, action_space, n_actions, &table)) return 1;
     if (!h->has_values) return fail("pi_infer_set_greedy: pi_infer_set_values was never called");
-    if (!h->has_dynamics) return fail("pi_infer_set_greedy: pi_infer_set_dynamics was never called");
-    std::ostringstream src;
-    src << "#define PI_GREEDY 1\n";
-    src << h->grid_defines;
-    src << pi_embedded_math << "\n";
-    src << "#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n";
-    src << "// ---- env plugin (user string) ----\n";
-    src << h->dynamics_src << "\n";
-    src << "// ---- rollout helpers ----\n";
-    src << pi_embedded_rollout << "\n";
-    src << "// ---- greedy kernels ----\n";
-    src << pi_embedded_greedy << "\n";
+    if (!h->rollout.ready) return fail("pi_infer_set_greedy: pi_infer_set_dynamics was never called");
     std::vector<char> image;
-    if (pi::compile_image(src.str(), h->has_cache_dir ? h->cache_dir.c_str() : nullptr, log, log_len, image, nullptr)) return 1;
-    if (pi::drop_greedy(h)) return 1;
-    if (h->device >= 0) {
-        pi::DeviceGuard guard(h->device);
-        // drop_greedy has waited for the launches that read the previous table, if there was one
-        if (h->d_greedy_actions) { (void)hipFree(h->d_greedy_actions); h->d_greedy_actions = nullptr; }
-        PI_HIP(hipMalloc((void**)&h->d_greedy_actions, (size_t)n_actions * sizeof(float)));
-        PI_HIP(hipMemcpy(h->d_greedy_actions, action_space, (size_t)n_actions * sizeof(float), hipMemcpyHostToDevice));
-        PI_HIP(hipModuleLoadData(&h->module_greedy, image.data()));
-        PI_HIP(hipModuleGetFunction(&h->f_greedy, h->module_greedy, "pi_greedy_kernel"));
-        PI_HIP(hipModuleGetFunction(&h->f_greedy_rollout, h->module_greedy, "pi_greedy_rollout_kernel"));
-    }
-    h->n_greedy_actions = n_actions;
-    h->has_greedy = true;
-    return 0;
+    if (pi::build_infer_module(h, "#define PI_GREEDY 1\n" + h->grid_defines, h->dynamics_src,
+                               {{"rollout helpers", pi_embedded_rollout}, {"greedy kernels", pi_embedded_greedy}}, log, log_len, image))
+        return 1;
+    return pi::install(h, h->greedy, image, &table, "pi_greedy_rollout_kernel", "pi_greedy_kernel");
 }
 
 int pi_infer_greedy(pi_infer* h, const float* d_points, int64_t m, float gamma, int32_t* d_best, float* d_action,
@@ -97,15 +62,15 @@ int pi_infer_greedy(pi_infer* h, const float* d_points, int64_t m, float gamma, 
     if (m == 0) return 0;                           // nothing to do: an empty batch has no buffers either
     if (!d_best && !d_action && !d_q_best && !d_q_all) return fail("pi_infer_greedy: all four outputs are null");
     int64_t q_floats = 0;
-    if (__builtin_mul_overflow(m, (int64_t)h->n_greedy_actions, &q_floats) || q_floats > (INT64_MAX >> 2))
+    if (__builtin_mul_overflow(m, (int64_t)h->greedy.n_actions, &q_floats) || q_floats > (INT64_MAX >> 2))
         return fail("m * n_actions does not fit 63 bits");
     const int64_t blocks = (m + kBlock - 1) / kBlock;
     if (blocks > INT32_MAX) return fail("m is too large for one launch");
-    if (h->device < 0 || !h->f_greedy) return fail("host-only handle (device = -1) cannot launch kernels");
+    if (h->device < 0 || !h->greedy.f_query) return fail("host-only handle (device = -1) cannot launch kernels");
     if (!d_points) return fail("null device pointer (d_points)");
     pi::DeviceGuard guard(h->device);
-    PI_HIP(pi::launch(h->f_greedy, {(unsigned)blocks, 1}, kBlock, (hipStream_t)stream, d_points, (long long)m,
-                      (const float*)h->d_values, (const float*)h->d_greedy_actions, h->n_greedy_actions, gamma, d_best,
+    PI_HIP(pi::launch(h->greedy.f_query, {(unsigned)blocks, 1}, kBlock, (hipStream_t)stream, d_points, (long long)m,
+                      (const float*)h->d_values, (const float*)h->greedy.d_actions, h->greedy.n_actions, gamma, d_best,
                       d_action, d_q_best, d_q_all));
     return 0;
 }
@@ -117,13 +82,13 @@ int pi_infer_rollout_greedy(pi_infer* h, const float* d_start, int64_t m, int n_
     if (check_module("pi_infer_rollout_greedy", h)) return 1;
     if (std::isnan(gamma)) return fail("pi_infer_rollout_greedy: gamma is NaN");
     if (std::isnan(lookahead_gamma)) return fail("pi_infer_rollout_greedy: lookahead_gamma is NaN");
-    if (h->device < 0 || !h->f_greedy_rollout) return fail("host-only handle (device = -1) cannot launch kernels");
+    if (h->device < 0 || !h->greedy.f_rollout) return fail("host-only handle (device = -1) cannot launch kernels");
     int64_t blocks = 0;
     if (const int rc = pi::check_rollout_args(h->D, d_start, m, n_steps, d_final, d_traj, traj_every, &blocks)) return rc == 2 ? 0 : 1;
     pi::DeviceGuard guard(h->device);
-    PI_HIP(pi::launch(h->f_greedy_rollout, {(unsigned)blocks, 1}, kBlock, (hipStream_t)stream, d_start, (long long)m, n_steps,
-                      gamma, lookahead_gamma, (const float*)h->d_values, (const float*)h->d_greedy_actions,
-                      h->n_greedy_actions, d_final, d_return, d_length, d_terminated,
+    PI_HIP(pi::launch(h->greedy.f_rollout, {(unsigned)blocks, 1}, kBlock, (hipStream_t)stream, d_start, (long long)m, n_steps,
+                      gamma, lookahead_gamma, (const float*)h->d_values, (const float*)h->greedy.d_actions,
+                      h->greedy.n_actions, d_final, d_return, d_length, d_terminated,
                       traj_every > 0 ? d_traj : (float*)nullptr, traj_every));
     return 0;
 }

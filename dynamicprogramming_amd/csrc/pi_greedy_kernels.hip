@@ -5,7 +5,7 @@
 //     <PI_GREEDY + PI_D + the inference grid: PI_LO_INIT, PI_HI_INIT, PI_SHAPE_INIT, PI_STRIDES_INIT, PI_BITS_INIT>
 //     <include/pi_math.h>  + #define sinf/cosf/fmodf -> pi_*        (deterministic math, as in the sweeps)
 //     <the user's step_dynamics C string>                           (env plugin)
-//     <csrc/pi_rollout_kernels.hip>                                 (PI_RG, pi_rollout_dynamics, pi_rollout_store_state)
+//     <csrc/pi_rollout_kernels.hip>                                 (PI_RG, pi_rollout_dynamics, pi_rollout_episodes)
 //     <this file>
 // and hipRTC compiles it with the sweeps' flags (-O3 -ffp-contract=off).
 //
@@ -33,7 +33,7 @@
 #endif
 
 #define PI_GR_C (1 << PI_D)
-#define PI_GR_BLOCK 256
+#define PI_GR_BLOCK 256                      // the query kernel's; the rollout kernel runs PI_RO_BLOCK threads
 
 // bit of dimension d in corner c
 __device__ constexpr int pi_greedy_bit(int c, int d) {
@@ -120,79 +120,35 @@ pi_greedy_kernel(const float* __restrict__ points, long long m, const float* __r
     if (out_qbest != nullptr) out_qbest[k] = best_q;
 }
 
-// pi_rollout_kernel (pi_rollout_kernels.hip) with the action chosen by the lookahead: state, return, discount, length,
-// frozen episodes, trajectory rows, the loop exit by vote and the output layout are that kernel's.  The step an episode
-// takes is step_dynamics(s, actions[best]): the lookahead has computed it already — the same inlined function on the
-// same inputs — so the winner's successor, reward and flag are kept instead of stepping again (action 0's when nothing
+// The controller of a fused rollout on the shared episode loop (pi_rollout_episodes, pi_rollout_kernels.hip).  The step an
+// episode takes is step_dynamics(s, actions[best]): the lookahead has computed it already — the same inlined function on
+// the same inputs — so the winner's successor, reward and flag are kept instead of stepping again (action 0's when nothing
 // wins).  `gamma` discounts the return, `lookahead_gamma` is the discount inside Q.
-extern "C" __global__ void __launch_bounds__(PI_GR_BLOCK)
+extern "C" __global__ void __launch_bounds__(PI_RO_BLOCK)
 pi_greedy_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, float gamma, float lookahead_gamma,
                          const float* __restrict__ V, const float* __restrict__ actions, int n_actions,
                          float* __restrict__ out_final, float* __restrict__ out_return, int* __restrict__ out_length,
                          unsigned char* __restrict__ out_terminated, float* __restrict__ traj, int traj_every) {
-    const long long k = (long long)blockIdx.x * PI_GR_BLOCK + threadIdx.x;
-    const bool exists = k < m;                       // lanes past the batch are frozen from the start and store nothing
-    float s[PI_D];
+    pi_rollout_episodes(start, m, n_steps, gamma, out_final, out_return, out_length, out_terminated, traj, traj_every,
+                        [&](const float (&s)[PI_D], int, long long, float (&best_n)[PI_D], float& best_r, bool& best_done) {
+                            float best_q = -1.0e30f;
+                            best_r = 0.0f;
+                            best_done = false;
 #pragma unroll
-    for (int d = 0; d < PI_D; ++d) s[d] = exists ? start[k * PI_D + d] : 0.0f;
-    const bool record = traj != nullptr && traj_every > 0;
-    float* row = traj + k * PI_D;                    // this lane's slot of the next trajectory row (used when exists)
-    const long long row_floats = m * PI_D;
-    int rows_left = 0, until_row = 0;
-    if (record) {
-        rows_left = n_steps / traj_every;
-        until_row = traj_every;
-        if (exists) pi_rollout_store_state(row, s);
-        row += row_floats;
-    }
-    float ret = 0.0f, disc = 1.0f;
-    int length = 0;
-    bool terminated = false, running = exists;
-    for (int t = 0; t < n_steps && __any(running); ++t) {
-        if (running) {
-            float best_q = -1.0e30f, best_r = 0.0f;
-            float best_n[PI_D];
-            bool best_done = false;
+                            for (int d = 0; d < PI_D; ++d) best_n[d] = s[d];
+                            for (int a = 0; a < n_actions; ++a) {
+                                float n[PI_D], r;
+                                bool done;
+                                const float q = pi_greedy_q(s, pi_rollout_table_entry(actions, a), V, lookahead_gamma, n, &r, &done);
+                                const bool wins = q > best_q;
+                                if (wins) best_q = q;
+                                if (wins || a == 0) {
 #pragma unroll
-            for (int d = 0; d < PI_D; ++d) best_n[d] = s[d];
-            for (int a = 0; a < n_actions; ++a) {
-                float n[PI_D], r;
-                bool done;
-                const float q = pi_greedy_q(s, actions[a], V, lookahead_gamma, n, &r, &done);
-                const bool wins = q > best_q;
-                if (wins) best_q = q;
-                if (wins || a == 0) {
-#pragma unroll
-                    for (int d = 0; d < PI_D; ++d) best_n[d] = n[d];
-                    best_r = r;
-                    best_done = done;
-                }
-            }
-            const float gain = disc * best_r;
-            ret = ret + gain;
-            disc = disc * gamma;
-#pragma unroll
-            for (int d = 0; d < PI_D; ++d) s[d] = best_n[d];
-            length = t + 1;
-            if (best_done) {
-                terminated = true;
-                running = false;
-            }
-        }
-        if (record && --until_row == 0) {
-            if (exists) pi_rollout_store_state(row, s);
-            row += row_floats;
-            until_row = traj_every;
-            --rows_left;
-        }
-    }
-    // the wave left the loop early: every episode of it is frozen, the remaining rows repeat the last state
-    if (record && exists)
-        for (; rows_left > 0; --rows_left, row += row_floats) pi_rollout_store_state(row, s);
-    if (!exists) return;
-    if (out_final != nullptr) pi_rollout_store_state(out_final + k * PI_D, s);
-    if (out_return != nullptr) out_return[k] = ret;
-    if (out_length != nullptr) out_length[k] = length;
-    if (out_terminated != nullptr) out_terminated[k] = terminated ? 1 : 0;
+                                    for (int d = 0; d < PI_D; ++d) best_n[d] = n[d];
+                                    best_r = r;
+                                    best_done = done;
+                                }
+                            }
+                        });
 }
 #endif  // PI_EXPECT_GREEDY

@@ -1,5 +1,5 @@
 // pi_hybrid.cpp — closed-loop rollouts that switch between two inference handles (include/pi_mi355.h, "Inference"
-// block): pi_infer_set_partner builds the primary handle's third module — its grid, the partner's grid, pi_math.h,
+// block): pi_infer_set_partner builds the primary handle's hybrid module — its grid, the partner's grid, pi_math.h,
 // the plugin pi_infer_set_dynamics was given, csrc/pi_rollout_kernels.hip (the shared interpolation) and
 // csrc/pi_hybrid_kernels.hip in one translation unit — and pi_infer_rollout_hybrid runs whole episodes of a batch of
 // start states in one launch.
@@ -7,7 +7,6 @@
 #include "pi_internal.h"
 
 #include <cmath>
-#include <sstream>
 
 #ifndef PI_CSRC_DIR
 #error "build with -DPI_CSRC_DIR=\"...\""
@@ -56,19 +55,6 @@ int check_pair(const char* who, const pi_infer* h, const pi_infer* partner) {
 
 }  // namespace
 
-int pi::drop_hybrid(pi_infer* h) {
-    if (h->module_hybrid) {                         // launches already enqueued have to finish first
-        pi::DeviceGuard guard(h->device);
-        PI_HIP(hipDeviceSynchronize());
-        PI_HIP(hipModuleUnload(h->module_hybrid));
-    }
-    h->module_hybrid = nullptr;
-    h->f_hybrid = nullptr;
-    h->has_partner = false;
-    h->partner_defines.clear();
-    return 0;
-}
-
 extern "C" {
 
 int pi_infer_set_partner(pi_infer* h, pi_infer* partner, char* log, size_t log_len) {
@@ -76,29 +62,15 @@ int pi_infer_set_partner(pi_infer* h, pi_infer* partner, char* log, size_t log_l
     if (log && log_len) log[0] = 0;
     if (!h || !partner) return fail("null handle");
     if (check_pair("pi_infer_set_partner", h, partner)) return 1;
-    if (!h->has_dynamics) return fail("pi_infer_set_partner: pi_infer_set_dynamics was never called on the primary handle");
-    std::ostringstream src;
-    src << "#define PI_HYBRID 1\n";
-    src << h->grid_defines;
-    src << "// ---- secondary grid ----\n" << second_defines(partner->grid_defines);
-    src << pi_embedded_math << "\n";
-    src << "#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n";
-    src << "// ---- env plugin (user string) ----\n";
-    src << h->dynamics_src << "\n";
-    src << "// ---- rollout helpers ----\n";
-    src << pi_embedded_rollout << "\n";
-    src << "// ---- hybrid rollout kernel ----\n";
-    src << pi_embedded_hybrid << "\n";
+    if (!h->rollout.ready) return fail("pi_infer_set_partner: pi_infer_set_dynamics was never called on the primary handle");
     std::vector<char> image;
-    if (pi::compile_image(src.str(), h->has_cache_dir ? h->cache_dir.c_str() : nullptr, log, log_len, image, nullptr)) return 1;
-    if (pi::drop_hybrid(h)) return 1;
-    if (h->device >= 0) {
-        pi::DeviceGuard guard(h->device);
-        PI_HIP(hipModuleLoadData(&h->module_hybrid, image.data()));
-        PI_HIP(hipModuleGetFunction(&h->f_hybrid, h->module_hybrid, "pi_hybrid_rollout_kernel"));
-    }
+    if (pi::build_infer_module(h, "#define PI_HYBRID 1\n" + h->grid_defines + "// ---- secondary grid ----\n" +
+                                      second_defines(partner->grid_defines),
+                               h->dynamics_src, {{"rollout helpers", pi_embedded_rollout}, {"hybrid rollout kernel", pi_embedded_hybrid}},
+                               log, log_len, image))
+        return 1;
+    if (pi::install(h, h->hybrid, image, nullptr, "pi_hybrid_rollout_kernel", nullptr)) return 1;
     h->partner_defines = partner->grid_defines;
-    h->has_partner = true;
     return 0;
 }
 
@@ -111,8 +83,8 @@ int pi_infer_rollout_hybrid(pi_infer* h, pi_infer* partner, const float* d_start
     if (check_pair("pi_infer_rollout_hybrid", h, partner)) return 1;
     if (!h->d_policy) return fail("pi_infer_rollout_hybrid: pi_infer_set_policy was never called on the primary handle");
     if (!partner->d_policy) return fail("pi_infer_rollout_hybrid: pi_infer_set_policy was never called on the partner");
-    if (!h->has_dynamics) return fail("pi_infer_rollout_hybrid: pi_infer_set_dynamics was never called on the primary handle");
-    if (!h->has_partner || !h->f_hybrid)
+    if (!h->rollout.ready) return fail("pi_infer_rollout_hybrid: pi_infer_set_dynamics was never called on the primary handle");
+    if (!h->hybrid.ready || !h->hybrid.f_rollout)
         return fail("pi_infer_rollout_hybrid: no hybrid module: call pi_infer_set_partner (again after every pi_infer_set_dynamics)");
     if (partner->grid_defines != h->partner_defines)
         return fail("pi_infer_rollout_hybrid: the hybrid module was built for another partner grid: call pi_infer_set_partner "
@@ -131,7 +103,7 @@ int pi_infer_rollout_hybrid(pi_infer* h, pi_infer* partner, const float* d_start
     int64_t blocks = 0;
     if (const int rc = pi::check_rollout_args(h->D, d_start, m, n_steps, d_final, d_traj, traj_every, &blocks)) return rc == 2 ? 0 : 1;
     pi::DeviceGuard guard(h->device);
-    PI_HIP(pi::launch(h->f_hybrid, {(unsigned)blocks, 1}, 256, (hipStream_t)stream, d_start, (long long)m, n_steps, gamma,
+    PI_HIP(pi::launch(h->hybrid.f_rollout, {(unsigned)blocks, 1}, 256, (hipStream_t)stream, d_start, (long long)m, n_steps, gamma,
                       (const int32_t*)h->d_policy, (const float*)h->d_actions, (const int32_t*)partner->d_policy,
                       (const float*)partner->d_actions, box, d_final, d_return, d_length, d_terminated, d_secondary_steps,
                       d_last_mode, traj_every > 0 ? d_traj : (float*)nullptr, traj_every));

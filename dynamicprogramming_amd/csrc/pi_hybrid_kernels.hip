@@ -8,16 +8,17 @@
 //     <the secondary grid: PI2_D, PI2_LO_INIT, PI2_HI_INIT, PI2_SHAPE_INIT, PI2_STRIDES_INIT, PI2_BITS_INIT>
 //     <include/pi_math.h>  + #define sinf/cosf/fmodf -> pi_*
 //     <the primary handle's step_dynamics C string>
-//     <pi_rollout_kernels.hip>      its helpers: the interpolation, the dynamics call, the trajectory stores
+//     <pi_rollout_kernels.hip>      its helpers: the interpolation, the dynamics call, the episode loop
 //     <this file>
 // and hipRTC compiles it with the sweeps' flags.
 //
-// One lane per episode; state, mode, counters, return and discount stay in registers for all steps.  Per step
+// The episode loop is pi_rollout_episodes (pi_rollout_kernels.hip); this file adds the mode and its counter, which stay in
+// registers for all steps beside the loop's own state.  Per step of a running episode
 //   1. the mode (0 primary, 1 secondary): a box with hysteresis, float32, strict comparisons —
 //      mode 1 stays unless fabsf(s[d]) > leave[d] for some d; mode 0 becomes 1 iff fabsf(s[d]) < enter[d] for every d;
 //   2. the interpolated action of the mode's policy on ITS grid, the arithmetic of pi_rollout_action;
 //   3. secondary_steps += mode;
-//   4. step_dynamics and the bookkeeping of pi_rollout_kernel.
+//   4. step_dynamics; return, length and the freeze are the loop's.
 // Lanes of one wave are in different modes, and a branch on the mode would run the 2^D-corner interpolation twice for
 // a mixed wave.  The interpolation is the same expression on both grids, so a lane SELECTS its operands — bounds,
 // shape, strides, the float64 cell widths (compile-time constants of either grid), the policy and action tables —
@@ -64,67 +65,25 @@ pi_hybrid_rollout_kernel(const float* __restrict__ start, long long m, int n_ste
                          float* __restrict__ out_final, float* __restrict__ out_return, int* __restrict__ out_length,
                          unsigned char* __restrict__ out_terminated, int* __restrict__ out_secondary,
                          unsigned char* __restrict__ out_last_mode, float* __restrict__ traj, int traj_every) {
-    const long long k = (long long)blockIdx.x * PI_RO_BLOCK + threadIdx.x;
-    const bool exists = k < m;                       // lanes past the batch are frozen from the start and store nothing
-    float s[PI_D];
-#pragma unroll
-    for (int d = 0; d < PI_D; ++d) s[d] = exists ? start[k * PI_D + d] : 0.0f;
-    const bool record = traj != nullptr && traj_every > 0;
-    float* row = traj + k * PI_D;                    // this lane's slot of the next trajectory row (used when exists)
-    const long long row_floats = m * PI_D;
-    int rows_left = 0, until_row = 0;
-    if (record) {
-        rows_left = n_steps / traj_every;
-        until_row = traj_every;
-        if (exists) pi_rollout_store_state(row, s);
-        row += row_floats;
-    }
-    float ret = 0.0f, disc = 1.0f;
-    int length = 0, secondary = 0;
+    int secondary = 0;
     bool second = false;                             // the mode; it changes on steps taken only, so it ends as last_mode
-    bool terminated = false, running = exists;
-    for (int t = 0; t < n_steps && __any(running); ++t) {
-        if (running) {
-            bool inside = true, outside = false;
+    pi_rollout_episodes(start, m, n_steps, gamma, out_final, out_return, out_length, out_terminated, traj, traj_every,
+                        [&](const float (&s)[PI_D], int, long long, float (&n)[PI_D], float& r, bool& done) {
+                            bool inside = true, outside = false;
 #pragma unroll
-            for (int d = 0; d < PI_D; ++d) {
-                const float mag = fabsf(s[d]);
-                inside = inside && mag < box.enter[d];
-                outside = outside || mag > box.leave[d];
-            }
-            second = second ? !outside : inside;
-            const float a = pi_rollout_action(PiGridPick{second}, s, second ? policy1 : policy0,
-                                              second ? actions1 : actions0);
-            secondary += second ? 1 : 0;
-            float n[PI_D], r;
-            bool done;
-            pi_rollout_dynamics(s, a, n, &r, &done);
-            const float gain = disc * r;
-            ret = ret + gain;
-            disc = disc * gamma;
-#pragma unroll
-            for (int d = 0; d < PI_D; ++d) s[d] = n[d];
-            length = t + 1;
-            if (done) {
-                terminated = true;
-                running = false;
-            }
-        }
-        if (record && --until_row == 0) {
-            if (exists) pi_rollout_store_state(row, s);
-            row += row_floats;
-            until_row = traj_every;
-            --rows_left;
-        }
-    }
-    // the wave left the loop early: every episode of it is frozen, the remaining rows repeat the last state
-    if (record && exists)
-        for (; rows_left > 0; --rows_left, row += row_floats) pi_rollout_store_state(row, s);
-    if (!exists) return;
-    if (out_final != nullptr) pi_rollout_store_state(out_final + k * PI_D, s);
-    if (out_return != nullptr) out_return[k] = ret;
-    if (out_length != nullptr) out_length[k] = length;
-    if (out_terminated != nullptr) out_terminated[k] = terminated ? 1 : 0;
+                            for (int d = 0; d < PI_D; ++d) {
+                                const float mag = fabsf(s[d]);
+                                inside = inside && mag < box.enter[d];
+                                outside = outside || mag > box.leave[d];
+                            }
+                            second = second ? !outside : inside;
+                            const float a = pi_rollout_action(PiGridPick{second}, s, second ? policy1 : policy0,
+                                                              second ? actions1 : actions0);
+                            secondary += second ? 1 : 0;
+                            pi_rollout_dynamics(s, a, n, &r, &done);
+                        });
+    const long long k = pi_rollout_lane();
+    if (k >= m) return;
     if (out_secondary != nullptr) out_secondary[k] = secondary;
     if (out_last_mode != nullptr) out_last_mode[k] = second ? 1 : 0;
 }

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <vector>
@@ -255,6 +256,19 @@ struct pi_handle {
     pi::P2pPending* p2p_pending = nullptr;   // pi_p2p_describe without its pi_comm_init_p2p yet (owned; pi_p2p.cpp)
 };
 
+namespace pi {
+// One rollout module of an inference handle: a code object built on demand by a pi_infer_set_* call, and the action table
+// that call brought, where it brings one.
+struct InferModule {
+    hipModule_t module = nullptr;
+    hipFunction_t f_rollout = nullptr, f_query = nullptr;   // its rollout kernel; its batched-query kernel, if it has one
+    bool ready = false;                  // the pi_infer_set_* call went through (host-only handles: the unit compiled)
+    float* d_actions = nullptr;          // the action table of that call (owned: a handle without a policy has no other)
+    int n_actions = 0;
+    float a_min = 0.0f, a_max = 0.0f;    // the table's extremes
+};
+}  // namespace pi
+
 // One inference handle (pi_infer.cpp; the rollout entry points on it: pi_rollout.cpp).
 struct pi_infer {
     int device = -1;
@@ -265,23 +279,26 @@ struct pi_infer {
     hipFunction_t f = nullptr;
     float* d_actions = nullptr;
     int32_t* d_policy = nullptr;
-    // what pi_infer_create was given, for the second module (pi_infer_set_dynamics): the grid as the generated
+    // what pi_infer_create was given, for the modules built later: the grid as the generated
     // defines of the translation unit (PI_D, PI_LO_INIT, ... PI_BITS_INIT) and the code-object cache
     std::string grid_defines, cache_dir;
     bool has_cache_dir = false;
-    // second module: grid + pi_math.h + the env plugin + csrc/pi_rollout_kernels.hip
-    hipModule_t module_rollout = nullptr;
-    hipFunction_t f_rollout = nullptr;
-    bool has_dynamics = false;           // pi_infer_set_dynamics went through (host-only handles: it compiled)
-    std::string dynamics_src;            // the plugin of that call, for the third module
+    std::string dynamics_src;            // the plugin of the last pi_infer_set_dynamics, for the modules built after it
     std::vector<int32_t> corner_bits;    // what pi_infer_create was given: both handles of a hybrid rollout share it
-    // third module (pi_infer_set_partner, pi_hybrid.cpp): this grid + a partner's grid + pi_math.h + the env plugin +
-    // csrc/pi_rollout_kernels.hip + csrc/pi_hybrid_kernels.hip; partner_defines: the partner grid it was built for
-    hipModule_t module_hybrid = nullptr;
-    hipFunction_t f_hybrid = nullptr;
-    bool has_partner = false;            // pi_infer_set_partner went through (host-only handles: it compiled)
+    // The rollout modules (pi::InferModule, above; pi::build_infer_module assembles their translation units).  Every one
+    // is this grid + pi_math.h + the env plugin + csrc/pi_rollout_kernels.hip, and then
+    //   rollout        (pi_infer_set_dynamics, pi_rollout.cpp)             nothing more: pi_rollout_kernel
+    //   hybrid         (pi_infer_set_partner, pi_hybrid.cpp)               a partner's grid + csrc/pi_hybrid_kernels.hip;
+    //                  partner_defines: the partner grid it was built for
+    //   greedy         (pi_infer_set_greedy, pi_greedy.cpp)                csrc/pi_greedy_kernels.hip; its launches read d_values
+    //   stochastic     (pi_infer_set_stochastic, pi_stochastic.cpp)        csrc/pi_stochastic_kernels.hip; f_query is
+    //                  pi_random_words_kernel; the table is what exploring steps draw from, its extremes clamp a noisy action
+    //   expect_greedy  (pi_infer_set_expect_greedy, pi_expect_greedy.cpp)  the functions of the greedy and the stochastic
+    //                  file + csrc/pi_expect_greedy_kernels.hip; the extremes clamp a + da_k and a noisy action
+    // A new plugin unloads the four that were built on the one before it.
+    pi::InferModule rollout, hybrid, greedy, stochastic, expect_greedy;
     std::string partner_defines;
-    // fourth module (pi_infer_set_values, pi_resample.cpp): this grid + csrc/pi_resample_kernels.hip, and the value
+    // the resample module (pi_infer_set_values, pi_resample.cpp): this grid + csrc/pi_resample_kernels.hip, and the value
     // function of the solution.  d_resample_tab: the destination's bin tables | action map of the last pi_infer_resample
     // (owned; resample_tab: the same words on the host — a call that brings the same destination uploads nothing)
     hipModule_t module_resample = nullptr;
@@ -291,33 +308,6 @@ struct pi_infer {
     uint32_t* d_resample_tab = nullptr;
     size_t resample_tab_capacity = 0;    // words allocated at d_resample_tab
     std::vector<uint32_t> resample_tab;
-    // fifth module (pi_infer_set_greedy, pi_greedy.cpp): this grid + pi_math.h + the env plugin + the helpers of
-    // csrc/pi_rollout_kernels.hip + csrc/pi_greedy_kernels.hip.  d_greedy_actions: the action table of that call
-    // (owned: a handle without a policy has no d_actions); the value function its launches read is d_values
-    hipModule_t module_greedy = nullptr;
-    hipFunction_t f_greedy = nullptr, f_greedy_rollout = nullptr;
-    bool has_greedy = false;             // pi_infer_set_greedy went through (host-only handles: it compiled)
-    float* d_greedy_actions = nullptr;
-    int n_greedy_actions = 0;
-    // sixth module (pi_infer_set_stochastic, pi_stochastic.cpp): this grid + pi_math.h + the env plugin + the helpers of
-    // csrc/pi_rollout_kernels.hip + csrc/pi_stochastic_kernels.hip.  d_stochastic_actions: the action table of that call
-    // (owned), the table exploring steps draw from; stochastic_a_min / _a_max: its extremes, the clamp of a noisy action
-    hipModule_t module_stochastic = nullptr;
-    hipFunction_t f_stochastic_rollout = nullptr, f_random_words = nullptr;
-    bool has_stochastic = false;         // pi_infer_set_stochastic went through (host-only handles: it compiled)
-    float* d_stochastic_actions = nullptr;
-    int n_stochastic_actions = 0;
-    float stochastic_a_min = 0.0f, stochastic_a_max = 0.0f;
-    // seventh module (pi_infer_set_expect_greedy, pi_expect_greedy.cpp): this grid + pi_math.h + the env plugin + the
-    // helpers of csrc/pi_rollout_kernels.hip + the functions of csrc/pi_greedy_kernels.hip and
-    // csrc/pi_stochastic_kernels.hip + csrc/pi_expect_greedy_kernels.hip.  d_expect_greedy_actions: the action table of
-    // that call (owned), expect_greedy_a_min / _a_max its extremes: the clamp of a + da_k and of a noisy action
-    hipModule_t module_expect_greedy = nullptr;
-    hipFunction_t f_expect_greedy = nullptr, f_expect_greedy_rollout = nullptr;
-    bool has_expect_greedy = false;      // pi_infer_set_expect_greedy went through (host-only handles: it compiled)
-    float* d_expect_greedy_actions = nullptr;
-    int n_expect_greedy_actions = 0;
-    float expect_greedy_a_min = 0.0f, expect_greedy_a_max = 0.0f;
     // the disturbance set of that controller (pi_infer_set_disturbances): K rows of {da, dx_0 .. dx_{D-1}, p} at d_dist,
     // a buffer of 64 rows allocated by the first call; dist_k == 0: no set.  Independent of the module
     float* d_dist = nullptr;
@@ -381,10 +371,38 @@ int compile_image(const std::string& src, const char* cache_dir, char* log, size
 // 63-bit size, d_start, alignment).  0: launch `*blocks` workgroups; 1: refused (pi::fail was called); 2: m == 0, nothing to do
 int check_rollout_args(int D, const float* d_start, int64_t m, int n_steps, const float* d_final, const float* d_traj,
                        int traj_every, int64_t* blocks);
-int drop_hybrid(pi_infer* h);           // pi_hybrid.cpp: unloads the third module (after a device synchronisation)
-int drop_greedy(pi_infer* h);           // pi_greedy.cpp: unloads the fifth module (after a device synchronisation)
-int drop_stochastic(pi_infer* h);       // pi_stochastic.cpp: unloads the sixth module (after a device synchronisation)
-int drop_expect_greedy(pi_infer* h);    // pi_expect_greedy.cpp: unloads the seventh module (after a device synchronisation)
+// pi_rollout.cpp: what the five rollout modules share.  build_infer_module assembles a translation unit — `leading` (the
+// module's defines and the grid(s)), pi_math.h, the sinf / cosf / fmodf defines, `plugin`, then every part behind its
+// "// ---- <section> ----" line — and compiles it with the handle's code-object cache.
+struct UnitPart {
+    const char *section, *text;
+};
+int build_infer_module(const pi_infer* h, const std::string& leading, const std::string& plugin,
+                       std::initializer_list<UnitPart> parts, char* log, size_t log_len, std::vector<char>& image);
+// the rules of an action table: not null, at least one entry and, where `finite`, every entry finite (`who` names the caller
+// in that message); fills values, n and the extremes
+struct ActionTable {
+    const float* values = nullptr;
+    int n = 0;
+    float a_min = 0.0f, a_max = 0.0f;
+};
+int check_action_table(const char* who, bool finite, const float* action_space, int n_actions, ActionTable* table);
+int unload(pi_infer* h, InferModule& mod);      // waits for the device, unloads the module, clears `ready`
+// replaces `mod` by `image`: unload, then (on a device) the upload of `table` if there is one, the load and the two kernels
+// by name (`query` may be null); sets `ready`
+int install(pi_infer* h, InferModule& mod, const std::vector<char>& image, const ActionTable* table, const char* rollout,
+            const char* query);
+// pi_stochastic.cpp: the rules of epsilon, action_noise, state_noise and gamma that both stochastic rollouts share
+struct StateNoise {                     // PiStateNoise of pi_stochastic_kernels.hip
+    float v[6];
+};
+struct StochasticArgs {
+    StateNoise noise = {};
+    int any_noise = 0;
+    unsigned int eps24 = 0;
+};
+int check_stochastic_args(const char* who, int D, float epsilon, float action_noise, const float* state_noise, float gamma,
+                          StochasticArgs* out);
 // pi_expect.cpp: the rules of a disturbance set, shared by pi_set_disturbances and pi_infer_set_disturbances (`who`).
 // 0: `table` holds K rows of {da, dx_0 .. dx_{D-1}, p}, null offsets as zeros (K == 0: empty); 1: refused (pi::fail was called)
 constexpr int kMaxDisturbances = 64;    // PI_NOISE_MAX

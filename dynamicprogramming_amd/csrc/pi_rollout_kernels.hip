@@ -9,7 +9,8 @@
 // and hipRTC compiles it with the sweeps' flags (-O3 -ffp-contract=off).  The grid is the caller's (archive)
 // description, dimensions in the order of step_dynamics' arguments: no memory-order permutation here.
 //
-// One lane per episode; the state stays in registers for all steps.  Per step
+// One lane per episode; the state stays in registers for all steps.  The episode loop (pi_rollout_episodes, below) is
+// shared by every fused rollout of the handle: a controller supplies step 1 and 2, the loop does the rest.  Per step
 //   1. the interpolated action, the arithmetic of pi_infer_kernel (pi_infer_kernels.hip) restated type for type:
 //      point clamped to the bounds, float64 cell widths, float64 weight products rounded once to float32, corners
 //      in the order of the caller's corner_bits, the action a float32 sum over ASCENDING corners, multiply then
@@ -29,7 +30,7 @@
 // per lane keep 8-byte alignment only).
 
 #define PI_RO_C (1 << PI_D)
-#define PI_RO_BLOCK 256
+#define PI_RO_BLOCK 256                              // threads per workgroup of every fused rollout kernel
 
 struct PiRolloutGrid {
     float lo[PI_D], hi[PI_D];
@@ -120,15 +121,27 @@ __device__ __forceinline__ void pi_rollout_store_state(float* __restrict__ row, 
 #endif
 }
 
-// the hybrid module holds pi_hybrid_rollout_kernel instead, the greedy module (pi_greedy_kernels.hip) and the stochastic
-// module (pi_stochastic_kernels.hip) their own two each
-#if !defined(PI_HYBRID) && !defined(PI_GREEDY) && !defined(PI_STOCHASTIC)
-extern "C" __global__ void __launch_bounds__(PI_RO_BLOCK)
-pi_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, float gamma,
-                  const int* __restrict__ policy, const float* __restrict__ actions,
-                  float* __restrict__ out_final, float* __restrict__ out_return, int* __restrict__ out_length,
-                  unsigned char* __restrict__ out_terminated, float* __restrict__ traj, int traj_every) {
-    const long long k = (long long)blockIdx.x * PI_RO_BLOCK + threadIdx.x;
+// An entry of a table the launch only reads, at a wave-uniform address.  Read through the constant address space the load
+// stays on the scalar unit whether or not the compiler can prove that the trajectory stores of the loop below leave the
+// table alone: the lookahead controllers wait on this load once per action, and as a vector load it cost the greedy
+// rollout up to a fifth of its time on small batches.
+__device__ __forceinline__ float pi_rollout_table_entry(const float* __restrict__ table, int i) {
+    return *(const __attribute__((address_space(4))) float*)(table + i);
+}
+
+// The episode loop of every fused rollout (this file's kernel and those of pi_hybrid_kernels.hip, pi_greedy_kernels.hip,
+// pi_stochastic_kernels.hip and pi_expect_greedy_kernels.hip): lane k of the launch is episode k of the batch.
+__device__ __forceinline__ long long pi_rollout_lane() { return (long long)blockIdx.x * PI_RO_BLOCK + threadIdx.x; }
+
+// Everything of a rollout but the controller: the start-state load, the trajectory rows, the loop exit by vote, return,
+// discount, length, the freeze on `done` and the four nullable outputs.  step(s, t, k, n, r, done) is called for a running
+// episode k at step t in the state s and fills the successor n, the reward r and the flag done.
+template <typename Step>
+__device__ __forceinline__ void pi_rollout_episodes(const float* __restrict__ start, long long m, int n_steps, float gamma,
+                                                    float* __restrict__ out_final, float* __restrict__ out_return,
+                                                    int* __restrict__ out_length, unsigned char* __restrict__ out_terminated,
+                                                    float* __restrict__ traj, int traj_every, Step&& step) {
+    const long long k = pi_rollout_lane();
     const bool exists = k < m;                       // lanes past the batch are frozen from the start and store nothing
     float s[PI_D];
 #pragma unroll
@@ -148,10 +161,9 @@ pi_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, flo
     bool terminated = false, running = exists;
     for (int t = 0; t < n_steps && __any(running); ++t) {
         if (running) {
-            const float a = pi_rollout_action(PiGridFixed(), s, policy, actions);
             float n[PI_D], r;
             bool done;
-            pi_rollout_dynamics(s, a, n, &r, &done);
+            step(s, t, k, n, r, done);
             const float gain = disc * r;
             ret = ret + gain;
             disc = disc * gamma;
@@ -178,5 +190,20 @@ pi_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, flo
     if (out_return != nullptr) out_return[k] = ret;
     if (out_length != nullptr) out_length[k] = length;
     if (out_terminated != nullptr) out_terminated[k] = terminated ? 1 : 0;
+}
+
+// the hybrid module holds pi_hybrid_rollout_kernel instead, the greedy module (pi_greedy_kernels.hip) and the stochastic
+// module (pi_stochastic_kernels.hip) their own two each
+#if !defined(PI_HYBRID) && !defined(PI_GREEDY) && !defined(PI_STOCHASTIC)
+extern "C" __global__ void __launch_bounds__(PI_RO_BLOCK)
+pi_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, float gamma,
+                  const int* __restrict__ policy, const float* __restrict__ actions,
+                  float* __restrict__ out_final, float* __restrict__ out_return, int* __restrict__ out_length,
+                  unsigned char* __restrict__ out_terminated, float* __restrict__ traj, int traj_every) {
+    pi_rollout_episodes(start, m, n_steps, gamma, out_final, out_return, out_length, out_terminated, traj, traj_every,
+                        [&](const float (&s)[PI_D], int, long long, float (&n)[PI_D], float& r, bool& done) {
+                            const float a = pi_rollout_action(PiGridFixed(), s, policy, actions);
+                            pi_rollout_dynamics(s, a, n, &r, &done);
+                        });
 }
 #endif  // PI_HYBRID, PI_GREEDY, PI_STOCHASTIC

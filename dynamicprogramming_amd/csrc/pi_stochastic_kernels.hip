@@ -5,7 +5,7 @@
 //     <PI_STOCHASTIC + PI_D + the inference grid: PI_LO_INIT, PI_HI_INIT, PI_SHAPE_INIT, PI_STRIDES_INIT, PI_BITS_INIT>
 //     <include/pi_math.h>  + #define sinf/cosf/fmodf -> pi_*        (deterministic math, as in the sweeps)
 //     <the user's step_dynamics C string>                           (env plugin)
-//     <csrc/pi_rollout_kernels.hip>                                 (pi_rollout_action, pi_rollout_dynamics, pi_rollout_store_state)
+//     <csrc/pi_rollout_kernels.hip>                                 (pi_rollout_action, pi_rollout_dynamics, pi_rollout_episodes)
 //     <this file>
 // and hipRTC compiles it with the sweeps' flags (-O3 -ffp-contract=off).
 //
@@ -24,14 +24,14 @@
 //     explore iff (x0 >> 8) < eps24, eps24 = llrint(epsilon * 2^24) on the host: 0 never explores, 2^24 always does
 //     index   = (uint32)(((uint64)x1 * n_actions) >> 32)
 //
-// pi_stochastic_rollout_kernel is pi_rollout_kernel (pi_rollout_kernels.hip) — one lane per episode, the state in
-// registers, the loop exit by vote, the trajectory layout and the vector stores are that kernel's — with, per step of a
-// running episode, in this order:
+// pi_stochastic_rollout_kernel runs on the shared episode loop (pi_rollout_episodes, pi_rollout_kernels.hip): one lane
+// per episode, the state in registers, the loop exit by vote, the trajectory layout and the outputs are the loop's.  This
+// file adds the stream and, per step of a running episode, in this order:
 //   1. a = the interpolated action (pi_rollout_action: the bits pi_infer_query returns); skipped without a policy
 //   2. explore: a = actions[index], from the module's own action table
 //   3. action_noise != 0: a = a + action_noise * sym(x2), a float32 multiply, then an add; then
 //      a = fminf(fmaxf(a, a_min), a_max), the table's extremes.  No clamp when action_noise == 0
-//   4. step_dynamics; ret, disc, length and the freeze exactly as in pi_rollout_kernel
+//   4. step_dynamics; ret, disc, length and the freeze are the loop's
 //   5. not `done`: for every d with state_noise[d] != 0, s'[d] = s'[d] + state_noise[d] * sym(word d).  A dimension with
 //      zero noise is not touched; the disturbed state is neither clamped nor wrapped; it is what the controller and the
 //      plugin see next and what the trajectory records.  A `done` step stores its successor undisturbed.
@@ -50,7 +50,7 @@
 #error "pi_stochastic_kernels.hip is built behind #define PI_STOCHASTIC 1 (pi_stochastic.cpp)"
 #endif
 
-#define PI_ST_BLOCK 256
+#define PI_ST_BLOCK 256                      // the words kernel's; the rollout kernel runs PI_RO_BLOCK threads
 
 // state_noise as a kernel argument: six floats whatever D is (the host launches one layout), entries past D are zero
 struct PiStateNoise {
@@ -88,6 +88,55 @@ __device__ __forceinline__ float pi_stochastic_sym(unsigned int x) {
     return (float)((int)(x >> 8) - 8388608) * 0x1p-23f;
 }
 
+// Block 0 of a step (header): whether the episode explores, the table index it then takes and the action-noise word.
+// Drawn only when `draw` (eps24 != 0 or action_noise != 0, wave-uniform); nothing explores otherwise.
+struct PiActionDraw {
+    bool explore;
+    unsigned int index, noise_word;
+};
+__device__ __forceinline__ PiActionDraw pi_stochastic_draw(bool draw, unsigned long long seed, unsigned long long episode,
+                                                           int t, unsigned int eps24, int n_actions) {
+    PiWords w0 = {{0u, 0u, 0u, 0u}};
+    if (draw) w0 = pi_stochastic_words(seed, episode, (unsigned int)t, 0u);
+    return {draw && (w0.x[0] >> 8) < eps24, __umulhi(w0.x[1], (unsigned int)n_actions), w0.x[2]};
+}
+
+// step 3 of the header: action noise, a multiply, then an add, then the clamp to the table's extremes; a untouched
+// when action_noise == 0
+__device__ __forceinline__ float pi_stochastic_noisy_action(float a, float action_noise, unsigned int noise_word,
+                                                            float a_min, float a_max) {
+    if (action_noise != 0.0f) {
+        const float push = action_noise * pi_stochastic_sym(noise_word);
+        a = a + push;
+        a = fminf(fmaxf(a, a_min), a_max);
+    }
+    return a;
+}
+
+// step 5 of the header: the successor n of a step that is not `done`, disturbed from blocks 1 and 2 in every dimension
+// with state_noise[d] != 0
+__device__ __forceinline__ void pi_stochastic_disturb(float (&n)[PI_D], const PiStateNoise& state_noise,
+                                                      unsigned long long seed, unsigned long long episode, int t) {
+    const PiWords w1 = pi_stochastic_words(seed, episode, (unsigned int)t, 1u);
+#pragma unroll
+    for (int d = 0; d < (PI_D < 4 ? PI_D : 4); ++d)
+        if (state_noise.v[d] != 0.0f) {
+            const float push = state_noise.v[d] * pi_stochastic_sym(w1.x[d]);
+            n[d] = n[d] + push;
+        }
+#if PI_D == 6
+    if (state_noise.v[4] != 0.0f || state_noise.v[5] != 0.0f) {
+        const PiWords w2 = pi_stochastic_words(seed, episode, (unsigned int)t, 2u);
+#pragma unroll
+        for (int d = 4; d < 6; ++d)
+            if (state_noise.v[d] != 0.0f) {
+                const float push = state_noise.v[d] * pi_stochastic_sym(w2.x[d - 4]);
+                n[d] = n[d] + push;
+            }
+    }
+#endif
+}
+
 // The expected-greedy module (pi_expect_greedy_kernels.hip) takes the functions above and leaves the two kernels out.
 #ifndef PI_EXPECT_GREEDY
 // Probe: the four words of (seed, first_episode + row, step, block) for rows 0 .. m, out (m, 4) uint32.
@@ -101,7 +150,7 @@ pi_random_words_kernel(unsigned long long seed, unsigned long long first_episode
     for (int i = 0; i < 4; ++i) out[k * 4 + i] = w.x[i];
 }
 
-extern "C" __global__ void __launch_bounds__(PI_ST_BLOCK)
+extern "C" __global__ void __launch_bounds__(PI_RO_BLOCK)
 pi_stochastic_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, float gamma,
                              const int* __restrict__ policy, const float* __restrict__ policy_actions, int use_policy,
                              const float* __restrict__ actions, int n_actions, float a_min, float a_max,
@@ -109,92 +158,19 @@ pi_stochastic_rollout_kernel(const float* __restrict__ start, long long m, int n
                              unsigned long long seed, unsigned long long first_episode,
                              float* __restrict__ out_final, float* __restrict__ out_return, int* __restrict__ out_length,
                              unsigned char* __restrict__ out_terminated, float* __restrict__ traj, int traj_every) {
-    const long long k = (long long)blockIdx.x * PI_ST_BLOCK + threadIdx.x;
-    const bool exists = k < m;                       // lanes past the batch are frozen from the start and store nothing
-    const unsigned long long episode = first_episode + (unsigned long long)k;
-    float s[PI_D];
-#pragma unroll
-    for (int d = 0; d < PI_D; ++d) s[d] = exists ? start[k * PI_D + d] : 0.0f;
-    const bool record = traj != nullptr && traj_every > 0;
-    float* row = traj + k * PI_D;                    // this lane's slot of the next trajectory row (used when exists)
-    const long long row_floats = m * PI_D;
-    int rows_left = 0, until_row = 0;
-    if (record) {
-        rows_left = n_steps / traj_every;
-        until_row = traj_every;
-        if (exists) pi_rollout_store_state(row, s);
-        row += row_floats;
-    }
     const bool draw_action = eps24 != 0u || action_noise != 0.0f;
-    float ret = 0.0f, disc = 1.0f;
-    int length = 0;
-    bool terminated = false, running = exists;
-    for (int t = 0; t < n_steps && __any(running); ++t) {
-        if (running) {
-            float a = 0.0f;
-            bool explore = false;
-            PiWords w0 = {{0u, 0u, 0u, 0u}};
-            if (draw_action) {
-                w0 = pi_stochastic_words(seed, episode, (unsigned int)t, 0u);
-                explore = (w0.x[0] >> 8) < eps24;
-            }
-            if (explore)
-                a = actions[__umulhi(w0.x[1], (unsigned int)n_actions)];
-            else if (use_policy)
-                a = pi_rollout_action(PiGridFixed(), s, policy, policy_actions);
-            if (action_noise != 0.0f) {
-                const float push = action_noise * pi_stochastic_sym(w0.x[2]);
-                a = a + push;
-                a = fminf(fmaxf(a, a_min), a_max);
-            }
-            float n[PI_D], r;
-            bool done;
-            pi_rollout_dynamics(s, a, n, &r, &done);
-            const float gain = disc * r;
-            ret = ret + gain;
-            disc = disc * gamma;
-            if (any_state_noise && !done) {
-                const PiWords w1 = pi_stochastic_words(seed, episode, (unsigned int)t, 1u);
-#pragma unroll
-                for (int d = 0; d < (PI_D < 4 ? PI_D : 4); ++d)
-                    if (state_noise.v[d] != 0.0f) {
-                        const float push = state_noise.v[d] * pi_stochastic_sym(w1.x[d]);
-                        n[d] = n[d] + push;
-                    }
-#if PI_D == 6
-                if (state_noise.v[4] != 0.0f || state_noise.v[5] != 0.0f) {
-                    const PiWords w2 = pi_stochastic_words(seed, episode, (unsigned int)t, 2u);
-#pragma unroll
-                    for (int d = 4; d < 6; ++d)
-                        if (state_noise.v[d] != 0.0f) {
-                            const float push = state_noise.v[d] * pi_stochastic_sym(w2.x[d - 4]);
-                            n[d] = n[d] + push;
-                        }
-                }
-#endif
-            }
-#pragma unroll
-            for (int d = 0; d < PI_D; ++d) s[d] = n[d];
-            length = t + 1;
-            if (done) {
-                terminated = true;
-                running = false;
-            }
-        }
-        if (record && --until_row == 0) {
-            if (exists) pi_rollout_store_state(row, s);
-            row += row_floats;
-            until_row = traj_every;
-            --rows_left;
-        }
-    }
-    // the wave left the loop early: every episode of it is frozen, the remaining rows repeat the last state
-    if (record && exists)
-        for (; rows_left > 0; --rows_left, row += row_floats) pi_rollout_store_state(row, s);
-    if (!exists) return;
-    if (out_final != nullptr) pi_rollout_store_state(out_final + k * PI_D, s);
-    if (out_return != nullptr) out_return[k] = ret;
-    if (out_length != nullptr) out_length[k] = length;
-    if (out_terminated != nullptr) out_terminated[k] = terminated ? 1 : 0;
+    pi_rollout_episodes(start, m, n_steps, gamma, out_final, out_return, out_length, out_terminated, traj, traj_every,
+                        [&](const float (&s)[PI_D], int t, long long k, float (&n)[PI_D], float& r, bool& done) {
+                            const unsigned long long episode = first_episode + (unsigned long long)k;
+                            const PiActionDraw draw = pi_stochastic_draw(draw_action, seed, episode, t, eps24, n_actions);
+                            float a = 0.0f;
+                            if (draw.explore)
+                                a = actions[draw.index];
+                            else if (use_policy)
+                                a = pi_rollout_action(PiGridFixed(), s, policy, policy_actions);
+                            a = pi_stochastic_noisy_action(a, action_noise, draw.noise_word, a_min, a_max);
+                            pi_rollout_dynamics(s, a, n, &r, &done);
+                            if (any_state_noise && !done) pi_stochastic_disturb(n, state_noise, seed, episode, t);
+                        });
 }
 #endif  // PI_EXPECT_GREEDY

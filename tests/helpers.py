@@ -78,6 +78,69 @@ def golden(name: str):
     return np.load(GOLDEN / f"{name}.npz")
 
 
+# ---- ahead-of-time builds of the units the library hands to hipRTC (the *_do_not_spill and register-budget tests) ----
+ROOT = GOLDEN.parents[1]
+
+
+def kernel_resource_usage(text: str, tmp_path, stem: str = "unit") -> dict:
+    """{kernel: {"vgpr", "sgpr", "scratch", "lds"}} of the translation unit `text`, built for gfx950 with the library's
+    flags; the figures are the compiler's own (-Rpass-analysis=kernel-resource-usage)."""
+    import subprocess
+    import __graft_entry__ as G
+    src = Path(tmp_path) / f"{stem}.hip"
+    src.write_text(text)
+    res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
+                          "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
+                          "-o", str(Path(tmp_path) / f"{stem}.hsaco")], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-2000:]
+    usage, fn = {}, None
+    for line in res.stderr.splitlines():
+        if "Function Name:" in line:
+            fn = line.split("Function Name:")[1].split()[0]
+            usage[fn] = {}
+        elif fn and " VGPRs:" in line:
+            usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
+        elif fn and "TotalSGPRs:" in line:
+            usage[fn]["sgpr"] = int(line.split("TotalSGPRs:")[1].split()[0])
+        elif fn and "ScratchSize" in line:
+            usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+        elif fn and "LDS Size" in line:
+            usage[fn]["lds"] = int(line.split(":")[-1].split()[0])
+    return usage
+
+
+def inference_grid(name: str, bins: int):
+    """(lo, hi, grid_shape, strides, corner_bits) of the env's grid with `bins` points per dimension, as pi_infer_create
+    takes them."""
+    from itertools import product
+    tabs = env_bins(name, (bins,) * envs.ENVS[name]._D)
+    return (*oracle.grid_metadata(tabs), np.array(list(product([0, 1], repeat=len(tabs))), dtype=np.int32))
+
+
+def inference_unit(grid, plugin, defines: str = "", kernel_files=(), second_grid=None) -> str:
+    """The translation unit of a module of the inference handle, restated from the kernel files' headers: `defines`, the
+    grid (then `second_grid` as PI2_*, the hybrid's), pi_math.h and the env `plugin` (None: a unit without dynamics has
+    neither), then the files of csrc/ in order."""
+    def braces(v, fmt):
+        return "{" + ",".join(fmt(x) for x in v) + "}"
+
+    def hexf(x):
+        return float(np.float32(x)).hex() + "f"
+
+    def grid_defines(prefix, lo, hi, gshape, strides, bits):
+        return (f"#define {prefix}_D {len(lo)}\n#define {prefix}_LO_INIT {braces(lo, hexf)}\n"
+                f"#define {prefix}_HI_INIT {braces(hi, hexf)}\n#define {prefix}_SHAPE_INIT {braces(gshape, str)}\n"
+                f"#define {prefix}_STRIDES_INIT {braces(strides, str)}\n"
+                f"#define {prefix}_BITS_INIT {braces(bits, lambda r: braces(r, str))}\n")
+    text = defines + grid_defines("PI", *grid)
+    if second_grid is not None:
+        text += grid_defines("PI2", *second_grid)
+    if plugin is not None:
+        text += ((ROOT / "include" / "pi_math.h").read_text() + "\n#define sinf pi_sinf\n#define cosf pi_cosf\n"
+                 "#define fmodf pi_fmodf\n" + envs.dynamics_source(plugin) + "\n")
+    return text + "".join((ROOT / "dynamicprogramming_amd" / "csrc" / f).read_text() + "\n" for f in kernel_files)
+
+
 # ---- exchange plans pinned to a record (tests/golden/shard_plans.json, tests/golden/make_shard_plans_golden.py) ----
 PLAN_INFO_KEYS = ("mode", "recv_elems", "send_elems", "send_ranges", "interior_ranges")      # info[0..4] of pi_exchange_plan
 PLAN_SELECTORS = ("PLAN", "REACH_UNITS", "ROW_EXACT", "FUSED", "PAIR_EXACT", "FUSED_VALUES", "FIRST_ENTRIES",

@@ -110,44 +110,14 @@ def test_resample_module_compiles_for_gfx950_without_a_gpu(D, tmp_path):
 
 def test_resample_kernel_does_not_spill(tmp_path):
     """The 6-D kernel holds 64 weights, 64 indices and 64 source values per lane: no scratch in any D, on the
-    ahead-of-time build of the translation unit pi_infer_set_values hands to hipRTC (restated here from the header's
-    description of it), for the BASELINE grids as sources."""
-    import subprocess
-    import __graft_entry__ as G
-    import oracle
+    ahead-of-time build of the translation unit pi_infer_set_values hands to hipRTC (tests/helpers.inference_unit restates
+    it from the header's description), for the BASELINE grids as sources."""
     from dynamicprogramming_amd import envs
     from tests import helpers as H
-    kernel = (ROOT / "dynamicprogramming_amd" / "csrc" / "pi_resample_kernels.hip").read_text()
     for name, bins in (("pendulum", 200), ("double_pendulum_swingup", 40), ("double_cartpole", 13)):
-        tabs = H.env_bins(name, (bins,) * envs.ENVS[name]._D)
-        lo, hi, gshape, strides = oracle.grid_metadata(tabs)
-        D = len(tabs)
-
-        def braces(v, fmt):
-            return "{" + ",".join(fmt(x) for x in v) + "}"
-
-        def hexf(x):
-            return float(np.float32(x)).hex() + "f"
-        text = (f"#define PI_D {D}\n#define PI_LO_INIT {braces(lo, hexf)}\n#define PI_HI_INIT {braces(hi, hexf)}\n"
-                f"#define PI_SHAPE_INIT {braces(gshape, str)}\n#define PI_STRIDES_INIT {braces(strides, str)}\n"
-                f"#define PI_BITS_INIT {braces(_bits(D).tolist(), lambda r: braces(r, str))}\n{kernel}\n")
-        src = tmp_path / f"{name}.hip"
-        src.write_text(text)
-        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                              "-o", str(tmp_path / f"{name}.hsaco")], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-2000:]
-        usage, fn = {}, None
-        for line in res.stderr.splitlines():
-            if "Function Name:" in line:
-                fn = line.split("Function Name:")[1].split()[0]
-                usage[fn] = {}
-            elif fn and " VGPRs:" in line:
-                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-            elif fn and "ScratchSize" in line:
-                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
-            elif fn and "LDS Size" in line:
-                usage[fn]["lds"] = int(line.split(":")[-1].split()[0])
+        D = envs.ENVS[name]._D
+        text = H.inference_unit(H.inference_grid(name, bins), None, "", ["pi_resample_kernels.hip"])
+        usage = H.kernel_resource_usage(text, tmp_path, name)
         print(f"{name} {bins}^{D}: {usage}")
         assert set(usage) == {"pi_resample_kernel", "pi_resample_wide_kernel"}
         for k in usage.values():

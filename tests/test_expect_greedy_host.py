@@ -10,7 +10,6 @@ The device half is tests/test_gpu_expect_greedy.py.
 from __future__ import annotations
 
 import re
-import subprocess
 from itertools import product
 from pathlib import Path
 
@@ -193,46 +192,15 @@ def test_expect_greedy_kernels_compile_for_gfx950_without_a_gpu(name, shape, tmp
 
 def test_expect_greedy_kernels_do_not_spill(tmp_path):
     """Both kernels without scratch in every D, on the ahead-of-time build of the translation unit
-    pi_infer_set_expect_greedy hands to hipRTC (restated here from the kernel file's header), the method of
-    tests/test_stochastic_host.py.  The register counts are printed: the kernel file's header quotes them."""
-    import __graft_entry__ as G
-    csrc = ROOT / "dynamicprogramming_amd" / "csrc"
-    parts = [(csrc / f).read_text() for f in ("pi_rollout_kernels.hip", "pi_greedy_kernels.hip", "pi_stochastic_kernels.hip",
-                                              "pi_expect_greedy_kernels.hip")]
-    pi_math = (ROOT / "include" / "pi_math.h").read_text()
+    pi_infer_set_expect_greedy hands to hipRTC (tests/helpers.inference_unit restates it from the kernel file's header), the
+    method of tests/test_stochastic_host.py.  The register counts are printed: the kernel file's header quotes them."""
     for name, bins in (("pendulum", 200), ("cartpole_swingup", 50), ("double_cartpole", 25), ("double_cartpole_swingup", 25)):
         D = envs.ENVS[name]._D
-        c = C.case(name, (2,) * D)
-        tabs = H.env_bins(name, (bins,) * D)
-        import oracle
-        lo, hi, gshape, strides = oracle.grid_metadata(tabs)
-
-        def braces(v, fmt):
-            return "{" + ",".join(fmt(x) for x in v) + "}"
-
-        def hexf(x):
-            return float(np.float32(x)).hex() + "f"
-        text = (f"#define PI_EXPECT_GREEDY 1\n#define PI_GREEDY 1\n#define PI_STOCHASTIC 1\n#define PI_D {D}\n"
-                f"#define PI_LO_INIT {braces(lo, hexf)}\n#define PI_HI_INIT {braces(hi, hexf)}\n"
-                f"#define PI_SHAPE_INIT {braces(gshape, str)}\n#define PI_STRIDES_INIT {braces(strides, str)}\n"
-                f"#define PI_BITS_INIT {braces(c['bits'], lambda r: braces(r, str))}\n"
-                f"{pi_math}\n#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n"
-                f"{envs.dynamics_source(name)}\n" + "\n".join(parts) + "\n")
-        src = tmp_path / f"{name}.hip"
-        src.write_text(text)
-        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                              "-o", str(tmp_path / f"{name}.hsaco")], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-2000:]
-        usage, fn = {}, None
-        for line in res.stderr.splitlines():
-            if "Function Name:" in line:
-                fn = line.split("Function Name:")[1].split()[0]
-                usage[fn] = {}
-            elif fn and " VGPRs:" in line:
-                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-            elif fn and "ScratchSize" in line:
-                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+        text = H.inference_unit(H.inference_grid(name, bins), name,
+                                "#define PI_EXPECT_GREEDY 1\n#define PI_GREEDY 1\n#define PI_STOCHASTIC 1\n",
+                                ["pi_rollout_kernels.hip", "pi_greedy_kernels.hip", "pi_stochastic_kernels.hip",
+                                 "pi_expect_greedy_kernels.hip"])
+        usage = H.kernel_resource_usage(text, tmp_path, name)
         assert set(usage) == {"pi_expect_greedy_kernel", "pi_expect_greedy_rollout_kernel"}
         for fn, k in usage.items():
             print(f"{fn} {name} {bins}^{D}: {k}")

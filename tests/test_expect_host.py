@@ -7,7 +7,6 @@ tests/noise_backend.py.
 from __future__ import annotations
 
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -251,23 +250,10 @@ def test_expectation_kernels_do_not_spill(tmp_path):
     kernel = (ROOT / "dynamicprogramming_amd" / "csrc" / "pi_expect_kernels.hip").read_text()
     for name, bins in (("pendulum", 200), ("cartpole_swingup", 50), ("double_cartpole", 25), ("double_cartpole_swingup", 25)):
         eng, dyn = G._engine_for(name, bins)
-        src = tmp_path / f"{name}.hip"
-        src.write_text(eng.kernel_source(dyn) + "\n" + kernel + "\n")
+        text = eng.kernel_source(dyn) + "\n" + kernel + "\n"
         n_actions = eng.info(Info.N_ACTIONS)
         eng.close()
-        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                              "-o", str(tmp_path / f"{name}.hsaco")], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-2000:]
-        usage, fn = {}, None
-        for line in res.stderr.splitlines():
-            if "Function Name:" in line:
-                fn = line.split("Function Name:")[1].split()[0]
-                usage[fn] = {}
-            elif fn and " VGPRs:" in line:
-                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-            elif fn and "ScratchSize" in line:
-                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+        usage = H.kernel_resource_usage(text, tmp_path, name)
         mine = {fn: k for fn, k in usage.items() if fn.startswith("pi_expect_")}
         assert set(mine) == {"pi_expect_eval_kernel", "pi_expect_improve_kernel", "pi_expect_value_kernel"}
         for fn, k in mine.items():

@@ -191,43 +191,14 @@ def test_greedy_kernels_compile_for_gfx950_without_a_gpu(name, shape, tmp_path):
 def test_greedy_kernels_do_not_spill(tmp_path):
     """Per action the 6-D lookahead holds 64 values and the weights and offsets of 64 corners next to the plugin's own
     registers: both kernels must fit the 512 registers a lane of a 256-thread workgroup may use, without scratch, in
-    every D.  Checked on the ahead-of-time build of the translation unit pi_infer_set_greedy hands to hipRTC (restated
-    here from the header's description of it), the method of test_resample_kernel_does_not_spill."""
-    import subprocess
-    import __graft_entry__ as G
-    csrc = ROOT / "dynamicprogramming_amd" / "csrc"
-    kernel, helpers = (csrc / "pi_greedy_kernels.hip").read_text(), (csrc / "pi_rollout_kernels.hip").read_text()
-    math = (ROOT / "include" / "pi_math.h").read_text()
+    every D.  Checked on the ahead-of-time build of the translation unit pi_infer_set_greedy hands to hipRTC
+    (tests/helpers.inference_unit restates it from the header's description), the method of
+    test_resample_kernel_does_not_spill."""
     for name, bins in (("pendulum", 200), ("cartpole_swingup", 50), ("double_cartpole", 25), ("double_cartpole_swingup", 25)):
-        tabs, (lo, hi, gshape, strides) = _grid(name, (bins,) * envs.ENVS[name]._D)
-        D = len(tabs)
-        bits = list(product([0, 1], repeat=D))
-
-        def braces(v, fmt):
-            return "{" + ",".join(fmt(x) for x in v) + "}"
-
-        def hexf(x):
-            return float(np.float32(x)).hex() + "f"
-        text = (f"#define PI_GREEDY 1\n#define PI_D {D}\n#define PI_LO_INIT {braces(lo, hexf)}\n"
-                f"#define PI_HI_INIT {braces(hi, hexf)}\n#define PI_SHAPE_INIT {braces(gshape, str)}\n"
-                f"#define PI_STRIDES_INIT {braces(strides, str)}\n#define PI_BITS_INIT {braces(bits, lambda r: braces(r, str))}\n"
-                f"{math}\n#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n"
-                f"{envs.dynamics_source(name)}\n{helpers}\n{kernel}\n")
-        src = tmp_path / f"{name}.hip"
-        src.write_text(text)
-        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                              "-o", str(tmp_path / f"{name}.hsaco")], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-2000:]
-        usage, fn = {}, None
-        for line in res.stderr.splitlines():
-            if "Function Name:" in line:
-                fn = line.split("Function Name:")[1].split()[0]
-                usage[fn] = {}
-            elif fn and " VGPRs:" in line:
-                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-            elif fn and "ScratchSize" in line:
-                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+        D = envs.ENVS[name]._D
+        text = H.inference_unit(H.inference_grid(name, bins), name, "#define PI_GREEDY 1\n",
+                                ["pi_rollout_kernels.hip", "pi_greedy_kernels.hip"])
+        usage = H.kernel_resource_usage(text, tmp_path, name)
         assert set(usage) == {"pi_greedy_kernel", "pi_greedy_rollout_kernel"}
         for fn, k in usage.items():
             print(f"{fn} {name} {bins}^{D}: {k}")

@@ -7,7 +7,6 @@ and refuse what they must, the runner takes the reference's flags.  The device h
 from __future__ import annotations
 
 import re
-import subprocess
 from itertools import product
 from pathlib import Path
 
@@ -150,47 +149,13 @@ def test_hybrid_kernel_does_not_spill(tmp_path):
     """Selecting a lane's grid costs registers next to the 2^D weights and indices: on the full-size grids (the 6-D pair
     is the hybrid runner's) the kernel must stay without scratch, like pi_rollout_kernel
     (tests/test_rollout_host.py::test_rollout_kernel_does_not_spill).  Checked on the ahead-of-time build of the
-    translation unit pi_infer_set_partner hands to hipRTC, restated here from the kernel file's description of it."""
-    import oracle
-    import __graft_entry__ as G
-    csrc = ROOT / "dynamicprogramming_amd" / "csrc"
-    helpers, kernel = (csrc / "pi_rollout_kernels.hip").read_text(), (csrc / "pi_hybrid_kernels.hip").read_text()
-    math = (ROOT / "include" / "pi_math.h").read_text()
-
-    def braces(v, fmt):
-        return "{" + ",".join(fmt(x) for x in v) + "}"
-
-    def hexf(x):
-        return float(np.float32(x)).hex() + "f"
-
-    def defines(prefix, name, bins):
-        tabs = H.env_bins(name, (bins,) * envs.ENVS[name]._D)
-        lo, hi, gshape, strides = oracle.grid_metadata(tabs)
-        bits = list(product([0, 1], repeat=len(tabs)))
-        return (f"#define {prefix}_D {len(tabs)}\n#define {prefix}_LO_INIT {braces(lo, hexf)}\n"
-                f"#define {prefix}_HI_INIT {braces(hi, hexf)}\n#define {prefix}_SHAPE_INIT {braces(gshape, str)}\n"
-                f"#define {prefix}_STRIDES_INIT {braces(strides, str)}\n"
-                f"#define {prefix}_BITS_INIT {braces(bits, lambda r: braces(r, str))}\n")
+    translation unit pi_infer_set_partner hands to hipRTC, restated by tests/helpers.inference_unit from the kernel file's
+    description of it."""
     for name, bins, name2, bins2 in (("pendulum", 200, "pendulum", 50), ("cartpole_swingup", 50, "cartpole_swingup", 30),
                                      ("double_cartpole_swingup", 25, "double_cartpole", 25)):
-        text = ("#define PI_HYBRID 1\n" + defines("PI", name, bins) + defines("PI2", name2, bins2) + math +
-                "\n#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n" +
-                f"{envs.dynamics_source(name)}\n{helpers}\n{kernel}\n")
-        src = tmp_path / f"{name}.hip"
-        src.write_text(text)
-        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                              "-o", str(tmp_path / f"{name}.hsaco")], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-2000:]
-        usage, fn = {}, None
-        for line in res.stderr.splitlines():
-            if "Function Name:" in line:
-                fn = line.split("Function Name:")[1].split()[0]
-                usage[fn] = {}
-            elif fn and " VGPRs:" in line:
-                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-            elif fn and "ScratchSize" in line:
-                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+        text = H.inference_unit(H.inference_grid(name, bins), name, "#define PI_HYBRID 1\n",
+                                ["pi_rollout_kernels.hip", "pi_hybrid_kernels.hip"], second_grid=H.inference_grid(name2, bins2))
+        usage = H.kernel_resource_usage(text, tmp_path, name)
         assert set(usage) == {"pi_hybrid_rollout_kernel"}
         k = usage["pi_hybrid_rollout_kernel"]
         print(f"pi_hybrid_rollout_kernel {name} {bins}^D + {name2} {bins2}^D: {k}")

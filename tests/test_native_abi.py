@@ -402,31 +402,15 @@ def test_register_budgets_of_the_baseline_kernels(tmp_path):
     negative_results.txt (8), (10)) AND at most 80 SGPRs (measured: at 84 .. 96 the same thing happens although
     the compiler still reports eight waves, negative_results.txt (15)); the 6-D kernels must not spill.
     Checked on the ahead-of-time build of the same translation units the library hands to hipRTC."""
-    import subprocess
     import __graft_entry__ as G
     budgets = {("double_pendulum_swingup", 80): {"pi_eval_sweep_kernel": 64, "pi_improve_sweep_kernel": 96},
                ("cartpole_swingup", 50): {"pi_eval_sweep_kernel": 64, "pi_improve_sweep_kernel": 96},
                ("double_cartpole", 25): {"pi_eval_sweep_kernel": 128, "pi_improve_sweep_kernel": 168}}
     for (name, bins), limits in budgets.items():
         eng, dyn = G._engine_for(name, bins)
-        src = tmp_path / f"{name}.hip"
-        src.write_text(eng.kernel_source(dyn))
+        text = eng.kernel_source(dyn)
         eng.close()
-        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                              "-o", str(tmp_path / f"{name}.hsaco")], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-2000:]
-        usage, fn = {}, None
-        for line in res.stderr.splitlines():
-            if "Function Name:" in line:
-                fn = line.split("Function Name:")[1].split()[0]
-                usage[fn] = {}
-            elif fn and " VGPRs:" in line:
-                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-            elif fn and "TotalSGPRs:" in line:
-                usage[fn]["sgpr"] = int(line.split("TotalSGPRs:")[1].split()[0])
-            elif fn and "ScratchSize" in line:
-                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+        usage = H.kernel_resource_usage(text, tmp_path, name)
         for kernel, limit in limits.items():
             assert usage[kernel]["vgpr"] <= limit, (name, kernel, usage[kernel])
             assert usage[kernel]["scratch"] == 0, (name, kernel, usage[kernel])
@@ -439,7 +423,6 @@ def test_one_launch_run_kernels_build_and_keep_their_residency_budget(tmp_path):
     of an XCD's 32 CUs: its LDS footprint must be more than half of a CU's 160 KB (a second workgroup cannot join) and
     within it, four waves per SIMD allow 128 VGPRs, nothing may spill, and 32 workgroups must cover the grid.
     pi_run_resident_kernel (C1, pendulum 50 x 50) is one workgroup with V and the policy in LDS."""
-    import subprocess
     import __graft_entry__ as G
     for (name, bins, actions), kernel in ((("pendulum", 200, None), "pi_xcd_kernel"),
                                           (("pendulum", 50, np.linspace(-2.0, 2.0, 11, dtype=np.float32)), "pi_run_resident_kernel")):
@@ -447,23 +430,7 @@ def test_one_launch_run_kernels_build_and_keep_their_residency_budget(tmp_path):
         text = eng.kernel_source(dyn)
         n = eng.n_states
         eng.close()
-        src = tmp_path / f"{name}_{bins}.hip"
-        src.write_text(text)
-        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                              "-o", str(tmp_path / f"{name}_{bins}.hsaco")], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-2000:]
-        usage, fn = {}, None
-        for line in res.stderr.splitlines():
-            if "Function Name:" in line:
-                fn = line.split("Function Name:")[1].split()[0]
-                usage[fn] = {}
-            elif fn and " VGPRs:" in line:
-                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-            elif fn and "ScratchSize" in line:
-                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
-            elif fn and "LDS Size" in line:
-                usage[fn]["lds"] = int(line.split(":")[-1].split()[0])
+        usage = H.kernel_resource_usage(text, tmp_path, f"{name}_{bins}")
         k = usage[kernel]
         assert k["vgpr"] <= 128 and k["scratch"] == 0, (kernel, k)
         if kernel == "pi_xcd_kernel":
@@ -573,7 +540,6 @@ def test_fused_exchange_kernels_build_and_keep_the_register_budget(tmp_path):
     orders through the library (Option.BUILD_PUSH on a host-only handle) and through hipcc, where pi_eval_push_kernel
     must stay inside the budget of the kernel it replaces in a sharded sweep: 64 VGPRs and 80 SGPRs on the 80^4 grid
     (two 1 024-thread workgroups per CU), no scratch anywhere."""
-    import subprocess
     import __graft_entry__ as G
     push = (ROOT / "dynamicprogramming_amd" / "csrc" / "pi_push_kernels.hip").read_text()
     for name, bins, vgprs in (("double_pendulum_swingup", 80, 64), ("double_cartpole", 25, 128)):
@@ -586,24 +552,9 @@ def test_fused_exchange_kernels_build_and_keep_the_register_budget(tmp_path):
         before = len(list(tmp_path.glob("pi_*.hsaco")))
         eng.set_option(Option.BUILD_PUSH, 1)                  # second module -> cache
         assert len(list(tmp_path.glob("pi_*.hsaco"))) == before + 1
-        src = tmp_path / f"{name}_push.hip"
-        src.write_text(eng.kernel_source(dyn) + push)
+        text = eng.kernel_source(dyn) + push
         eng.close()
-        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                              "-o", str(tmp_path / f"{name}_push.hsaco")], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-2000:]
-        usage, fn = {}, None
-        for line in res.stderr.splitlines():
-            if "Function Name:" in line:
-                fn = line.split("Function Name:")[1].split()[0]
-                usage[fn] = {}
-            elif fn and " VGPRs:" in line:
-                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-            elif fn and "TotalSGPRs:" in line:
-                usage[fn]["sgpr"] = int(line.split("TotalSGPRs:")[1].split()[0])
-            elif fn and "ScratchSize" in line:
-                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+        usage = H.kernel_resource_usage(text, tmp_path, f"{name}_push")
         assert {"pi_eval_push_kernel", "pi_reach_pairs_kernel"} <= set(usage)
         k = usage["pi_eval_push_kernel"]
         assert k["vgpr"] <= vgprs and k["scratch"] == 0 and usage["pi_reach_pairs_kernel"]["scratch"] == 0, (name, usage)

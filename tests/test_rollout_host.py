@@ -57,44 +57,12 @@ def test_a_broken_plugin_is_reported_by_set_dynamics(tmp_path):
 def test_rollout_kernel_does_not_spill(tmp_path):
     """The 6-D kernel keeps 64 weights and 64 indices live per lane next to the plugin's own registers: it must fit the
     512 registers a lane of a 256-thread workgroup may use without scratch; so must the others.  Checked on the
-    ahead-of-time build of the translation unit pi_infer_set_dynamics hands to hipRTC (restated here from the header's
-    description of it)."""
-    import subprocess
-    import __graft_entry__ as G
-    root = H.GOLDEN.parents[1]
-    kernel = (root / "dynamicprogramming_amd" / "csrc" / "pi_rollout_kernels.hip").read_text()
-    math = (root / "include" / "pi_math.h").read_text()
+    ahead-of-time build of the translation unit pi_infer_set_dynamics hands to hipRTC (tests/helpers.inference_unit
+    restates it from the header's description)."""
     for name, bins in (("pendulum", 200), ("cartpole_swingup", 50), ("double_cartpole", 25), ("double_cartpole_swingup", 25)):
-        tabs = H.env_bins(name, (bins,) * envs.ENVS[name]._D)
-        lo, hi, gshape, strides = oracle.grid_metadata(tabs)
-        D = len(tabs)
-        bits = list(product([0, 1], repeat=D))
-
-        def braces(v, fmt):
-            return "{" + ",".join(fmt(x) for x in v) + "}"
-
-        def hexf(x):
-            return float(np.float32(x)).hex() + "f"
-        text = (f"#define PI_D {D}\n#define PI_LO_INIT {braces(lo, hexf)}\n#define PI_HI_INIT {braces(hi, hexf)}\n"
-                f"#define PI_SHAPE_INIT {braces(gshape, str)}\n#define PI_STRIDES_INIT {braces(strides, str)}\n"
-                f"#define PI_BITS_INIT {braces(bits, lambda r: braces(r, str))}\n{math}\n"
-                "#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n"
-                f"{envs.dynamics_source(name)}\n{kernel}\n")
-        src = tmp_path / f"{name}.hip"
-        src.write_text(text)
-        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                              "-o", str(tmp_path / f"{name}.hsaco")], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-2000:]
-        usage, fn = {}, None
-        for line in res.stderr.splitlines():
-            if "Function Name:" in line:
-                fn = line.split("Function Name:")[1].split()[0]
-                usage[fn] = {}
-            elif fn and " VGPRs:" in line:
-                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-            elif fn and "ScratchSize" in line:
-                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+        D = envs.ENVS[name]._D
+        text = H.inference_unit(H.inference_grid(name, bins), name, "", ["pi_rollout_kernels.hip"])
+        usage = H.kernel_resource_usage(text, tmp_path, name)
         k = usage["pi_rollout_kernel"]
         print(f"pi_rollout_kernel {name} {bins}^{D}: {k}")
         assert k["scratch"] == 0 and k["vgpr"] <= 512, (name, k)

@@ -236,43 +236,14 @@ def test_stochastic_kernels_compile_for_gfx950_without_a_gpu(name, shape, tmp_pa
 
 def test_stochastic_kernels_do_not_spill(tmp_path):
     """Both kernels without scratch in every D, on the ahead-of-time build of the translation unit
-    pi_infer_set_stochastic hands to hipRTC (restated here from the header's description of it), the method of
-    tests/test_greedy_host.py::test_greedy_kernels_do_not_spill.  The register counts are printed: the kernel file's
+    pi_infer_set_stochastic hands to hipRTC (tests/helpers.inference_unit restates it from the header's description), the
+    method of tests/test_greedy_host.py::test_greedy_kernels_do_not_spill.  The register counts are printed: the kernel file's
     header quotes them."""
-    import subprocess
-    import __graft_entry__ as G
-    csrc = ROOT / "dynamicprogramming_amd" / "csrc"
-    kernel, helpers = (csrc / "pi_stochastic_kernels.hip").read_text(), (csrc / "pi_rollout_kernels.hip").read_text()
-    pi_math = (ROOT / "include" / "pi_math.h").read_text()
     for name, bins in (("pendulum", 200), ("cartpole_swingup", 50), ("double_cartpole", 25), ("double_cartpole_swingup", 25)):
-        tabs, (lo, hi, gshape, strides, bits) = _grid(name, (bins,) * envs.ENVS[name]._D)
-        D = len(tabs)
-
-        def braces(v, fmt):
-            return "{" + ",".join(fmt(x) for x in v) + "}"
-
-        def hexf(x):
-            return float(np.float32(x)).hex() + "f"
-        text = (f"#define PI_STOCHASTIC 1\n#define PI_D {D}\n#define PI_LO_INIT {braces(lo, hexf)}\n"
-                f"#define PI_HI_INIT {braces(hi, hexf)}\n#define PI_SHAPE_INIT {braces(gshape, str)}\n"
-                f"#define PI_STRIDES_INIT {braces(strides, str)}\n#define PI_BITS_INIT {braces(bits, lambda r: braces(r, str))}\n"
-                f"{pi_math}\n#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n"
-                f"{envs.dynamics_source(name)}\n{helpers}\n{kernel}\n")
-        src = tmp_path / f"{name}.hip"
-        src.write_text(text)
-        res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                              "-o", str(tmp_path / f"{name}.hsaco")], capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-2000:]
-        usage, fn = {}, None
-        for line in res.stderr.splitlines():
-            if "Function Name:" in line:
-                fn = line.split("Function Name:")[1].split()[0]
-                usage[fn] = {}
-            elif fn and " VGPRs:" in line:
-                usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-            elif fn and "ScratchSize" in line:
-                usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+        D = envs.ENVS[name]._D
+        text = H.inference_unit(H.inference_grid(name, bins), name, "#define PI_STOCHASTIC 1\n",
+                                ["pi_rollout_kernels.hip", "pi_stochastic_kernels.hip"])
+        usage = H.kernel_resource_usage(text, tmp_path, name)
         assert set(usage) == {"pi_stochastic_rollout_kernel", "pi_random_words_kernel"}
         for fn, k in usage.items():
             print(f"{fn} {name} {bins}^{D}: {k}")

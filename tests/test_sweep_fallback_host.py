@@ -3,13 +3,12 @@ paths first") on a host-only handle: what the generated text holds, the register
 production memory order, and the plugins that keep the old single-instantiation form."""
 from __future__ import annotations
 
-import subprocess
-
 import numpy as np
 import pytest
 
 import __graft_entry__ as G
 from dynamicprogramming_amd import _native, envs
+from tests import helpers as H
 
 NAME = "double_pendulum_swingup"
 
@@ -24,31 +23,10 @@ def _engine_80(order="production"):
                           np.asarray(cls.ACTIONS, dtype=np.float32), device=-1, order=order)
 
 
-def _usage(text, tmp_path):
-    src = tmp_path / "unit.hip"
-    src.write_text(text)
-    res = subprocess.run([G.HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
-                          "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src),
-                          "-o", str(tmp_path / "unit.hsaco")], capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    usage, fn = {}, None
-    for line in res.stderr.splitlines():
-        if "Function Name:" in line:
-            fn = line.split("Function Name:")[1].split()[0]
-            usage[fn] = {}
-        elif fn and " VGPRs:" in line:
-            usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
-        elif fn and "TotalSGPRs:" in line:
-            usage[fn]["sgpr"] = int(line.split("TotalSGPRs:")[1].split()[0])
-        elif fn and "ScratchSize" in line:
-            usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
-    return usage
-
-
 @pytest.fixture(scope="module")
 def usage_80(tmp_path_factory):
     eng = _engine_80()
-    usage = _usage(eng.kernel_source(envs.dynamics_source(NAME)), tmp_path_factory.mktemp("unit80"))
+    usage = H.kernel_resource_usage(eng.kernel_source(envs.dynamics_source(NAME)), tmp_path_factory.mktemp("unit80"))
     eng.close()
     return usage
 
