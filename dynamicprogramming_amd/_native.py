@@ -110,6 +110,11 @@ SIGNATURES = {
     "pi_infer_rollout_expect_greedy": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                                       ctypes.c_float, ctypes.c_float, _f32p, ctypes.c_uint64, ctypes.c_uint64,
                                                       _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
+    "pi_infer_set_partner_stochastic": (ctypes.c_int, [_vp, _vp, _f32p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
+    "pi_infer_rollout_hybrid_stochastic": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, _f32p,
+                                                          _f32p, ctypes.c_float, ctypes.c_float, _f32p, ctypes.c_uint64,
+                                                          ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                          ctypes.c_int, _vp]),
     "pi_plan_schedule": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.POINTER(ctypes.c_uint64)]),
     "pi_set_option": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int64]),
@@ -697,6 +702,44 @@ class InferenceEngine:
                                              d_length or None, d_terminated or None, d_secondary_steps or None,
                                              d_last_mode or None, d_traj or None, int(traj_every), stream or None),
                "pi_infer_rollout_hybrid")
+
+    def set_partner_stochastic(self, partner: "InferenceEngine", action_space) -> str:
+        """Upload the pair's exploration table and build this handle's stochastic hybrid module: its grid + `partner`'s
+        grid + the plugin of the last set_dynamics + the stochastic hybrid rollout kernel (a compile check on host-only
+        handles); returns the compiler's log.  A later set_dynamics drops the module again."""
+        act = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        log = ctypes.create_string_buffer(1 << 16)
+        rc = lib().pi_infer_set_partner_stochastic(self._h, partner._h if partner is not None else None,
+                                                   None if act is None else act.ctypes.data_as(_f32p),
+                                                   0 if act is None else len(act), log, len(log))
+        text = log.value.decode(errors="replace")
+        if rc != 0:
+            raise NativeError(f"pi_infer_set_partner_stochastic failed:\n{last_error()}")
+        return text
+
+    def rollout_hybrid_stochastic(self, partner: "InferenceEngine", d_start, m, n_steps, enter, leave, gamma=1.0, epsilon=0.0,
+                                  action_noise=0.0, state_noise=None, seed=0, first_episode=0, d_final=0, d_return=0,
+                                  d_length=0, d_terminated=0, d_secondary_steps=0, d_last_mode=0, d_switches=0, d_traj=0,
+                                  traj_every=0, stream=0) -> None:
+        """`rollout_hybrid` with the epsilon-random actions, action noise and state noise of `rollout_stochastic` from the
+        same stream, in one launch (pi_infer_rollout_hybrid_stochastic; raw device pointers, `enter` / `leave` /
+        `state_noise` host arrays of D floats; `d_switches` counts an episode's mode changes; asynchronous)."""
+        box = [None if v is None else np.ascontiguousarray(v, dtype=np.float32) for v in (enter, leave)]
+        for v in box:
+            if v is not None and v.shape != (self.D,):
+                raise ValueError(f"enter and leave must hold {self.D} thresholds each")
+        ent, lea = (None if v is None else v.ctypes.data_as(_f32p) for v in box)
+        noise = None
+        if state_noise is not None:
+            noise = np.ascontiguousarray(state_noise, dtype=np.float32)
+            if noise.shape != (self.D,):
+                raise ValueError(f"state_noise must hold {self.D} values")
+        _check(lib().pi_infer_rollout_hybrid_stochastic(
+            self._h, partner._h if partner is not None else None, d_start or None, int(m), int(n_steps), float(gamma), ent,
+            lea, float(epsilon), float(action_noise), None if noise is None else noise.ctypes.data_as(_f32p), int(seed),
+            int(first_episode), d_final or None, d_return or None, d_length or None, d_terminated or None,
+            d_secondary_steps or None, d_last_mode or None, d_switches or None, d_traj or None, int(traj_every),
+            stream or None), "pi_infer_rollout_hybrid_stochastic")
 
     def set_values(self, values) -> str:
         """Upload the value function of this handle's grid (the user's order) and build the resample kernel (a compile

@@ -58,6 +58,8 @@ struct PiHybridBox {
     float enter[6], leave[6];
 };
 
+// The stochastic hybrid module (pi_hybrid_stochastic_kernels.hip) takes what stands above and leaves the kernel out.
+#ifndef PI_HYBRID_STOCHASTIC
 extern "C" __global__ void __launch_bounds__(PI_RO_BLOCK)
 pi_hybrid_rollout_kernel(const float* __restrict__ start, long long m, int n_steps, float gamma,
                          const int* __restrict__ policy0, const float* __restrict__ actions0,
@@ -87,3 +89,4 @@ pi_hybrid_rollout_kernel(const float* __restrict__ start, long long m, int n_ste
     if (out_secondary != nullptr) out_secondary[k] = secondary;
     if (out_last_mode != nullptr) out_last_mode[k] = second ? 1 : 0;
 }
+#endif  // PI_HYBRID_STOCHASTIC

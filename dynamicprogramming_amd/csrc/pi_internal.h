@@ -7,7 +7,8 @@
 //   pi_onelaunch.cpp  the one-launch families (dataflow, XCD-local, LDS-resident runs) and their scratch blocks
 //   pi_live.cpp       the live-state list of pi_prepare_mask and the per-evaluation list of pi_eval_begin
 //   pi_comm.cpp       multi-GPU transports and the sharded sweep driver;  pi_p2p.cpp  the peer-to-peer transport
-//   pi_infer.cpp, pi_rollout.cpp   the inference handle and its rollouts;  pi_hybrid.cpp  rollouts that switch between two handles
+//   pi_infer.cpp, pi_rollout.cpp   the inference handle and its rollouts;  pi_hybrid.cpp  rollouts that switch between two handles,
+//                     deterministic and with the stochastic rollouts' stream inside
 //   pi_resample.cpp   the inference handle's solution interpolated onto another grid (grid continuation)
 //   pi_greedy.cpp     value-greedy control on the inference handle: one-step lookahead on V, queries and rollouts
 //   pi_stochastic.cpp stochastic rollouts on the inference handle: random baseline, epsilon-random actions, noise (Philox)
@@ -295,9 +296,12 @@ struct pi_infer {
     //                  pi_random_words_kernel; the table is what exploring steps draw from, its extremes clamp a noisy action
     //   expect_greedy  (pi_infer_set_expect_greedy, pi_expect_greedy.cpp)  the functions of the greedy and the stochastic
     //                  file + csrc/pi_expect_greedy_kernels.hip; the extremes clamp a + da_k and a noisy action
-    // A new plugin unloads the four that were built on the one before it.
-    pi::InferModule rollout, hybrid, greedy, stochastic, expect_greedy;
-    std::string partner_defines;
+    //   hybrid_stochastic  (pi_infer_set_partner_stochastic, pi_hybrid.cpp)  a partner's grid + the functions of the hybrid
+    //                  and the stochastic file + csrc/pi_hybrid_stochastic_kernels.hip; the table is the pair's exploration
+    //                  table; partner_stochastic_defines: the partner grid it was built for
+    // A new plugin unloads the five that were built on the one before it.
+    pi::InferModule rollout, hybrid, greedy, stochastic, expect_greedy, hybrid_stochastic;
+    std::string partner_defines, partner_stochastic_defines;
     // the resample module (pi_infer_set_values, pi_resample.cpp): this grid + csrc/pi_resample_kernels.hip, and the value
     // function of the solution.  d_resample_tab: the destination's bin tables | action map of the last pi_infer_resample
     // (owned; resample_tab: the same words on the host — a call that brings the same destination uploads nothing)
@@ -371,7 +375,7 @@ int compile_image(const std::string& src, const char* cache_dir, char* log, size
 // 63-bit size, d_start, alignment).  0: launch `*blocks` workgroups; 1: refused (pi::fail was called); 2: m == 0, nothing to do
 int check_rollout_args(int D, const float* d_start, int64_t m, int n_steps, const float* d_final, const float* d_traj,
                        int traj_every, int64_t* blocks);
-// pi_rollout.cpp: what the five rollout modules share.  build_infer_module assembles a translation unit — `leading` (the
+// pi_rollout.cpp: what the six rollout modules share.  build_infer_module assembles a translation unit — `leading` (the
 // module's defines and the grid(s)), pi_math.h, the sinf / cosf / fmodf defines, `plugin`, then every part behind its
 // "// ---- <section> ----" line — and compiles it with the handle's code-object cache.
 struct UnitPart {

@@ -130,7 +130,8 @@ __device__ __forceinline__ float pi_rollout_table_entry(const float* __restrict_
 }
 
 // The episode loop of every fused rollout (this file's kernel and those of pi_hybrid_kernels.hip, pi_greedy_kernels.hip,
-// pi_stochastic_kernels.hip and pi_expect_greedy_kernels.hip): lane k of the launch is episode k of the batch.
+// pi_stochastic_kernels.hip, pi_expect_greedy_kernels.hip and pi_hybrid_stochastic_kernels.hip): lane k of the launch is
+// episode k of the batch.
 __device__ __forceinline__ long long pi_rollout_lane() { return (long long)blockIdx.x * PI_RO_BLOCK + threadIdx.x; }
 
 // Everything of a rollout but the controller: the start-state load, the trajectory rows, the loop exit by vote, return,

@@ -137,8 +137,9 @@ __device__ __forceinline__ void pi_stochastic_disturb(float (&n)[PI_D], const Pi
 #endif
 }
 
-// The expected-greedy module (pi_expect_greedy_kernels.hip) takes the functions above and leaves the two kernels out.
-#ifndef PI_EXPECT_GREEDY
+// The expected-greedy module (pi_expect_greedy_kernels.hip) and the stochastic hybrid module
+// (pi_hybrid_stochastic_kernels.hip) take the functions above and leave the two kernels out.
+#if !defined(PI_EXPECT_GREEDY) && !defined(PI_HYBRID_STOCHASTIC)
 // Probe: the four words of (seed, first_episode + row, step, block) for rows 0 .. m, out (m, 4) uint32.
 extern "C" __global__ void __launch_bounds__(PI_ST_BLOCK)
 pi_random_words_kernel(unsigned long long seed, unsigned long long first_episode, long long m, unsigned int step,
@@ -173,4 +174,4 @@ pi_stochastic_rollout_kernel(const float* __restrict__ start, long long m, int n
                             if (any_state_noise && !done) pi_stochastic_disturb(n, state_noise, seed, episode, t);
                         });
 }
-#endif  // PI_EXPECT_GREEDY
+#endif  // PI_EXPECT_GREEDY, PI_HYBRID_STOCHASTIC

@@ -624,6 +624,42 @@ int pi_plan_schedule(pi_handle* h, int block, int64_t first, int64_t count, int6
  *                       state_noise, seed, first_episode, gamma and the outputs as in pi_infer_rollout_stochastic;
  *                       neither gamma may be NaN.  Needs no policy.  Refused without the module or without a set; every
  *                       refusal is an error code and pi_last_error, never a launch.  m == 0 is a no-op.  Asynchronous.
+ * Stochastic hybrid rollouts (no reference counterpart: the reference's hybrid demo runs in a noiseless world, where the
+ * hysteresis of its switch is never tested): pi_infer_rollout_hybrid with the stream of pi_infer_rollout_stochastic
+ * inside, as ONE launch for m episodes.  The counters, the conversions and the words of blocks 0, 1 and 2 are exactly
+ * those of the stochastic rollouts, so the pair and a single policy are compared under common random numbers.  Per step
+ * of a running episode, in this order:
+ *   1. mode: the rule of pi_infer_rollout_hybrid (float32, strict comparisons, mode 0 at the start of every episode)
+ *      applied to the state the step starts from, which the step before may have disturbed; on every step taken,
+ *      exploring or not.  secondary_steps += mode; switches += 1 when the mode differs from that of the previous step
+ *      taken — before step 0 the mode is 0, so an episode that enters at step 0 counts one
+ *   2. block 0, drawn only when eps24 != 0 or action_noise != 0; explore iff (x0 >> 8) < eps24, as in the stochastic
+ *      rollouts
+ *   3. action: an exploring step takes action_space[(uint32)(((uint64)x1 * n_actions) >> 32)] from the module's own
+ *      exploration table — ONE table for the pair: one plant, one actuator; any other step takes the interpolated action
+ *      of the mode's policy on its own grid, the bits pi_infer_query returns on that handle
+ *   4. action_noise != 0: a = a + action_noise * sym(x2), a float32 multiply, then an add; then
+ *      a = fminf(fmaxf(a, a_min), a_max), the extremes of the exploration table.  No clamp when action_noise == 0
+ *   5. step_dynamics with the primary handle's plugin; ret, disc, length and the freeze exactly as in pi_infer_rollout
+ *   6. not `done`: the state noise of block 1 (and block 2 in 6-D) as in the stochastic rollouts, step 5 there: neither
+ *      clamped nor wrapped, it is what the trajectory records and what the next step's mode rule, controller and plugin see.
+ * With epsilon, action_noise and state_noise all zero the outputs are pi_infer_rollout_hybrid's, bit for bit; with
+ * enter = 0 they are pi_infer_rollout_stochastic's on the primary handle with the same table.
+ *   pi_infer_set_partner_stochastic  host array: the exploration table (n_actions >= 1 finite float32), copied to the
+ *                       device — the module's own copy; builds h's EIGHTH module: h's grid + partner's grid + the plugin
+ *                       last given to pi_infer_set_dynamics(h) + the functions of csrc/pi_hybrid_kernels.hip and
+ *                       csrc/pi_stochastic_kernels.hip + csrc/pi_hybrid_stochastic_kernels.hip.  The pair must pass the
+ *                       checks of pi_infer_set_partner.  Same cache, flags and log convention as pi_infer_set_dynamics;
+ *                       device = -1 handles: compile check.  pi_infer_set_dynamics on h drops the module again (the next
+ *                       call then fails, naming pi_infer_set_partner_stochastic).  Independent of pi_infer_set_partner
+ *                       and pi_infer_set_stochastic: neither is needed
+ *   pi_infer_rollout_hybrid_stochastic  arguments, outputs and refusals of pi_infer_rollout_hybrid (the pair, a policy on
+ *                       BOTH handles whatever epsilon is, the module missing or built for another partner grid, NaN
+ *                       thresholds, enter[d] > leave[d]), plus epsilon, action_noise, state_noise, seed, first_episode
+ *                       with the rules of pi_infer_rollout_stochastic, and d_switches (m) int32, which may be null like
+ *                       every other output.  Every refusal is an error code and pi_last_error, never a launch.
+ *                       m == 0 is a no-op, n_steps == 0 copies the start (lengths, returns, secondary_steps, last_mode,
+ *                       switches 0).  Asynchronous.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pi_infer pi_infer;
 pi_infer* pi_infer_create(int device, int D, const float* lo, const float* hi, const int32_t* grid_shape,
@@ -669,6 +705,14 @@ int pi_infer_rollout_expect_greedy(pi_infer* h, const float* d_start, int64_t m,
                                    float lookahead_gamma, float epsilon, float action_noise, const float* state_noise,
                                    uint64_t seed, uint64_t first_episode, float* d_final, float* d_return,
                                    int32_t* d_length, uint8_t* d_terminated, float* d_traj, int traj_every, void* stream);
+int pi_infer_set_partner_stochastic(pi_infer* h, pi_infer* partner, const float* action_space, int n_actions, char* log,
+                                    size_t log_len);
+int pi_infer_rollout_hybrid_stochastic(pi_infer* h, pi_infer* partner, const float* d_start, int64_t m, int n_steps,
+                                       float gamma, const float* enter, const float* leave, float epsilon,
+                                       float action_noise, const float* state_noise, uint64_t seed, uint64_t first_episode,
+                                       float* d_final, float* d_return, int32_t* d_length, uint8_t* d_terminated,
+                                       int32_t* d_secondary_steps, uint8_t* d_last_mode, int32_t* d_switches, float* d_traj,
+                                       int traj_every, void* stream);
 
 /* Tuning: the `what` of pi_set_option. */
 enum pi_option_code {

@@ -14,6 +14,15 @@ moved by U(-0.05, 0.05) from default_rng(seed), in episode order.
 Flags: --episodes, --steps, --seed act; --render, --record, --random, --bins, --no-plot, --retrain, --save-path are
 accepted and ignored with a note, as the reference's runner ignores the last five.  --swingup-path / --balance-path
 are extensions (the reference's paths are fixed).
+
+--epsilon E, --action-noise A and --state-noise X [X ...] (extensions, default 0; the flags of the other runners,
+runners/_cli.py) run the same episodes in a noisy world (HybridPolicy.rollout(epsilon=..., action_noise=...,
+state_noise=...); csrc/pi_hybrid_stochastic_kernels.hip): a step takes a uniformly random action of the swing-up
+policy's action set with probability E, actuator noise A * u is added to every action, X * u to the state after every
+step, and the switch rule sees the disturbed state.  The stream is seeded by --seed like the starts, as in the other
+runners.  Every episode line then gains switches=N, how often the episode changed its mode, and one summary line
+follows: mean reward, share of episodes terminated, share ending in BALANCE, mean switches.  Without these flags the
+output is what it was.
 """
 import argparse
 import sys
@@ -52,7 +61,19 @@ def build_parser() -> argparse.ArgumentParser:
                    help=f"(extension) the swing-up policy archive (default: {SWINGUP_POLICY_PATH})")
     p.add_argument("--balance-path", type=Path, default=BALANCE_POLICY_PATH,
                    help=f"(extension) the balance policy archive (default: {BALANCE_POLICY_PATH})")
+    p.add_argument("--epsilon", type=float, default=0.0, metavar="E",
+                   help="(extension) probability that a step takes a uniformly random action instead")
+    p.add_argument("--action-noise", type=float, default=0.0, metavar="A",
+                   help="(extension) actuator noise: A * u, u uniform in [-1, 1), added to every action, "
+                        "which is then clamped to the action set's range")
+    p.add_argument("--state-noise", type=float, nargs="+", default=None, metavar="X",
+                   help="(extension) state disturbance after every step: X * u per dimension (one value "
+                        "for every dimension, or one per dimension)")
     return p
+
+
+def noise_requested(args) -> bool:
+    return args.epsilon != 0.0 or args.action_noise != 0.0 or args.state_noise is not None
 
 
 def ignored_flags(args) -> list:
@@ -89,23 +110,31 @@ def hybrid_policy(swingup_path: Path, balance_path: Path, device="cuda:0"):
 
 
 def evaluate(n_episodes: int = 3, steps: int = 1000, seed: int = 42, swingup_path: Path = SWINGUP_POLICY_PATH,
-             balance_path: Path = BALANCE_POLICY_PATH):
-    """All episodes in one hybrid launch; one line per episode in the reference's format (:129-134).  Returns the
-    HybridRolloutResult."""
+             balance_path: Path = BALANCE_POLICY_PATH, noise=None):
+    """All episodes in one hybrid launch; one line per episode in the reference's format (:129-134).  `noise`: the
+    keywords epsilon, action_noise, state_noise of a stochastic rollout (--epsilon, --action-noise, --state-noise), its
+    stream seeded by `seed` like the starts; the lines then carry the switch count and a summary line follows.  Returns
+    the HybridRolloutResult (the StochasticHybridRolloutResult)."""
     import numpy as np
     hp = hybrid_policy(swingup_path, balance_path)
     try:
-        res = hp.rollout(start_states(seed, n_episodes), steps)
+        extra = {} if noise is None else dict(noise, seed=seed)
+        res = hp.rollout(start_states(seed, n_episodes), steps, **extra)
     finally:
         hp.primary.close()
         hp.secondary.close()
     for ep in range(n_episodes):
         x, xd, th1, w1, th2, w2 = res.states[ep]
         mode = "BALANCE" if res.last_mode[ep] else "SWINGUP"
+        switches = "" if noise is None else f"switches={int(res.switches[ep])} | "
         print(f"Ep {ep + 1}: {int(res.lengths[ep])} steps | reward={float(res.returns[ep]):.0f} | "
-              f"balance_steps={int(res.secondary_steps[ep])} | last_mode={mode} | "
+              f"balance_steps={int(res.secondary_steps[ep])} | {switches}last_mode={mode} | "
               f"th1={np.degrees(th1):+.1f}° th2={np.degrees(th2):+.1f}° "
               f"w1={w1:+.2f} w2={w2:+.2f}")
+    if noise is not None and n_episodes > 0:
+        print(f"Summary: {n_episodes} episodes | mean reward={float(np.mean(res.returns)):.1f} | "
+              f"terminated={float(np.mean(res.terminated)):.2f} | ending in BALANCE={float(np.mean(res.last_mode != 0)):.2f} | "
+              f"mean switches={float(np.mean(res.switches)):.2f}")
     return res
 
 
@@ -122,7 +151,9 @@ def main(argv=None):
                  "    python runners/double_cartpole_swingup_cuda.py   (writes results/double_cartpole_swingup_cuda_policy.npz)\n"
                  "    python runners/double_cartpole_cuda.py           (writes results/double_cartpole_cuda_policy.npz)\n"
                  "or name them with --swingup-path / --balance-path")
-    return evaluate(args.episodes, args.steps, args.seed, args.swingup_path, args.balance_path)
+    noise = dict(epsilon=args.epsilon, action_noise=args.action_noise, state_noise=args.state_noise) \
+        if noise_requested(args) else None
+    return evaluate(args.episodes, args.steps, args.seed, args.swingup_path, args.balance_path, noise)
 
 
 if __name__ == "__main__":

@@ -37,7 +37,14 @@ interpolated-policy rollouts of the same batch, then the registers and scratch o
 the noise planned for, on the two settings of tools/expect_bench.py with common seeds: nominal and noise-aware training,
 each under its policy table and under the lookahead (zero set on the nominal V, the training set on the noise-aware V).
 The table is written to --out.
-usage: python tools/rollout_bench.py [--hybrid | --greedy | --stochastic | --expected] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
+--hybrid --stochastic: the two-policy rollout under noise (pi_infer_rollout_hybrid_stochastic,
+csrc/pi_hybrid_stochastic_kernels.hip): a 2-D, a 4-D and the 6-D pair of --hybrid (HYBRID_PAIRS), seeded random policies, the
+noise of --stochastic, m = 4 096 episodes of --steps steps (profiles/r15 was taken with --steps 300); per pair the fused
+launch, the loop it replaces (per step a query on each handle, the words of pi_infer_random_words, one pi_probe_step and the
+mixing as torch ops), the deterministic hybrid rollout and the single-policy stochastic rollout of the same batch — a sample
+of a fused path is ten calls back to back —, then the registers and scratch of the kernel and of the hybrid kernel beside
+it.  The table is written to --out.
+usage: python tools/rollout_bench.py [--hybrid | --greedy | --stochastic | --expected | --hybrid --stochastic] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
 """
 import argparse
 import json
@@ -764,6 +771,248 @@ def expected_driver(args):
     print(out.read_text())
 
 
+INF = float("inf")
+# --hybrid --stochastic: (primary env, bins, secondary env, bins, enter, leave) per D; the 6-D pair and its box are --hybrid's
+# (the runner's), the 2-D and 4-D pairs a coarser grid of the same env behind a box around the upright position
+HYBRID_PAIRS = {
+    "c2": ("pendulum", 200, "pendulum", 50, (1.0, 3.0), (1.4, 5.0)),
+    "c3": ("cartpole_swingup", 50, "cartpole_swingup", 30, (INF, INF, 0.9, 5.0), (INF, INF, 1.1, 7.0)),
+    "c5": ("double_cartpole_swingup", 25, "double_cartpole", 25, (INF, INF, 0.32, 4.0, 0.32, 4.0), (INF, INF, 0.38, 5.0, 0.38, 5.0)),
+}
+FUSED_PER_SAMPLE = 10       # a fused launch takes 0.3 to 2 ms: a sample times this many back to back
+
+
+def _grid_tables(env, bins):
+    import numpy as np
+    from dynamicprogramming_amd import envs
+    tabs = [np.asarray(b, np.float32) for b in envs.ENVS[env].bins_space(bins).values()]
+    D = len(tabs)
+    shape = np.array([len(t) for t in tabs], np.int32)
+    lo, hi = np.array([t.min() for t in tabs], np.float32), np.array([t.max() for t in tabs], np.float32)
+    strides = np.array([int(np.prod(shape[d + 1:])) for d in range(D)], np.int32)
+    bits = np.array(list(product([0, 1], repeat=D)), dtype=np.int32)
+    return tabs, (lo, hi, shape, strides, bits)
+
+
+def hybrid_stochastic_child(args):
+    import numpy as np
+    import torch
+    from dynamicprogramming_amd import _native, envs
+    from utils import barycentric as B
+    env, bins, env2, bins2, enter, leave = HYBRID_PAIRS[args.config]
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(0)
+    pols = []
+    for e, g in ((env, bins), (env2, bins2)):
+        tabs, grid = _grid_tables(e, g)
+        acts = np.asarray(envs.ENVS[e].ACTIONS, np.float32)
+        policy = rng.integers(0, len(acts), size=int(np.prod(grid[2].astype(np.int64))), dtype=np.int32)
+        pols.append(B.DevicePolicy(policy, acts, *grid, device=dev))
+    dp, dp2 = pols
+    tabs, (lo, hi, shape, _, _) = _grid_tables(env, bins)
+    D = len(tabs)
+    acts = np.asarray(envs.ENVS[env].ACTIONS, np.float32)
+    dyn = envs.dynamics_source(env)
+    dp.set_dynamics(dyn)
+    dp.set_stochastic()                                   # the loop's words and the single-policy stochastic rollout
+    hp = B.HybridPolicy(dp, dp2, enter, leave)
+    m, steps, seed = args.m, args.steps, 20261020
+    epsilon, a_noise = 0.3, float(np.float32(0.1) * (acts.max() - acts.min()))
+    s_noise = (np.float32(0.002) * (hi - lo)).astype(np.float32)             # every dimension: all the draw blocks of D
+    noisy = dict(epsilon=epsilon, action_noise=a_noise, state_noise=s_noise, seed=seed)
+    starts = torch.from_numpy((lo + (hi - lo) * rng.random((m, D), dtype=np.float32)).astype(np.float32)).to(dev)
+    eng = _native.Engine(D, shape, lo, hi, tabs, acts, device=0)
+    eng.compile(dyn)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ent, lea = torch.tensor(enter, dtype=torch.float32, device=dev), torch.tensor(leave, dtype=torch.float32, device=dev)
+    d_acts = torch.from_numpy(acts).to(dev)
+    eps24, n_act = B.explore_threshold(epsilon), len(acts)
+    amp = torch.tensor(a_noise, dtype=torch.float32, device=dev)
+    d_noise = torch.from_numpy(s_noise).to(dev)
+    a_lo, a_hi = d_acts.min(), d_acts.max()
+    blocks = (1, 2) if D > 4 else (1,)
+
+    def sym(x):                                           # int32 words holding uint32 bits -> [-1, 1), exact
+        return (((x >> 8) & 0xFFFFFF) - 8388608).to(torch.float32) * 2.0 ** -23
+
+    def loop():                                           # two queries, the probe kernel's words, one plugin step, torch mixing
+        states = starts.clone()
+        nxt = torch.empty_like(states)
+        rew = torch.empty(m, dtype=torch.float32, device=dev)
+        done = torch.empty(m, dtype=torch.uint8, device=dev)
+        ret = torch.zeros(m, dtype=torch.float32, device=dev)
+        length = torch.zeros(m, dtype=torch.int32, device=dev)
+        second = torch.zeros(m, dtype=torch.int32, device=dev)
+        switches = torch.zeros(m, dtype=torch.int32, device=dev)
+        ended = torch.zeros(m, dtype=torch.bool, device=dev)
+        mode = torch.zeros(m, dtype=torch.bool, device=dev)
+        w0 = torch.empty((m, 4), dtype=torch.int32, device=dev)
+        w = torch.empty((len(blocks), m, 4), dtype=torch.int32, device=dev)
+        for t in range(steps):
+            run = ~ended
+            mag = states.abs()
+            now = torch.where(mode, ~(mag > lea).any(dim=1), (mag < ent).all(dim=1))
+            switches = switches + (run & (now != mode)).to(torch.int32)
+            mode = torch.where(run, now, mode)
+            second = second + (run & mode).to(torch.int32)
+            act = torch.where(mode, dp2(states), dp(states))
+            dp._engine.random_words(seed, 0, m, t, 0, w0.data_ptr(), stream=st)
+            explore = ((w0[:, 0] >> 8) & 0xFFFFFF) < eps24
+            index = ((w0[:, 1].to(torch.int64) & 0xFFFFFFFF) * n_act) >> 32
+            act = torch.where(explore, d_acts[index], act)
+            push = amp * sym(w0[:, 2])
+            act = torch.fmin(torch.fmax(act + push, a_lo), a_hi).contiguous()
+            eng.probe_step(states.data_ptr(), act.data_ptr(), nxt.data_ptr(), rew.data_ptr(), done.data_ptr(), m, st)
+            for k, j in enumerate(blocks):
+                dp._engine.random_words(seed, 0, m, t, j, w[k].data_ptr(), stream=st)
+            words = torch.cat(list(w), dim=1)[:, :D]
+            push = d_noise * sym(words)
+            nxt2 = torch.where((done == 0)[:, None], nxt + push, nxt)
+            ret = torch.where(run, ret + rew, ret)
+            states = torch.where(run[:, None], nxt2, states)
+            length = torch.where(run, torch.full_like(length, t + 1), length)
+            ended = ended | (run & (done != 0))
+        return B.StochasticHybridRolloutResult(states, ret, length, ended, None, second, mode.to(torch.uint8), switches)
+
+    def timed(fn, calls=1):                               # ms per call of `calls` back to back, one synchronise at the end
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record()
+        for _ in range(calls):
+            out = fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / calls, out
+
+    def fused():
+        return hp.rollout(starts, steps, **noisy)
+
+    def plain():                                          # the deterministic hybrid rollout of the same batch
+        return hp.rollout(starts, steps)
+
+    def single():                                         # the single-policy stochastic rollout of the same batch
+        return dp.rollout(starts, steps, **noisy)
+    a, b = fused(), loop()                                # warm-up of all paths, and: same results
+    p, s = plain(), single()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(a.states.view(torch.int32), b.states.view(torch.int32)) and torch.equal(a.lengths, b.lengths)
+                and torch.equal(a.returns.view(torch.int32), b.returns.view(torch.int32))
+                and torch.equal(a.secondary_steps, b.secondary_steps) and torch.equal(a.last_mode, b.last_mode)
+                and torch.equal(a.switches, b.switches))
+    t_fused, t_loop, t_plain, t_single = [], [], [], []
+    for _ in range(args.repeat):                          # alternating, so that drift hits all alike
+        t_fused.append(timed(fused, FUSED_PER_SAMPLE)[0])
+        t_loop.append(timed(loop)[0])
+        t_plain.append(timed(plain, FUSED_PER_SAMPLE)[0])
+        t_single.append(timed(single, FUSED_PER_SAMPLE)[0])
+    print(json.dumps({"config": args.config, "pair": f"{env} {bins}^{D} + {env2} {bins2}^{D}", "D": D, "m": m, "steps": steps,
+                      "same_bits": same, "fused_ms": min(t_fused), "loop_ms": min(t_loop), "plain_ms": min(t_plain),
+                      "single_ms": min(t_single), "fused_ms_all": t_fused, "loop_ms_all": t_loop,
+                      "episode_steps": int(a.lengths.sum().item()), "plain_episode_steps": int(p.lengths.sum().item()),
+                      "single_episode_steps": int(s.lengths.sum().item()),
+                      "secondary_steps": int(a.secondary_steps.sum().item()), "switches": int(a.switches.sum().item()),
+                      "terminated_share": float(a.terminated.float().mean().item()),
+                      "launches_loop": (4 + len(blocks)) * steps}))
+    dp.close()
+    dp2.close()
+    eng.close()
+
+
+def hybrid_usage(config, stochastic):
+    """VGPRs and scratch bytes per lane of the hybrid kernel (`stochastic`: of the stochastic hybrid kernel) for a pair of
+    HYBRID_PAIRS: the translation unit pi_infer_set_partner (pi_infer_set_partner_stochastic) hands to hipRTC, built ahead
+    of time with the same flags."""
+    import tempfile
+    import numpy as np
+    from __graft_entry__ import HIPCC
+    from dynamicprogramming_amd import envs
+    env, bins, env2, bins2, _, _ = HYBRID_PAIRS[config]
+
+    def braces(v, fmt):
+        return "{" + ",".join(fmt(x) for x in v) + "}"
+
+    def hexf(x):
+        return float(np.float32(x)).hex() + "f"
+
+    def grid_defines(prefix, e, g):
+        _, (lo, hi, shape, strides, bits) = _grid_tables(e, g)
+        return (f"#define {prefix}_D {len(lo)}\n#define {prefix}_LO_INIT {braces(lo, hexf)}\n"
+                f"#define {prefix}_HI_INIT {braces(hi, hexf)}\n#define {prefix}_SHAPE_INIT {braces(shape, str)}\n"
+                f"#define {prefix}_STRIDES_INIT {braces(strides, str)}\n"
+                f"#define {prefix}_BITS_INIT {braces(bits, lambda r: braces(r, str))}\n")
+    csrc = ROOT / "dynamicprogramming_amd" / "csrc"
+    defines = "#define PI_HYBRID_STOCHASTIC 1\n#define PI_HYBRID 1\n#define PI_STOCHASTIC 1\n" if stochastic else "#define PI_HYBRID 1\n"
+    files = ["pi_rollout_kernels.hip", "pi_hybrid_kernels.hip"] + (
+        ["pi_stochastic_kernels.hip", "pi_hybrid_stochastic_kernels.hip"] if stochastic else [])
+    text = (defines + grid_defines("PI", env, bins) + grid_defines("PI2", env2, bins2) +
+            f"{(ROOT / 'include' / 'pi_math.h').read_text()}\n#define sinf pi_sinf\n#define cosf pi_cosf\n#define fmodf pi_fmodf\n"
+            f"{envs.dynamics_source(env)}\n" + "".join((csrc / f).read_text() + "\n" for f in files))
+    usage, fn = {}, None
+    with tempfile.TemporaryDirectory(prefix="pi_hybrid_") as tmp:
+        src = Path(tmp) / "hybrid.hip"
+        src.write_text(text)
+        res = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "--genco",
+                              "-include", "hip/hip_runtime.h", "-Rpass-analysis=kernel-resource-usage", str(src), "-o",
+                              str(Path(tmp) / "hybrid.hsaco")], capture_output=True, text=True)
+    if res.returncode != 0:
+        sys.exit(f"hipcc failed on the hybrid translation unit of {config}\n{res.stderr[-2000:]}")
+    for line in res.stderr.splitlines():
+        if "Function Name:" in line:
+            fn = line.split("Function Name:")[1].split()[0]
+            usage[fn] = {}
+        elif fn and " VGPRs:" in line:
+            usage[fn]["vgpr"] = int(line.split("VGPRs:")[1].split()[0])
+        elif fn and "ScratchSize" in line:
+            usage[fn]["scratch"] = int(line.split(":")[-1].split()[0])
+    return usage
+
+
+def hybrid_stochastic_driver(args):
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    me = [sys.executable, str(Path(__file__).resolve())]
+    rows = []
+    for config in HYBRID_PAIRS:
+        res = subprocess.run(["timeout", "-k", "10", str(CHILD_SECONDS), *me, "--child", "--hybrid", "--stochastic", "--config",
+                              config, "--m", str(args.m), "--steps", str(args.steps), "--repeat", str(args.repeat)],
+                             capture_output=True, text=True)
+        if res.returncode != 0:                           # a fault, an abort or a time limit: nothing more runs
+            sys.exit(f"stochastic hybrid {config} ended with status {res.returncode}; stopping\n{res.stdout[-2000:]}\n{res.stderr[-2000:]}")
+        rows.append(json.loads(res.stdout.strip().splitlines()[-1]))
+        print(rows[-1], flush=True)
+    lines = [f"stochastic hybrid rollouts (two policies, Philox4x32-10 in the kernel) vs the step-by-step loop, MI355X, commit {args.commit}",
+             f"{args.m} episodes of {args.steps} steps, seeded random policies on both grids, epsilon 0.3, action noise a tenth of the "
+             "action range, state noise 0.2 % of the span in every dimension, the primary's actions as the exploration table, "
+             f"starts uniform in the primary grid; times in ms per call: the better of {args.repeat} samples after one warm-up, "
+             f"device events around {FUSED_PER_SAMPLE} fused calls back to back (one call of the loop), the four paths alternating",
+             "loop: per step a query on each handle, the probe kernel's words, one plugin step and the mixing as torch ops; "
+             "hybrid: the deterministic hybrid rollout (pi_infer_rollout_hybrid) of the same batch; single: the single-policy "
+             "stochastic rollout (pi_infer_rollout_stochastic) of the same batch; ep-steps: steps actually taken (episodes that "
+             "ended stop), in the order fused / hybrid / single",
+             "",
+             f"{'pair':58s} {'fused':>8s} {'loop':>10s} {'loop/fused':>10s} {'hybrid':>8s} {'single':>8s} {'ep-steps':>28s} "
+             f"{'mode-1':>9s} {'switches':>9s} {'ended':>6s} {'same bits':>9s}"]
+    for r in rows:
+        steps3 = f"{r['episode_steps']} / {r['plain_episode_steps']} / {r['single_episode_steps']}"
+        lines.append(f"{r['config'] + ' ' + r['pair']:58s} {r['fused_ms']:8.3f} {r['loop_ms']:10.3f} {r['loop_ms'] / r['fused_ms']:10.1f} "
+                     f"{r['plain_ms']:8.3f} {r['single_ms']:8.3f} {steps3:>28s} {r['secondary_steps']:9d} {r['switches']:9d} "
+                     f"{r['terminated_share']:6.3f} {str(r['same_bits']):>9s}")
+    lines += ["", "all samples per config (ms per call): " + "; ".join(
+        f"{r['config']} fused {[round(t, 3) for t in r['fused_ms_all']]} loop {[round(t, 1) for t in r['loop_ms_all']]}" for r in rows)]
+    slower = [r["config"] for r in rows if r["fused_ms"] >= r["loop_ms"] or not r["same_bits"]]
+    lines += ["", "the fused kernel is faster than its own step-by-step loop, with the same bits, on every pair" if not slower else
+              f"the fused kernel is NOT faster than its own step-by-step loop with the same bits on: {', '.join(slower)}", "",
+              "registers and scratch (hipcc -Rpass-analysis=kernel-resource-usage, the translation units of "
+              "pi_infer_set_partner_stochastic and pi_infer_set_partner):"]
+    for config in HYBRID_PAIRS:
+        for stochastic in (True, False):
+            for fn, k in sorted(hybrid_usage(config, stochastic).items()):
+                lines.append(f"  {config} {fn:38s} VGPRs {k['vgpr']:4d}  scratch {k['scratch']} bytes/lane")
+    lines += ["", "closed loop of the reference pair (trained 6-D archives) under noise: not measured"]
+    out.write_text("\n".join(lines) + "\n")
+    print(out.read_text())
+
+
 def hybrid_driver(args):
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
@@ -850,7 +1099,9 @@ def main():
     ap.add_argument("--config", choices=list(CONFIGS), default="c3")
     ap.add_argument("--m", type=int, default=4096)
     args = ap.parse_args()
-    if args.greedy:
+    if args.hybrid and args.stochastic:
+        (hybrid_stochastic_child if args.child else hybrid_stochastic_driver)(args)
+    elif args.greedy:
         (greedy_child if args.child else greedy_driver)(args)
     elif args.stochastic:
         (stochastic_child if args.child else stochastic_driver)(args)

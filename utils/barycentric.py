@@ -58,6 +58,9 @@ RolloutResult = namedtuple("RolloutResult", "states returns lengths terminated t
 # secondary_steps (m) int32 = steps taken on the secondary policy, last_mode (m) uint8 = the mode (0 primary, 1 secondary)
 # of the last step taken, 0 for an episode of length 0.
 HybridRolloutResult = namedtuple("HybridRolloutResult", RolloutResult._fields + ("secondary_steps", "last_mode"))
+# ... and one that does so under noise (``HybridPolicy.rollout(epsilon=..., ...)``, ``stochastic_hybrid_rollout``): the same
+# fields plus switches (m) int32 = the steps whose mode differs from that of the step taken before (mode 0 before step 0).
+StochasticHybridRolloutResult = namedtuple("StochasticHybridRolloutResult", HybridRolloutResult._fields + ("switches",))
 
 
 class DevicePolicy:
@@ -404,30 +407,63 @@ class HybridPolicy:
             raise ValueError(f"enter and leave must hold {primary.D} thresholds each")
         self._built_for = None                     # the primary's set_dynamics call the hybrid module was built after
 
-    def rollout(self, states, steps, gamma=1.0, record_every=0):
+    def rollout(self, states, steps, gamma=1.0, record_every=0, *, epsilon=None, action_noise=None, state_noise=None,
+                seed=None, first_episode=None, action_space=None):
         """Closed-loop episodes from ``states`` (m, D) in ONE kernel launch, in/out conventions of ``DevicePolicy.rollout``;
         returns a ``HybridRolloutResult``.  The hybrid kernel is built on first use and again after a new
-        ``primary.set_dynamics``."""
+        ``primary.set_dynamics``.
+        With any of the keywords given (the others default to 0) the episodes run in a noisy world — the device twin of
+        ``stochastic_hybrid_rollout``, same bits: ``epsilon``, ``action_noise``, ``state_noise``, ``seed`` and
+        ``first_episode`` mean what they mean in ``DevicePolicy.rollout`` and draw from the same counters, so the pair and
+        a single policy are compared under common random numbers.  The mode rule sees the disturbed state and is applied
+        on every step, exploring or not.  An exploring step takes its action from ``action_space``, ONE table for the pair
+        (default: the primary's), whose extremes clamp a noisy action.  Returns a ``StochasticHybridRolloutResult``: the
+        same fields plus ``switches``, how often each episode changed its mode.  That kernel is built on first use, and
+        again after a new ``primary.set_dynamics`` or for another ``action_space``."""
         a, b = self.primary, self.secondary
         if not b._has_policy:
             raise RuntimeError("the secondary DevicePolicy was built without a policy table")
+        noisy = any(v is not None for v in (epsilon, action_noise, state_noise, seed, first_episode, action_space))
+        if noisy:
+            epsilon = 0.0 if epsilon is None else epsilon
+            explore_threshold(epsilon)              # raises outside [0, 1]
+            a_noise = float(_checked_action_noise(0.0 if action_noise is None else action_noise))
+            s_noise = _noise_vector(state_noise, a.D)
+            table = a._action_space if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+            if table is None:
+                raise ValueError("a stochastic hybrid rollout needs an exploration table: give action_space")
         on_device, d_start, m, steps, every, final, ret, length, term, traj = a._rollout_buffers(states, steps, record_every)
-        if self._built_for != a._dynamics_serial:
-            a._engine.set_partner(b._engine)
-            self._built_for = a._dynamics_serial
         torch = a._torch
         second = torch.empty(m, dtype=torch.int32, device=a.device)
         mode = torch.empty(m, dtype=torch.uint8, device=a.device)
-        a._engine.rollout_hybrid(b._engine, d_start.data_ptr(), m, steps, self.enter, self.leave, gamma,
-                                 d_final=final.data_ptr(), d_return=ret.data_ptr(), d_length=length.data_ptr(),
-                                 d_terminated=term.data_ptr(), d_secondary_steps=second.data_ptr(),
-                                 d_last_mode=mode.data_ptr(), d_traj=traj.data_ptr() if every else 0, traj_every=every,
-                                 stream=a._stream())
-        term = term != 0
+        outs = dict(d_final=final.data_ptr(), d_return=ret.data_ptr(), d_length=length.data_ptr(),
+                    d_terminated=term.data_ptr(), d_secondary_steps=second.data_ptr(), d_last_mode=mode.data_ptr(),
+                    d_traj=traj.data_ptr() if every else 0, traj_every=every, stream=a._stream())
+        extra = ()
+        if noisy:
+            # the module lives on the primary's handle, and so does the note of what it was built for: HybridPolicy
+            # objects that share a primary replace each other's module
+            built = getattr(a, "_partner_stochastic", None)
+            if built is None or built[0] != a._dynamics_serial or built[1] is not b or not np.array_equal(built[2], table):
+                a._engine.set_partner_stochastic(b._engine, table)
+                a._partner_stochastic = (a._dynamics_serial, b, table.copy())
+            switches = torch.empty(m, dtype=torch.int32, device=a.device)
+            a._engine.rollout_hybrid_stochastic(b._engine, d_start.data_ptr(), m, steps, self.enter, self.leave, gamma,
+                                                epsilon=epsilon, action_noise=a_noise, state_noise=s_noise,
+                                                seed=int(0 if seed is None else seed) & (2 ** 64 - 1),
+                                                first_episode=int(0 if first_episode is None else first_episode) & (2 ** 64 - 1),
+                                                d_switches=switches.data_ptr(), **outs)
+            extra = (switches,)
+        else:
+            if self._built_for != a._dynamics_serial:
+                a._engine.set_partner(b._engine)
+                self._built_for = a._dynamics_serial
+            a._engine.rollout_hybrid(b._engine, d_start.data_ptr(), m, steps, self.enter, self.leave, gamma, **outs)
+        result = StochasticHybridRolloutResult if noisy else HybridRolloutResult
+        fields = (final, ret, length, term != 0, traj, second, mode) + extra
         if on_device:
-            return HybridRolloutResult(final, ret, length, term, traj, second, mode)
-        return HybridRolloutResult(final.cpu().numpy(), ret.cpu().numpy(), length.cpu().numpy(), term.cpu().numpy(),
-                                   traj.cpu().numpy() if every else None, second.cpu().numpy(), mode.cpu().numpy())
+            return result(*fields)
+        return result(*(None if x is None else x.cpu().numpy() for x in fields))
 
 
 def get_barycentric_weights_and_indices(points, bounds_low, bounds_high, grid_shape, strides,
@@ -823,11 +859,43 @@ def stochastic_rollout(step, states, steps, policy, action_space, bounds_low, bo
                               first_episode, gamma, record_every)
 
 
+def stochastic_hybrid_rollout(step, states, steps, primary, secondary, enter, leave, action_space, epsilon, action_noise,
+                              state_noise, seed, first_episode=0, gamma=1.0, record_every=0):
+    """Closed-loop episodes that switch between two policies under epsilon-random actions, action noise and state noise,
+    on the CPU (numpy): the twin of ``HybridPolicy.rollout(epsilon=..., action_noise=..., state_noise=..., seed=...,
+    first_episode=..., action_space=...)``, same bits.  ``hybrid_rollout`` inside the loop of ``stochastic_rollout``: per
+    step of a running episode ``switch_mode`` on the state the step starts from — disturbed or not, exploring or not —,
+    ``secondary_steps`` counts the steps in mode 1 and ``switches`` those whose mode differs from that of the step taken
+    before (mode 0 before step 0); an exploring step takes its action from ``action_space``, the ONE exploration table of
+    the pair, any other the interpolated action of the mode's policy on its own grid; action noise (clamped to the
+    extremes of ``action_space``), ``step`` and state noise as in ``stochastic_rollout``, from the same words.  Returns a
+    ``StochasticHybridRolloutResult``."""
+    m = len(np.atleast_2d(states))
+    mode = np.zeros(m, bool)
+    second = np.zeros(m, np.int32)
+    switches = np.zeros(m, np.int32)
+
+    def controller(pts, wanted, live):
+        now = switch_mode(mode[live], pts, enter, leave)
+        switches[live] += now != mode[live]
+        mode[live] = now
+        second[live] += now
+        a = np.zeros(len(live), np.float32)
+        for which, tables in ((~now & wanted, primary), (now & wanted, secondary)):
+            if which.any():
+                a[which] = _interpolated_actions(pts[which], *tables)
+        return a
+    res = _noisy_closed_loop(step, states, steps, controller, action_space, epsilon, action_noise, state_noise, seed,
+                             first_episode, gamma, record_every, with_live=True)
+    return StochasticHybridRolloutResult(*res, second, mode.astype(np.uint8), switches)
+
+
 def _noisy_closed_loop(step, states, steps, controller, action_space, epsilon, action_noise, state_noise, seed,
-                       first_episode, gamma, record_every):
+                       first_episode, gamma, record_every, with_live=False):
     """The loop ``stochastic_rollout`` documents, for any controller: ``controller(states (k, D), wanted (k,) bool) ->
     actions (k,) float32`` is asked for the running episodes; only the entries where ``wanted`` (the episode does not
-    explore this step) are used.  Returns a ``RolloutResult``."""
+    explore this step) are used.  ``with_live``: the controller keeps state per episode and is handed the indices of the
+    running episodes as a third argument.  Returns a ``RolloutResult``."""
     acts = np.ascontiguousarray(action_space, dtype=np.float32).ravel()
     if len(acts) < 1 or not np.isfinite(acts).all():
         raise ValueError("action_space needs at least one action, all finite")
@@ -843,7 +911,7 @@ def _noisy_closed_loop(step, states, steps, controller, action_space, epsilon, a
         now["episodes"] = _episode_numbers(first_episode, live)
         w = _episode_words(seed, now["episodes"], now["t"], 0)
         explore = (w[:, 0] >> np.uint32(8)) < eps24
-        a = np.asarray(controller(pts, ~explore), np.float32)
+        a = np.asarray(controller(pts, ~explore, live) if with_live else controller(pts, ~explore), np.float32)
         a = np.where(explore, acts[random_action_index(w[:, 1], len(acts))], a).astype(np.float32)
         if a_noise != 0:
             with np.errstate(invalid="ignore"):
