@@ -36,10 +36,10 @@
 //
 // Resource usage from the code objects (hipcc --offload-arch=gfx950 -O3, kernel-resource-usage;
 // tests/test_hybrid_stochastic_host.py asserts the scratch): no scratch in any D.  VGPRs of
-// pi_hybrid_stochastic_rollout_kernel: 68 at pendulum 200^2 + 50^2, 100 at cartpole swing-up 50^4 + 30^4 and 256 at
-// double cart-pole swing-up 25^6 + double cart-pole 25^6 — against 56 / 82 / 224 of pi_hybrid_rollout_kernel on the same
+// pi_hybrid_stochastic_rollout_kernel: 70 at pendulum 200^2 + 50^2, 102 at cartpole swing-up 50^4 + 30^4 and 256 at
+// double cart-pole swing-up 25^6 + double cart-pole 25^6 — against 58 / 82 / 226 of pi_hybrid_rollout_kernel on the same
 // pairs.  The 6-D figure is pi_rollout_action's 64 weights and 64 indices, as in the other 6-D rollouts (the
-// single-policy stochastic kernel holds 250 to 256 there); 256 is the most two waves per SIMD allow, which is what every
+// single-policy stochastic kernel holds 253 to 256 there); 256 is the most two waves per SIMD allow, which is what every
 // 6-D rollout of the handle runs at, so the kernel fits that budget exactly and has nothing to spare in it.
 
 #ifndef PI_HYBRID_STOCHASTIC

@@ -8,7 +8,19 @@
 // corner_bits, row-major) and hipRTC compiles it like the sweep kernels, with -ffp-contract=off.
 // The arithmetic is the helper's, type for type (numba's typing of the body):
 //   step  = float64(hi - lo [float32 subtraction]) / (shape - 1)
-//   p     = max(lo, min(point, hi))                            float32, the POINT is clamped
+//   p     = max(lo, min(point, hi))                            float32, the POINT is clamped; Python's min / max, i.e.
+//           m = (hi < x) ? hi : x;  p = (m > lo) ? m : lo      two selects on comparisons, NOT fminf / fmaxf:
+//             - a NaN coordinate fails both comparisons and lands on lo: cell 0, t = +0, finite weights (fminf would
+//               drop the NaN and send the point to hi);
+//             - +inf lands on hi, -inf on lo;
+//             - of two zeros of opposite sign (x = -0.0 with lo = +0.0, ...) the BOUND's zero is kept on the lo side and
+//               x's on the hi side, as the expression yields, so t and the weights carry the reference's zero signs;
+//             - every other input: the value fmaxf(lo, fminf(x, hi)) gives.
+//           The compiler lowers the second select to v_max_f32 (NaN behaviour the same), which orders -0 < +0 and so
+//           returns x's zero for lo = -0.0, x = +0.0; a third select, p = (p == lo) ? lo : p, restores the bound's
+//           zero.  It folds away for every bound that is not a zero (tests/golden/barycentric_edges.npz, grid z4).
+//           (Derived from the reference's text executed under CPython; numba's lowering of min / max is the same pair
+//           of comparisons as far as its source shows, but no numba run backs that.)
 //   cell  = float64(p - lo [float32 subtraction]) / step;  idx = int(cell), capped at shape - 2
 //   t     = float32((float64(p) - (float64(lo) + idx * step)) / step)
 //   w[c]  = float32(1.0 * prod_d (bit ? float64(t_d) : 1.0 - float64(t_d)))   in dimension order
@@ -77,7 +89,9 @@ pi_infer_kernel(const float* __restrict__ pts, long long m, const int* __restric
         const float l = PI_IG.lo[d], h = PI_IG.hi[d];
         const double step = (double)(h - l) / (double)(PI_IG.shape[d] - 1);
         const float x = pts[k * PI_D + d];
-        const float p = fmaxf(l, fminf(x, h));
+        const float mn = (h < x) ? h : x;               // two selects, not fminf / fmaxf: see "p" above
+        const float q = (mn > l) ? mn : l;
+        const float p = (q == l) ? l : q;               // the bound's zero: the compiler turns the select above into v_max_f32
         const double cell = (double)(p - l) / step;
         int i = (int)cell;
         if (i >= PI_IG.shape[d] - 1) i = PI_IG.shape[d] - 2;

@@ -14,7 +14,9 @@
 //      stages into LDS.  The 64-bit divisions are done once per workgroup, on its first position (wave-uniform); a
 //      thread adds its own 0 .. 255 with 32-bit arithmetic;
 //   2. weights and flat indices at the point x on the source grid: the arithmetic of pi_infer_kernel
-//      (pi_infer_kernels.hip) restated type for type — the point clamped to the source bounds, float64 cell widths,
+//      (pi_infer_kernels.hip) restated type for type — the point clamped to the source bounds by the reference's
+//      comparisons (a NaN node lands on lo, +-inf on the bounds, a zero at a zero lower bound takes the bound's sign),
+//      float64 cell widths,
 //      float64 weight products rounded once to float32, corners in the order of the caller's corner_bits;
 //   3. V = V + w[c] * Vsrc[flat[c]] in float32 from 0.0f over ASCENDING corners, multiply then add.  The corner loop is
 //      fully unrolled over the constant table: the 2^D source-value loads are in flight together;
@@ -74,7 +76,9 @@ __device__ __forceinline__ void pi_resample_body(const float* __restrict__ Vsrc,
         const float x = lds_bins[dst.offset[d] + (int)i_dst];
         const float l = PI_SG.lo[d], h = PI_SG.hi[d];
         const double step = (double)(h - l) / (double)(PI_SG.shape[d] - 1);
-        const float pt = fmaxf(l, fminf(x, h));
+        const float mn = (h < x) ? h : x;               // the reference's min / max as two selects: NaN -> lo, +-inf ->
+        const float q = (mn > l) ? mn : l;              // the bounds, opposite-sign zeros as in pi_infer_kernels.hip,
+        const float pt = (q == l) ? l : q;              // whose third select this is
         const double cell = (double)(pt - l) / step;
         int i = (int)cell;
         if (i >= PI_SG.shape[d] - 1) i = PI_SG.shape[d] - 2;

@@ -12,9 +12,10 @@
 // One lane per episode; the state stays in registers for all steps.  The episode loop (pi_rollout_episodes, below) is
 // shared by every fused rollout of the handle: a controller supplies step 1 and 2, the loop does the rest.  Per step
 //   1. the interpolated action, the arithmetic of pi_infer_kernel (pi_infer_kernels.hip) restated type for type:
-//      point clamped to the bounds, float64 cell widths, float64 weight products rounded once to float32, corners
-//      in the order of the caller's corner_bits, the action a float32 sum over ASCENDING corners, multiply then
-//      add.  The corner loop is fully unrolled: the 2^D policy look-ups of a step are in flight together and the
+//      point clamped to the bounds by the reference's comparisons (a NaN coordinate — step_dynamics is free to return
+//      one — lands on lo, +-inf on the bounds, a zero at a zero lower bound takes the bound's sign), float64 cell
+//      widths, float64 weight products rounded once to float32, corners in the order of the caller's corner_bits,
+//      the action a float32 sum over ASCENDING corners, multiply then add.  The corner loop is fully unrolled: the 2^D policy look-ups of a step are in flight together and the
 //      action values follow as a second independent batch (profiles/r03/inference.txt);
 //   2. step_dynamics with the arity for D;
 //   3. ret = ret + disc * r;  disc = disc * gamma      float32, separate multiply and add (gamma = 1: the plain sum);
@@ -62,7 +63,9 @@ __device__ __forceinline__ float pi_rollout_action(const G& g, const float (&s)[
     for (int d = 0; d < PI_D; ++d) {
         const float l = g.lo(d), h = g.hi(d);
         const double step = g.step(d);
-        const float p = fmaxf(l, fminf(s[d], h));
+        const float mn = (h < s[d]) ? h : s[d];         // the reference's min / max as two selects: NaN -> lo, +-inf ->
+        const float q = (mn > l) ? mn : l;              // the bounds, opposite-sign zeros as in pi_infer_kernels.hip,
+        const float p = (q == l) ? l : q;               // whose third select this is
         const double cell = (double)(p - l) / step;
         int i = (int)cell;
         if (i >= g.shape(d) - 1) i = g.shape(d) - 2;

@@ -40,10 +40,10 @@
 // everything at zero does the work of pi_rollout_kernel and returns its bits.
 //
 // Resource usage from the code objects (hipcc --offload-arch=gfx950 -O3, kernel-resource-usage; tests/test_stochastic_host.py
-// asserts the scratch): no scratch in any D; pi_random_words_kernel 9 VGPRs; pi_stochastic_rollout_kernel 48 VGPRs at
-// 200^2 (pendulum), 77 at 50^4 (cartpole swing-up), 250 at 25^6 (double cart-pole) and 256 at 25^6 (its swing-up) —
-// against 44 / 70 / 236 / 246 of pi_rollout_kernel on the same grids.  The 6-D figure is pi_rollout_action's: its fully
-// unrolled 64-corner look-up holds 64 weights and 64 indices, and this kernel adds 10 to 14 registers to it.  It is above
+// asserts the scratch): no scratch in any D; pi_random_words_kernel 9 VGPRs; pi_stochastic_rollout_kernel 50 VGPRs at
+// 200^2 (pendulum), 81 at 50^4 (cartpole swing-up), 253 at 25^6 (double cart-pole) and 256 at 25^6 (its swing-up) —
+// against 46 / 71 / 238 / 250 of pi_rollout_kernel on the same grids.  The 6-D figure is pi_rollout_action's: its fully
+// unrolled 64-corner look-up holds 64 weights and 64 indices, and this kernel adds 6 to 15 registers to it.  It is above
 // the greedy rollout's 136 (that kernel never calls pi_rollout_action); both 6-D rollouts run two waves per SIMD.
 
 #ifndef PI_STOCHASTIC

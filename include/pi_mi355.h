@@ -458,6 +458,13 @@ int pi_plan_schedule(pi_handle* h, int block, int64_t first, int64_t count, int6
  * to the bounds, weights = float64 products rounded once to float32, corners in the order of the
  * caller's corner_bits table — itertools.product, MSB first, in the reference :233).  Independent of
  * pi_handle: needs no env plugin.
+ * The clamp is the reference's max(lo, min(x, hi)) with Python's comparisons, m = (hi < x) ? hi : x; p = (m > lo) ? m : lo
+ * (from the reference's text run under CPython; numba is read, not run, to lower min / max the same way): a NaN
+ * coordinate lands on lo — cell 0, t = +0, finite weights —, +inf on hi, -inf on lo, and when x and lo are zeros of
+ * opposite sign p is lo's zero (at hi the sign of the point does not reach t).  Every other input gives the value of
+ * fmaxf(lo, fminf(x, hi)).  The query, the policy-table rollouts (pi_infer_rollout, _hybrid, _stochastic,
+ * _hybrid_stochastic) and pi_infer_resample share this clamp; the lookaheads (pi_infer_greedy, pi_infer_expect_greedy
+ * and their rollouts) interpolate as the sweeps do, where a NaN lands on the top border.
  *   pi_infer_create     host arrays; corner_bits is (n_corners = 2^D, D) int32 of 0/1; device = -1
  *                       builds the kernel only (compile check without a GPU); cache_dir as pi_compile.
  *                       The grid and the corner table are compiled INTO the kernel (hipRTC, one code

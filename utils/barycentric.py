@@ -466,6 +466,17 @@ class HybridPolicy:
         return result(*(None if x is None else x.cpu().numpy() for x in fields))
 
 
+def _clamp_point(pts, lo, hi):
+    """The reference's ``max(lo, min(x, hi))`` as Python's min / max compare — ``m = hi if hi < x else x``, ``p = m if
+    m > lo else lo`` — not ``np.maximum(lo, np.minimum(x, hi))``: a NaN coordinate fails both comparisons and lands on
+    ``lo`` (cell 0, t = +0, finite weights), +-inf lands on the bounds, and when ``x`` and a bound are zeros of opposite
+    sign the result is ``lo``'s zero on the low side and ``x``'s on the high side.  Every other input: the same value.
+    (CPython semantics, from the reference's text run in memory; that numba lowers min / max to the same comparisons is
+    read from its source, not from a numba run.)  The device kernels use the same two selects."""
+    m = np.where(hi < pts, hi, pts)
+    return np.where(m > lo, m, lo)
+
+
 def get_barycentric_weights_and_indices(points, bounds_low, bounds_high, grid_shape, strides,
                                         corner_bits, *, device=None):
     """
@@ -485,7 +496,7 @@ def get_barycentric_weights_and_indices(points, bounds_low, bounds_high, grid_sh
     st = np.asarray(strides).astype(np.int64)
     bits = np.asarray(corner_bits).astype(np.int64)           # (C, D)
     step = (hi - lo) / (shape - 1)                             # float64, like the reference
-    p = np.maximum(lo, np.minimum(pts, hi))                    # clamp the point
+    p = _clamp_point(pts, lo, hi)
     cell = (p - lo) / step
     idx = cell.astype(np.int64)                                # truncation, cell >= 0
     idx = np.where(idx >= shape - 1, shape - 2, idx)
