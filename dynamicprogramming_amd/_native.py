@@ -649,6 +649,62 @@ class InferenceEngine:
         self.device = int(device)
         self.n_corners = len(self._bits)
 
+    # -- marshalling: every group of C arguments that several entry points share is built here, once ----------------
+    def _build(self, name, *args, failed=None) -> str:
+        """pi_infer_<name>(h, *args, log, log_len), a call that builds a module: returns the compiler's log, raises
+        NativeError — "pi_infer_<name> failed:", or `failed` — with the library's message."""
+        log = ctypes.create_string_buffer(1 << 16)
+        rc = getattr(lib(), "pi_infer_" + name)(self._h, *args, log, len(log))
+        text = log.value.decode(errors="replace")
+        if rc != 0:
+            raise NativeError(f"{failed or f'pi_infer_{name} failed:'}\n{last_error()}")
+        return text
+
+    @staticmethod
+    def _table(action_space):
+        """(const float* action_space, int n_actions) of a host table of any shape; None travels as (NULL, 0)."""
+        if action_space is None:
+            return None, 0
+        act = np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        return act.ctypes.data_as(_f32p), len(act)          # the pointer keeps its array alive
+
+    def _vector(self, values, message):
+        """`const float*` of a host vector of D floats, NULL for None; ValueError(message, its {D} filled in) for another
+        shape."""
+        if values is None:
+            return None
+        v = np.ascontiguousarray(values, dtype=np.float32)
+        if v.shape != (self.D,):
+            raise ValueError(message.format(D=self.D))
+        return v.ctypes.data_as(_f32p)                      # the pointer keeps its array alive
+
+    def _thresholds(self, enter, leave):
+        """(const float* enter, const float* leave) of the hybrid rollouts."""
+        message = "enter and leave must hold {D} thresholds each"
+        return self._vector(enter, message), self._vector(leave, message)
+
+    def _noise(self, epsilon, action_noise, state_noise, seed, first_episode):
+        """(float epsilon, float action_noise, const float* state_noise, uint64 seed, uint64 first_episode) of the noisy
+        rollouts."""
+        return (float(epsilon), float(action_noise), self._vector(state_noise, "state_noise must hold {D} values"),
+                int(seed), int(first_episode))
+
+    def _rollout(self, name, handles, d_start, m, n_steps, gamma, middle, d_final, d_return, d_length, d_terminated, d_traj,
+                 traj_every, stream, *d_counts) -> None:
+        """One rollout launch, the arguments in the ABI's order: `handles`, the batch, `middle` (what only this rollout
+        takes), then the group every rollout ends with — the four per-episode outputs, the per-episode counts of the
+        hybrid rollouts (`d_counts`: secondary_steps, last_mode, switches), the trajectory, its period, the stream."""
+        _check(getattr(lib(), name)(*handles, d_start or None, int(m), int(n_steps), float(gamma), *middle, d_final or None,
+                                    d_return or None, d_length or None, d_terminated or None,
+                                    *[p or None for p in d_counts], d_traj or None, int(traj_every), stream or None), name)
+
+    def _pair(self, partner):
+        return self._h, partner._h if partner is not None else None
+
+    def _lookahead(self, name, d_points, m, gamma, d_best, d_action, d_q_best, d_q_all, stream) -> None:
+        _check(getattr(lib(), name)(self._h, d_points or None, int(m), float(gamma), d_best or None, d_action or None,
+                                    d_q_best or None, d_q_all or None, stream or None), name)
+
     def set_policy(self, policy, action_space) -> None:
         pol = np.ascontiguousarray(policy, dtype=np.int32)
         act = np.ascontiguousarray(action_space, dtype=np.float32)
@@ -663,59 +719,33 @@ class InferenceEngine:
     def set_dynamics(self, dynamics_src: str) -> str:
         """Build the rollout kernel for the env plugin `dynamics_src` on this handle's grid (a compile check on a
         host-only handle); returns the compiler's log.  Calling it again replaces the plugin."""
-        log = ctypes.create_string_buffer(1 << 16)
-        rc = lib().pi_infer_set_dynamics(self._h, dynamics_src.encode(), log, len(log))
-        text = log.value.decode(errors="replace")
-        if rc != 0:
-            raise NativeError(f"rollout kernel compilation failed:\n{last_error()}")
-        return text
+        return self._build("set_dynamics", dynamics_src.encode(), failed="rollout kernel compilation failed:")
 
     def rollout(self, d_start, m, n_steps, gamma=1.0, d_final=0, d_return=0, d_length=0, d_terminated=0, d_traj=0,
                 traj_every=0, stream=0) -> None:
         """m episodes of n_steps closed-loop steps in one launch (pi_infer_rollout; raw device pointers, asynchronous)."""
-        _check(lib().pi_infer_rollout(self._h, d_start or None, int(m), int(n_steps), float(gamma), d_final or None,
-                                      d_return or None, d_length or None, d_terminated or None, d_traj or None,
-                                      int(traj_every), stream or None), "pi_infer_rollout")
+        self._rollout("pi_infer_rollout", (self._h,), d_start, m, n_steps, gamma, (), d_final, d_return, d_length, d_terminated,
+                      d_traj, traj_every, stream)
 
     def set_partner(self, partner: "InferenceEngine") -> str:
         """Build this handle's hybrid module: its grid + `partner`'s grid + the plugin of the last set_dynamics + the hybrid
         rollout kernel (a compile check on host-only handles); returns the compiler's log."""
-        log = ctypes.create_string_buffer(1 << 16)
-        rc = lib().pi_infer_set_partner(self._h, partner._h, log, len(log))
-        text = log.value.decode(errors="replace")
-        if rc != 0:
-            raise NativeError(f"hybrid rollout kernel compilation failed:\n{last_error()}")
-        return text
+        return self._build("set_partner", partner._h, failed="hybrid rollout kernel compilation failed:")
 
     def rollout_hybrid(self, partner: "InferenceEngine", d_start, m, n_steps, enter, leave, gamma=1.0, d_final=0,
                        d_return=0, d_length=0, d_terminated=0, d_secondary_steps=0, d_last_mode=0, d_traj=0, traj_every=0,
                        stream=0) -> None:
         """m episodes of n_steps closed-loop steps that switch between this handle's policy and `partner`'s, in one launch
         (pi_infer_rollout_hybrid; raw device pointers, `enter` / `leave` host arrays of D thresholds; asynchronous)."""
-        box = [None if v is None else np.ascontiguousarray(v, dtype=np.float32) for v in (enter, leave)]
-        for v in box:
-            if v is not None and v.shape != (self.D,):
-                raise ValueError(f"enter and leave must hold {self.D} thresholds each")
-        ent, lea = (None if v is None else v.ctypes.data_as(_f32p) for v in box)
-        _check(lib().pi_infer_rollout_hybrid(self._h, partner._h if partner is not None else None, d_start or None, int(m),
-                                             int(n_steps), float(gamma), ent, lea, d_final or None, d_return or None,
-                                             d_length or None, d_terminated or None, d_secondary_steps or None,
-                                             d_last_mode or None, d_traj or None, int(traj_every), stream or None),
-               "pi_infer_rollout_hybrid")
+        self._rollout("pi_infer_rollout_hybrid", self._pair(partner), d_start, m, n_steps, gamma,
+                      self._thresholds(enter, leave), d_final, d_return, d_length, d_terminated, d_traj, traj_every, stream,
+                      d_secondary_steps, d_last_mode)
 
     def set_partner_stochastic(self, partner: "InferenceEngine", action_space) -> str:
         """Upload the pair's exploration table and build this handle's stochastic hybrid module: its grid + `partner`'s
         grid + the plugin of the last set_dynamics + the stochastic hybrid rollout kernel (a compile check on host-only
         handles); returns the compiler's log.  A later set_dynamics drops the module again."""
-        act = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
-        log = ctypes.create_string_buffer(1 << 16)
-        rc = lib().pi_infer_set_partner_stochastic(self._h, partner._h if partner is not None else None,
-                                                   None if act is None else act.ctypes.data_as(_f32p),
-                                                   0 if act is None else len(act), log, len(log))
-        text = log.value.decode(errors="replace")
-        if rc != 0:
-            raise NativeError(f"pi_infer_set_partner_stochastic failed:\n{last_error()}")
-        return text
+        return self._build("set_partner_stochastic", self._pair(partner)[1], *self._table(action_space))
 
     def rollout_hybrid_stochastic(self, partner: "InferenceEngine", d_start, m, n_steps, enter, leave, gamma=1.0, epsilon=0.0,
                                   action_noise=0.0, state_noise=None, seed=0, first_episode=0, d_final=0, d_return=0,
@@ -724,33 +754,16 @@ class InferenceEngine:
         """`rollout_hybrid` with the epsilon-random actions, action noise and state noise of `rollout_stochastic` from the
         same stream, in one launch (pi_infer_rollout_hybrid_stochastic; raw device pointers, `enter` / `leave` /
         `state_noise` host arrays of D floats; `d_switches` counts an episode's mode changes; asynchronous)."""
-        box = [None if v is None else np.ascontiguousarray(v, dtype=np.float32) for v in (enter, leave)]
-        for v in box:
-            if v is not None and v.shape != (self.D,):
-                raise ValueError(f"enter and leave must hold {self.D} thresholds each")
-        ent, lea = (None if v is None else v.ctypes.data_as(_f32p) for v in box)
-        noise = None
-        if state_noise is not None:
-            noise = np.ascontiguousarray(state_noise, dtype=np.float32)
-            if noise.shape != (self.D,):
-                raise ValueError(f"state_noise must hold {self.D} values")
-        _check(lib().pi_infer_rollout_hybrid_stochastic(
-            self._h, partner._h if partner is not None else None, d_start or None, int(m), int(n_steps), float(gamma), ent,
-            lea, float(epsilon), float(action_noise), None if noise is None else noise.ctypes.data_as(_f32p), int(seed),
-            int(first_episode), d_final or None, d_return or None, d_length or None, d_terminated or None,
-            d_secondary_steps or None, d_last_mode or None, d_switches or None, d_traj or None, int(traj_every),
-            stream or None), "pi_infer_rollout_hybrid_stochastic")
+        self._rollout("pi_infer_rollout_hybrid_stochastic", self._pair(partner), d_start, m, n_steps, gamma,
+                      (*self._thresholds(enter, leave), *self._noise(epsilon, action_noise, state_noise, seed, first_episode)),
+                      d_final, d_return, d_length, d_terminated, d_traj, traj_every, stream, d_secondary_steps, d_last_mode,
+                      d_switches)
 
     def set_values(self, values) -> str:
         """Upload the value function of this handle's grid (the user's order) and build the resample kernel (a compile
         check on a host-only handle); returns the compiler's log."""
         val = np.ascontiguousarray(values, dtype=np.float32).ravel()
-        log = ctypes.create_string_buffer(1 << 16)
-        rc = lib().pi_infer_set_values(self._h, val.ctypes.data_as(_f32p), len(val), log, len(log))
-        text = log.value.decode(errors="replace")
-        if rc != 0:
-            raise NativeError(f"pi_infer_set_values failed:\n{last_error()}")
-        return text
+        return self._build("set_values", val.ctypes.data_as(_f32p), len(val))
 
     def resample(self, dst_shape, dst_strides, dst_bins, d_term=0, d_values=0, d_policy=0, action_map=None, n_actions=0,
                  stream=0) -> None:
@@ -779,42 +792,25 @@ class InferenceEngine:
         """Upload the action table of the value-greedy controller and build the greedy kernels behind the plugin of the
         last set_dynamics (a compile check on a host-only handle); needs set_values and set_dynamics; returns the
         compiler's log.  A later set_dynamics drops the module again."""
-        act = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
-        log = ctypes.create_string_buffer(1 << 16)
-        rc = lib().pi_infer_set_greedy(self._h, None if act is None else act.ctypes.data_as(_f32p),
-                                       0 if act is None else len(act), log, len(log))
-        text = log.value.decode(errors="replace")
-        if rc != 0:
-            raise NativeError(f"pi_infer_set_greedy failed:\n{last_error()}")
-        return text
+        return self._build("set_greedy", *self._table(action_space))
 
     def greedy(self, d_points, m, gamma, d_best=0, d_action=0, d_q_best=0, d_q_all=0, stream=0) -> None:
         """The one-step lookahead on the value function at m query points in one launch (pi_infer_greedy; raw device
         pointers, asynchronous): greedy index, its action value, its Q and the (m, n_actions) matrix of all Q."""
-        _check(lib().pi_infer_greedy(self._h, d_points or None, int(m), float(gamma), d_best or None, d_action or None,
-                                     d_q_best or None, d_q_all or None, stream or None), "pi_infer_greedy")
+        self._lookahead("pi_infer_greedy", d_points, m, gamma, d_best, d_action, d_q_best, d_q_all, stream)
 
     def rollout_greedy(self, d_start, m, n_steps, lookahead_gamma, gamma=1.0, d_final=0, d_return=0, d_length=0,
                        d_terminated=0, d_traj=0, traj_every=0, stream=0) -> None:
         """m episodes of n_steps closed-loop steps under the value-greedy controller in one launch
         (pi_infer_rollout_greedy; raw device pointers, asynchronous)."""
-        _check(lib().pi_infer_rollout_greedy(self._h, d_start or None, int(m), int(n_steps), float(gamma),
-                                             float(lookahead_gamma), d_final or None, d_return or None, d_length or None,
-                                             d_terminated or None, d_traj or None, int(traj_every), stream or None),
-               "pi_infer_rollout_greedy")
+        self._rollout("pi_infer_rollout_greedy", (self._h,), d_start, m, n_steps, gamma, (float(lookahead_gamma),), d_final,
+                      d_return, d_length, d_terminated, d_traj, traj_every, stream)
 
     def set_stochastic(self, action_space) -> str:
         """Upload the action table exploring steps draw from and build the stochastic rollout kernels behind the plugin
         of the last set_dynamics (a compile check on a host-only handle); needs set_dynamics, neither a policy nor
         values; returns the compiler's log.  A later set_dynamics drops the module again."""
-        act = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
-        log = ctypes.create_string_buffer(1 << 16)
-        rc = lib().pi_infer_set_stochastic(self._h, None if act is None else act.ctypes.data_as(_f32p),
-                                           0 if act is None else len(act), log, len(log))
-        text = log.value.decode(errors="replace")
-        if rc != 0:
-            raise NativeError(f"pi_infer_set_stochastic failed:\n{last_error()}")
-        return text
+        return self._build("set_stochastic", *self._table(action_space))
 
     def rollout_stochastic(self, d_start, m, n_steps, gamma=1.0, epsilon=0.0, action_noise=0.0, state_noise=None, seed=0,
                            first_episode=0, d_final=0, d_return=0, d_length=0, d_terminated=0, d_traj=0, traj_every=0,
@@ -822,16 +818,9 @@ class InferenceEngine:
         """m episodes of n_steps closed-loop steps with epsilon-random actions, action noise and state noise from the
         counter-based stream (seed, first_episode + row, step), in one launch (pi_infer_rollout_stochastic; raw device
         pointers, `state_noise` a host array of D floats or None; asynchronous)."""
-        noise = None
-        if state_noise is not None:
-            noise = np.ascontiguousarray(state_noise, dtype=np.float32)
-            if noise.shape != (self.D,):
-                raise ValueError(f"state_noise must hold {self.D} values")
-        _check(lib().pi_infer_rollout_stochastic(self._h, d_start or None, int(m), int(n_steps), float(gamma), float(epsilon),
-                                                 float(action_noise), None if noise is None else noise.ctypes.data_as(_f32p),
-                                                 int(seed), int(first_episode), d_final or None, d_return or None,
-                                                 d_length or None, d_terminated or None, d_traj or None, int(traj_every),
-                                                 stream or None), "pi_infer_rollout_stochastic")
+        self._rollout("pi_infer_rollout_stochastic", (self._h,), d_start, m, n_steps, gamma,
+                      self._noise(epsilon, action_noise, state_noise, seed, first_episode), d_final, d_return, d_length,
+                      d_terminated, d_traj, traj_every, stream)
 
     def random_words(self, seed, first_episode, m, step, block, d_words, stream=0) -> None:
         """The four Philox words of (seed, first_episode + row, step, block) for rows 0 .. m into the (m, 4) uint32 device
@@ -843,14 +832,7 @@ class InferenceEngine:
         """Upload the action table of the expected-value greedy controller and build its kernels behind the plugin of the
         last set_dynamics (a compile check on a host-only handle); needs set_values and set_dynamics; returns the
         compiler's log.  A later set_dynamics drops the module again."""
-        act = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
-        log = ctypes.create_string_buffer(1 << 16)
-        rc = lib().pi_infer_set_expect_greedy(self._h, None if act is None else act.ctypes.data_as(_f32p),
-                                              0 if act is None else len(act), log, len(log))
-        text = log.value.decode(errors="replace")
-        if rc != 0:
-            raise NativeError(f"pi_infer_set_expect_greedy failed:\n{last_error()}")
-        return text
+        return self._build("set_expect_greedy", *self._table(action_space))
 
     def set_disturbances(self, action_offsets, state_offsets, weights) -> int:
         """The disturbance set the expected-value greedy controller takes its expectation over
@@ -874,9 +856,7 @@ class InferenceEngine:
     def expect_greedy(self, d_points, m, gamma, d_best=0, d_action=0, d_q_best=0, d_q_all=0, stream=0) -> None:
         """The one-step lookahead with the expectation over the disturbance set at m query points in one launch
         (pi_infer_expect_greedy; raw device pointers, asynchronous): the outputs of `greedy`."""
-        _check(lib().pi_infer_expect_greedy(self._h, d_points or None, int(m), float(gamma), d_best or None,
-                                            d_action or None, d_q_best or None, d_q_all or None, stream or None),
-               "pi_infer_expect_greedy")
+        self._lookahead("pi_infer_expect_greedy", d_points, m, gamma, d_best, d_action, d_q_best, d_q_all, stream)
 
     def rollout_expect_greedy(self, d_start, m, n_steps, lookahead_gamma, gamma=1.0, epsilon=0.0, action_noise=0.0,
                               state_noise=None, seed=0, first_episode=0, d_final=0, d_return=0, d_length=0, d_terminated=0,
@@ -885,17 +865,9 @@ class InferenceEngine:
         actions, action noise and state noise of `rollout_stochastic` from the same stream, in one launch
         (pi_infer_rollout_expect_greedy; raw device pointers, `state_noise` a host array of D floats or None;
         asynchronous)."""
-        noise = None
-        if state_noise is not None:
-            noise = np.ascontiguousarray(state_noise, dtype=np.float32)
-            if noise.shape != (self.D,):
-                raise ValueError(f"state_noise must hold {self.D} values")
-        _check(lib().pi_infer_rollout_expect_greedy(self._h, d_start or None, int(m), int(n_steps), float(gamma),
-                                                    float(lookahead_gamma), float(epsilon), float(action_noise),
-                                                    None if noise is None else noise.ctypes.data_as(_f32p), int(seed),
-                                                    int(first_episode), d_final or None, d_return or None, d_length or None,
-                                                    d_terminated or None, d_traj or None, int(traj_every), stream or None),
-               "pi_infer_rollout_expect_greedy")
+        self._rollout("pi_infer_rollout_expect_greedy", (self._h,), d_start, m, n_steps, gamma,
+                      (float(lookahead_gamma), *self._noise(epsilon, action_noise, state_noise, seed, first_episode)),
+                      d_final, d_return, d_length, d_terminated, d_traj, traj_every, stream)
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -1062,9 +1062,8 @@ class _CudaPolicyIterationBase(abc.ABC):
         DevicePolicy.rollout documents them) — epsilon-random actions from this solver's action table, action noise and
         state noise from a stream that depends on (seed, first_episode + row, step) only.  controller="random" is the
         random-policy baseline (epsilon = 1): it reads no table, so it also works on an instance that has never run."""
-        from utils.barycentric import DevicePolicy
-        if controller not in ("policy", "greedy", "random", "expected"):
-            raise ValueError(f"controller must be 'policy', 'greedy', 'random' or 'expected', not {controller!r}")
+        from utils.barycentric import DevicePolicy, check_controller, is_stochastic, refuse_noisy_greedy
+        check_controller(controller)
         greedy = controller == "greedy"
         expected = controller == "expected"
         if disturbances is not None and not expected:
@@ -1075,11 +1074,8 @@ class _CudaPolicyIterationBase(abc.ABC):
                 raise RuntimeError("controller='expected' needs a disturbance set: pass disturbances=, or install one with "
                                    "set_disturbances (a load()ed archive carries the set it was solved with)")
         noisy = dict(epsilon=epsilon, action_noise=action_noise, state_noise=state_noise, seed=seed, first_episode=first_episode)
-        stochastic = controller == "random" or float(epsilon) != 0.0 or float(action_noise) != 0.0 or \
-            (state_noise is not None and bool(np.any(np.asarray(state_noise, dtype=np.float32) != 0)))
-        if greedy and stochastic:
-            raise ValueError("controller='greedy' takes no epsilon, action_noise or state_noise: a stochastic greedy "
-                             "controller does not exist")
+        stochastic = is_stochastic(controller, epsilon, action_noise, state_noise)      # DevicePolicy.rollout's own rule
+        refuse_noisy_greedy(controller, stochastic)
         no_policy = greedy or expected or controller == "random" or float(epsilon) == 1.0
         values = getattr(self, "value_function", None)
         if (greedy or expected) and values is None and hasattr(self, "d_value_function") and self._comm is None:

@@ -63,6 +63,51 @@ HybridRolloutResult = namedtuple("HybridRolloutResult", RolloutResult._fields + 
 StochasticHybridRolloutResult = namedtuple("StochasticHybridRolloutResult", HybridRolloutResult._fields + ("switches",))
 
 
+def check_controller(controller) -> None:
+    if controller not in ("policy", "greedy", "random", "expected"):
+        raise ValueError(f"controller must be 'policy', 'greedy', 'random' or 'expected', not {controller!r}")
+
+
+def is_stochastic(controller, epsilon=0.0, action_noise=0.0, state_noise=None) -> bool:
+    """Whether a rollout with these arguments runs a stochastic kernel: the random controller, or an epsilon, an action
+    noise or a state noise that is not zero — the noises as the float32 values the kernel is given.  It judges, it does
+    not check: a value out of range counts as noise and is refused where the keywords are parsed."""
+    return controller == "random" or float(epsilon) != 0.0 or (action_noise != 0 and np.float32(action_noise) != 0) or \
+        (state_noise is not None and bool(np.asarray(state_noise, dtype=np.float32).any()))
+
+
+def refuse_noisy_greedy(controller, stochastic) -> None:
+    if controller == "greedy" and stochastic:
+        raise ValueError("controller='greedy' takes no epsilon, action_noise or state_noise: a stochastic greedy "
+                         "controller does not exist")
+
+
+def _u64(x) -> int:
+    """A seed or an episode number as the uint64 the kernels count in (wrapping at 2^64)."""
+    return int(x) & (2 ** 64 - 1)
+
+
+def _table(action_space, default=None):
+    """An action table as flat float32; None: `default`."""
+    return default if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+
+
+def _noise_keywords(policy, epsilon, action_noise, state_noise) -> dict:
+    """The noise keywords of a ``rollout``, checked in this order, as the keywords the engine's noisy rollouts take;
+    ``state_noise`` None stays None (no vector, and ``policy.D`` is not read)."""
+    explore_threshold(epsilon)                      # raises outside [0, 1]
+    a_noise = float(_checked_action_noise(action_noise))
+    s_noise = None if state_noise is None else _noise_vector(state_noise, policy.D)
+    return dict(epsilon=epsilon, action_noise=a_noise, state_noise=s_noise)
+
+
+def _result(kind, on_device, fields):
+    """The output tensors of a rollout (``terminated``, the fourth, still uint8) as the result namedtuple `kind`: as they
+    are for a caller that gave device states, numpy otherwise."""
+    fields[3] = fields[3] != 0
+    return kind(*fields) if on_device else kind(*(None if x is None else x.cpu().numpy() for x in fields))
+
+
 class DevicePolicy:
     """A trained policy resident on the GPU for batched queries: ``DevicePolicy(policy, action_space,
     bounds_low, bounds_high, grid_shape, strides, corner_bits, device="cuda:0")``; calling it with
@@ -70,6 +115,16 @@ class DevicePolicy:
     returns what ``get_barycentric_weights_and_indices`` returns.  ``policy`` may be None when only
     weights and indices, or the value-greedy controller (``set_values``, ``set_dynamics``, ``set_greedy``: it acts on
     the value function and ``action_space``), are wanted.  Raises if the native library or a GPU is missing (no fallback)."""
+
+    # what the setters below record, at its value before any of them was called
+    _has_dynamics = False                      # set_dynamics was called
+    _has_values = False                        # set_values was called
+    _dynamics_serial = 0                       # the number of set_dynamics calls: HybridPolicy rebuilds its modules after one
+    _greedy_actions = None                     # the table of the last set_greedy; None: no greedy module
+    _stochastic_actions = None                 # the table of the last set_stochastic; None: no stochastic module
+    _expected_actions = None                   # the table of the last set_expected_greedy; None: no such module
+    _disturbances = None                       # the set of the last set_disturbances
+    _partner_stochastic = None                 # (serial, secondary, table) HybridPolicy built this handle's noisy module for
 
     def __init__(self, policy, action_space, bounds_low, bounds_high, grid_shape, strides, corner_bits,
                  device="cuda:0"):
@@ -86,11 +141,7 @@ class DevicePolicy:
         self._has_policy = policy is not None
         self._n_actions = 0
         # the action table on its own: the value-greedy controller needs no policy (set_greedy)
-        self._action_space = None if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
-        self._greedy_actions = None                # the table of the last set_greedy; None: no greedy module
-        self._stochastic_actions = None            # the table of the last set_stochastic; None: no stochastic module
-        self._expected_actions = None              # the table of the last set_expected_greedy; None: no such module
-        self._disturbances = None                  # the set of the last set_disturbances
+        self._action_space = _table(action_space)
         if self._has_policy:
             self._engine.set_policy(policy, action_space)
             self._n_actions = len(np.asarray(action_space))
@@ -100,6 +151,15 @@ class DevicePolicy:
         assert pts.shape[1] == self.D, f"states must be (m, {self.D})"
         return self._torch.from_numpy(pts).to(self.device), len(pts)
 
+    def _device_states(self, states):
+        """(on_device, float32 (m, D) tensor on this device, m) of states given as numpy or as such a tensor."""
+        if not self._torch.is_tensor(states):
+            return (False, *self._points(states))
+        if states.device != self.device or states.dtype != self._torch.float32 or states.dim() != 2 \
+                or states.shape[1] != self.D:
+            raise ValueError(f"device states must be a float32 (m, {self.D}) tensor on {self.device}")
+        return True, states.contiguous(), states.shape[0]
+
     def _stream(self):
         return self._torch.cuda.current_stream(self.device).cuda_stream
 
@@ -108,14 +168,7 @@ class DevicePolicy:
         device -> a torch tensor on the device (no host round trip: closed-loop rollouts on the GPU)."""
         if not self._has_policy:
             raise RuntimeError("this DevicePolicy was built without a policy table")
-        on_device = self._torch.is_tensor(states)
-        if on_device:
-            if states.device != self.device or states.dtype != self._torch.float32 or states.dim() != 2 \
-                    or states.shape[1] != self.D:
-                raise ValueError(f"device states must be a float32 (m, {self.D}) tensor on {self.device}")
-            d_pts, m = states.contiguous(), states.shape[0]
-        else:
-            d_pts, m = self._points(states)
+        on_device, d_pts, m = self._device_states(states)
         out = self._torch.empty(m, dtype=self._torch.float32, device=self.device)
         self._engine.query(d_pts.data_ptr(), m, d_actions=out.data_ptr(), stream=self._stream())
         return out if on_device else out.cpu().numpy()
@@ -132,37 +185,33 @@ class DevicePolicy:
         through; returns the compiler's log.  Calling it again replaces the plugin."""
         log = self._engine.set_dynamics(dynamics_src)
         self._has_dynamics = True
-        self._dynamics_serial = getattr(self, "_dynamics_serial", 0) + 1      # HybridPolicy rebuilds its module after this
+        self._dynamics_serial += 1                                            # HybridPolicy rebuilds its module after this
         self._greedy_actions = None                                           # the library dropped the greedy module
         self._stochastic_actions = None                                       # ... and the stochastic one
         self._expected_actions = None                                         # ... and the expected-greedy one
         return log
 
     def _rollout_buffers(self, states, steps, record_every, need_policy=True):
-        """Checked arguments and the output tensors every rollout fills: (on_device, d_start, m, steps, every, final,
-        returns, lengths, terminated (uint8), trajectory or None)."""
+        """Checked arguments and the output tensors every rollout fills: (on_device, d_start, m, steps, [final, returns,
+        lengths, terminated (uint8), trajectory or None], the keywords that hand those to the engine's rollouts)."""
         torch = self._torch
         if need_policy and not self._has_policy:
             raise RuntimeError("this DevicePolicy was built without a policy table")
-        if not getattr(self, "_has_dynamics", False):
+        if not self._has_dynamics:
             raise RuntimeError("rollout needs the env's dynamics: call set_dynamics(dynamics_src) first")
         steps, every = int(steps), int(record_every)
         if steps < 0 or every < 0 or (steps > 0 and every > steps):
             raise ValueError("rollout needs steps >= 0 and 0 <= record_every <= steps")
-        on_device = torch.is_tensor(states)
-        if on_device:
-            if states.device != self.device or states.dtype != torch.float32 or states.dim() != 2 \
-                    or states.shape[1] != self.D:
-                raise ValueError(f"device states must be a float32 (m, {self.D}) tensor on {self.device}")
-            d_start, m = states.contiguous(), states.shape[0]
-        else:
-            d_start, m = self._points(states)
+        on_device, d_start, m = self._device_states(states)
         final = torch.empty((m, self.D), dtype=torch.float32, device=self.device)
         ret = torch.empty(m, dtype=torch.float32, device=self.device)
         length = torch.empty(m, dtype=torch.int32, device=self.device)
         term = torch.empty(m, dtype=torch.uint8, device=self.device)
         traj = torch.empty((steps // every + 1, m, self.D), dtype=torch.float32, device=self.device) if every else None
-        return on_device, d_start, m, steps, every, final, ret, length, term, traj
+        outs = dict(d_final=final.data_ptr(), d_return=ret.data_ptr(), d_length=length.data_ptr(),
+                    d_terminated=term.data_ptr(), d_traj=traj.data_ptr() if every else 0, traj_every=every,
+                    stream=self._stream())
+        return on_device, d_start, m, steps, [final, ret, length, term, traj], outs
 
     def rollout(self, states, steps, gamma=1.0, record_every=0, controller="policy", lookahead_gamma=None, *,
                 epsilon=0.0, action_noise=0.0, state_noise=None, seed=0, first_episode=0):
@@ -189,54 +238,37 @@ class DevicePolicy:
         the disturbance set inside it.  It accepts the five stochastic keywords, drawn from the same counters as the
         policy-table controller's (an exploring step takes its random action instead of the lookahead's), so the two can
         be compared under common random numbers; with ``Disturbances.none(D)`` it is the greedy lookahead under noise."""
-        if controller not in ("policy", "greedy", "random", "expected"):
-            raise ValueError(f"controller must be 'policy', 'greedy', 'random' or 'expected', not {controller!r}")
+        check_controller(controller)
         greedy = controller == "greedy"
         expected = controller == "expected"
         if controller == "random":
             if float(epsilon) not in (0.0, 1.0):
                 raise ValueError("controller='random' is epsilon = 1: give no other epsilon with it")
             epsilon = 1.0
-        explore_threshold(epsilon)                  # raises outside [0, 1]
-        a_noise = float(_checked_action_noise(action_noise))
-        s_noise = _noise_vector(state_noise, self.D) if state_noise is not None else None
-        stochastic = controller == "random" or float(epsilon) != 0.0 or a_noise != 0.0 or \
-            (s_noise is not None and bool(s_noise.any()))
-        if greedy and stochastic:
-            raise ValueError("controller='greedy' takes no epsilon, action_noise or state_noise: a stochastic greedy "
-                             "controller does not exist")
+        noise = _noise_keywords(self, epsilon, action_noise, state_noise)
+        stochastic = is_stochastic(controller, **noise)
+        refuse_noisy_greedy(controller, stochastic)
         if (greedy or expected) and lookahead_gamma is None:
             raise ValueError(f"controller={controller!r} needs lookahead_gamma, the discount the value function was solved with")
-        if expected and getattr(self, "_expected_actions", None) is None:
-            raise RuntimeError("the expected controller needs set_expected_greedy() (again after every set_dynamics)")
-        if expected and getattr(self, "_disturbances", None) is None:
-            raise RuntimeError("the expected controller needs a disturbance set: call set_disturbances(...) first")
-        if greedy and getattr(self, "_greedy_actions", None) is None:
-            raise RuntimeError("the greedy controller needs set_greedy() (again after every set_dynamics)")
-        if stochastic and not expected and getattr(self, "_stochastic_actions", None) is None:
-            raise RuntimeError("a stochastic rollout needs set_stochastic() (again after every set_dynamics)")
-        on_device, d_start, m, steps, every, final, ret, length, term, traj = \
+        if expected:
+            self._need_expected_greedy()
+        elif greedy:
+            self._need_greedy()
+        elif stochastic:
+            self._need_stochastic("a stochastic rollout")
+        on_device, d_start, m, steps, out, outs = \
             self._rollout_buffers(states, steps, record_every, need_policy=not greedy and not expected and float(epsilon) != 1.0)
-        outs = dict(d_final=final.data_ptr(), d_return=ret.data_ptr(), d_length=length.data_ptr(),
-                    d_terminated=term.data_ptr(), d_traj=traj.data_ptr() if every else 0, traj_every=every,
-                    stream=self._stream())
+        if expected or stochastic:
+            noise.update(seed=_u64(seed), first_episode=_u64(first_episode))
         if greedy:
             self._engine.rollout_greedy(d_start.data_ptr(), m, steps, lookahead_gamma, gamma, **outs)
         elif expected:
-            self._engine.rollout_expect_greedy(d_start.data_ptr(), m, steps, lookahead_gamma, gamma, epsilon=epsilon,
-                                               action_noise=a_noise, state_noise=s_noise, seed=int(seed) & (2 ** 64 - 1),
-                                               first_episode=int(first_episode) & (2 ** 64 - 1), **outs)
+            self._engine.rollout_expect_greedy(d_start.data_ptr(), m, steps, lookahead_gamma, gamma, **noise, **outs)
         elif stochastic:
-            self._engine.rollout_stochastic(d_start.data_ptr(), m, steps, gamma, epsilon=epsilon, action_noise=a_noise,
-                                            state_noise=s_noise, seed=int(seed) & (2 ** 64 - 1),
-                                            first_episode=int(first_episode) & (2 ** 64 - 1), **outs)
+            self._engine.rollout_stochastic(d_start.data_ptr(), m, steps, gamma, **noise, **outs)
         else:
             self._engine.rollout(d_start.data_ptr(), m, steps, gamma, **outs)
-        term = term != 0
-        if on_device:
-            return RolloutResult(final, ret, length, term, traj)
-        return RolloutResult(final.cpu().numpy(), ret.cpu().numpy(), length.cpu().numpy(), term.cpu().numpy(),
-                             traj.cpu().numpy() if every else None)
+        return _result(RolloutResult, on_device, out)
 
     def set_values(self, V) -> str:
         """The value function that goes with this policy's grid (n_states float32, the user's order), for ``resample``;
@@ -250,30 +282,16 @@ class DevicePolicy:
         the plugin of ``set_dynamics`` — over ``action_space`` (default: the table the constructor was given); returns
         the compiler's log.  Needs no policy table.  ``set_dynamics`` drops it again; ``set_values`` only replaces the
         values it reads."""
-        acts = self._action_space if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
-        if acts is None:
-            raise ValueError("set_greedy needs an action table: this DevicePolicy was built without one")
-        if not getattr(self, "_has_values", False):
-            raise RuntimeError("the greedy controller needs the value function: call set_values(V) first")
-        if not getattr(self, "_has_dynamics", False):
-            raise RuntimeError("the greedy controller needs the env's dynamics: call set_dynamics(dynamics_src) first")
-        log = self._engine.set_greedy(acts)
-        self._greedy_actions = acts
-        return log
+        return self._build_module("set_greedy", "the greedy controller", action_space, self._engine.set_greedy,
+                                  "_greedy_actions")
 
     def set_stochastic(self, action_space=None) -> str:
         """Build the stochastic rollout kernels — ``rollout(epsilon=..., action_noise=..., state_noise=...)`` and
         ``controller="random"`` — through the plugin of ``set_dynamics``; exploring steps draw from ``action_space``
         (default: the table the constructor was given), whose extremes clamp a noisy action.  Returns the compiler's
         log.  Needs neither a policy table nor values.  ``set_dynamics`` drops it again."""
-        acts = self._action_space if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
-        if acts is None:
-            raise ValueError("set_stochastic needs an action table: this DevicePolicy was built without one")
-        if not getattr(self, "_has_dynamics", False):
-            raise RuntimeError("a stochastic rollout needs the env's dynamics: call set_dynamics(dynamics_src) first")
-        log = self._engine.set_stochastic(acts)
-        self._stochastic_actions = acts
-        return log
+        return self._build_module("set_stochastic", "a stochastic rollout", action_space, self._engine.set_stochastic,
+                                  "_stochastic_actions", needs_values=False)
 
     def set_expected_greedy(self, action_space=None) -> str:
         """Build the expected-value greedy controller — the one-step lookahead on the value function of ``set_values``
@@ -281,16 +299,37 @@ class DevicePolicy:
         ``action_space`` (default: the table the constructor was given; finite values: its extremes clamp ``a + da_k`` and
         a noisy action); returns the compiler's log.  Needs no policy table.  ``set_dynamics`` drops it again;
         ``set_values`` and ``set_disturbances`` only replace what it reads."""
-        acts = self._action_space if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        return self._build_module("set_expected_greedy", "the expected controller", action_space,
+                                  self._engine.set_expect_greedy, "_expected_actions")
+
+    def _build_module(self, setter, who, action_space, build, record, needs_values=True) -> str:
+        """What set_greedy, set_stochastic and set_expected_greedy do: the table (default: the constructor's), the
+        refusals in `setter`'s and `who`'s name, the engine's `build`, and the table noted in the attribute `record`."""
+        acts = _table(action_space, self._action_space)
         if acts is None:
-            raise ValueError("set_expected_greedy needs an action table: this DevicePolicy was built without one")
-        if not getattr(self, "_has_values", False):
-            raise RuntimeError("the expected controller needs the value function: call set_values(V) first")
-        if not getattr(self, "_has_dynamics", False):
-            raise RuntimeError("the expected controller needs the env's dynamics: call set_dynamics(dynamics_src) first")
-        log = self._engine.set_expect_greedy(acts)
-        self._expected_actions = acts
+            raise ValueError(f"{setter} needs an action table: this DevicePolicy was built without one")
+        if needs_values and not self._has_values:
+            raise RuntimeError(f"{who} needs the value function: call set_values(V) first")
+        if not self._has_dynamics:
+            raise RuntimeError(f"{who} needs the env's dynamics: call set_dynamics(dynamics_src) first")
+        log = build(acts)
+        setattr(self, record, acts)
         return log
+
+    # the modules a rollout or a query needs, refused in one place each
+    def _need_greedy(self) -> None:
+        if self._greedy_actions is None:
+            raise RuntimeError("the greedy controller needs set_greedy() (again after every set_dynamics)")
+
+    def _need_expected_greedy(self) -> None:
+        if self._expected_actions is None:
+            raise RuntimeError("the expected controller needs set_expected_greedy() (again after every set_dynamics)")
+        if self._disturbances is None:
+            raise RuntimeError("the expected controller needs a disturbance set: call set_disturbances(...) first")
+
+    def _need_stochastic(self, who) -> None:
+        if self._stochastic_actions is None:
+            raise RuntimeError(f"{who} needs set_stochastic() (again after every set_dynamics)")
 
     def set_disturbances(self, disturbances) -> None:
         """The ``dynamicprogramming_amd.noise.Disturbances`` set the expected controller takes its expectation over
@@ -308,23 +347,18 @@ class DevicePolicy:
         """``greedy`` with the expectation over the disturbance set inside Q, in ONE kernel launch — the device twin of
         ``dynamicprogramming_amd.noise.expected_greedy_action``, same bits; the same outputs and in/out conventions.
         After ``set_expected_greedy`` and ``set_disturbances``."""
-        if getattr(self, "_expected_actions", None) is None:
-            raise RuntimeError("the expected controller needs set_expected_greedy() (again after every set_dynamics)")
-        if getattr(self, "_disturbances", None) is None:
-            raise RuntimeError("the expected controller needs a disturbance set: call set_disturbances(...) first")
+        self._need_expected_greedy()
         return self._lookahead(self._engine.expect_greedy, self._expected_actions, states, gamma, q_values)
 
     def random_words(self, seed, first_episode, m, step, block):
         """The random stream the stochastic rollouts draw from, read on the device: the (m, 4) uint32 words of draw
         block ``block`` at step ``step`` of the episodes ``first_episode + 0 .. m`` under ``seed`` (numpy) — the device
         twin of the module's ``random_words``, same bits.  After ``set_stochastic``."""
-        if getattr(self, "_stochastic_actions", None) is None:
-            raise RuntimeError("random_words needs set_stochastic() (again after every set_dynamics)")
+        self._need_stochastic("random_words")
         torch = self._torch
         m = int(m)
         out = torch.empty((m, 4), dtype=torch.int32, device=self.device)
-        self._engine.random_words(int(seed) & (2 ** 64 - 1), int(first_episode) & (2 ** 64 - 1), m, step, block,
-                                  out.data_ptr(), stream=self._stream())
+        self._engine.random_words(_u64(seed), _u64(first_episode), m, step, block, out.data_ptr(), stream=self._stream())
         return out.cpu().numpy().view(np.uint32)
 
     def greedy(self, states, gamma, q_values=False):
@@ -332,21 +366,13 @@ class DevicePolicy:
         ``greedy_action``, same bits: ``(best_index (m,) int32, action (m,) float32, q_best (m,) float32)`` and, with
         ``q_values=True``, the matrix ``Q (m, n_actions)`` float32 behind them.  A numpy array in -> numpy out, a float32
         tensor on this device in -> torch tensors on the device out, like calling this object."""
-        if getattr(self, "_greedy_actions", None) is None:
-            raise RuntimeError("the greedy controller needs set_greedy() (again after every set_dynamics)")
+        self._need_greedy()
         return self._lookahead(self._engine.greedy, self._greedy_actions, states, gamma, q_values)
 
     def _lookahead(self, launch, actions, states, gamma, q_values):
         """A lookahead query (``greedy``, ``expected_greedy``): the checked points, the output tensors, one launch."""
         torch = self._torch
-        on_device = torch.is_tensor(states)
-        if on_device:
-            if states.device != self.device or states.dtype != torch.float32 or states.dim() != 2 \
-                    or states.shape[1] != self.D:
-                raise ValueError(f"device states must be a float32 (m, {self.D}) tensor on {self.device}")
-            d_pts, m = states.contiguous(), states.shape[0]
-        else:
-            d_pts, m = self._points(states)
+        on_device, d_pts, m = self._device_states(states)
         best = torch.empty(m, dtype=torch.int32, device=self.device)
         act = torch.empty(m, dtype=torch.float32, device=self.device)
         qb = torch.empty(m, dtype=torch.float32, device=self.device)
@@ -370,7 +396,7 @@ class DevicePolicy:
         n = int(np.prod([len(t) for t in tables], dtype=np.int64))
         if out_values is None and out_policy is None:
             raise ValueError("resample needs out_values or out_policy")
-        if out_values is not None and not getattr(self, "_has_values", False):
+        if out_values is not None and not self._has_values:
             raise RuntimeError("resample of values needs the value function: call set_values(V) first")
         if out_policy is not None and not self._has_policy:
             raise RuntimeError("this DevicePolicy was built without a policy table")
@@ -424,46 +450,37 @@ class HybridPolicy:
         if not b._has_policy:
             raise RuntimeError("the secondary DevicePolicy was built without a policy table")
         noisy = any(v is not None for v in (epsilon, action_noise, state_noise, seed, first_episode, action_space))
-        if noisy:
-            epsilon = 0.0 if epsilon is None else epsilon
-            explore_threshold(epsilon)              # raises outside [0, 1]
-            a_noise = float(_checked_action_noise(0.0 if action_noise is None else action_noise))
-            s_noise = _noise_vector(state_noise, a.D)
-            table = a._action_space if action_space is None else np.ascontiguousarray(action_space, dtype=np.float32).ravel()
+        if noisy:                                   # a keyword that was not given is 0: no such noise
+            noise = _noise_keywords(a, epsilon or 0.0, action_noise or 0.0, state_noise)
+            if state_noise is None:
+                noise["state_noise"] = np.zeros(a.D, np.float32)
+            table = _table(action_space, a._action_space)
             if table is None:
                 raise ValueError("a stochastic hybrid rollout needs an exploration table: give action_space")
-        on_device, d_start, m, steps, every, final, ret, length, term, traj = a._rollout_buffers(states, steps, record_every)
+        on_device, d_start, m, steps, out, outs = a._rollout_buffers(states, steps, record_every)
         torch = a._torch
         second = torch.empty(m, dtype=torch.int32, device=a.device)
         mode = torch.empty(m, dtype=torch.uint8, device=a.device)
-        outs = dict(d_final=final.data_ptr(), d_return=ret.data_ptr(), d_length=length.data_ptr(),
-                    d_terminated=term.data_ptr(), d_secondary_steps=second.data_ptr(), d_last_mode=mode.data_ptr(),
-                    d_traj=traj.data_ptr() if every else 0, traj_every=every, stream=a._stream())
-        extra = ()
+        outs.update(d_secondary_steps=second.data_ptr(), d_last_mode=mode.data_ptr())
+        out += [second, mode]
+        # _built_for (this object) and _partner_stochastic (the primary) rebuild at different times: merging them changes behaviour
         if noisy:
             # the module lives on the primary's handle, and so does the note of what it was built for: HybridPolicy
             # objects that share a primary replace each other's module
-            built = getattr(a, "_partner_stochastic", None)
+            built = a._partner_stochastic
             if built is None or built[0] != a._dynamics_serial or built[1] is not b or not np.array_equal(built[2], table):
                 a._engine.set_partner_stochastic(b._engine, table)
                 a._partner_stochastic = (a._dynamics_serial, b, table.copy())
             switches = torch.empty(m, dtype=torch.int32, device=a.device)
             a._engine.rollout_hybrid_stochastic(b._engine, d_start.data_ptr(), m, steps, self.enter, self.leave, gamma,
-                                                epsilon=epsilon, action_noise=a_noise, state_noise=s_noise,
-                                                seed=int(0 if seed is None else seed) & (2 ** 64 - 1),
-                                                first_episode=int(0 if first_episode is None else first_episode) & (2 ** 64 - 1),
-                                                d_switches=switches.data_ptr(), **outs)
-            extra = (switches,)
-        else:
-            if self._built_for != a._dynamics_serial:
-                a._engine.set_partner(b._engine)
-                self._built_for = a._dynamics_serial
-            a._engine.rollout_hybrid(b._engine, d_start.data_ptr(), m, steps, self.enter, self.leave, gamma, **outs)
-        result = StochasticHybridRolloutResult if noisy else HybridRolloutResult
-        fields = (final, ret, length, term != 0, traj, second, mode) + extra
-        if on_device:
-            return result(*fields)
-        return result(*(None if x is None else x.cpu().numpy() for x in fields))
+                                                seed=_u64(seed or 0), first_episode=_u64(first_episode or 0),
+                                                d_switches=switches.data_ptr(), **noise, **outs)
+            return _result(StochasticHybridRolloutResult, on_device, out + [switches])
+        if self._built_for != a._dynamics_serial:
+            a._engine.set_partner(b._engine)
+            self._built_for = a._dynamics_serial
+        a._engine.rollout_hybrid(b._engine, d_start.data_ptr(), m, steps, self.enter, self.leave, gamma, **outs)
+        return _result(HybridRolloutResult, on_device, out)
 
 
 def _clamp_point(pts, lo, hi):
@@ -791,11 +808,11 @@ def random_words(seed, first_episode, m, step, block):
 def _episode_numbers(first_episode, rows):
     """first_episode + rows as uint64 (wrapping at 2^64, as the kernel's addition does)."""
     with np.errstate(over="ignore"):
-        return np.uint64(int(first_episode) & (2 ** 64 - 1)) + np.asarray(rows).astype(np.uint64)
+        return np.uint64(_u64(first_episode)) + np.asarray(rows).astype(np.uint64)
 
 
 def _episode_words(seed, episodes, step, block):
-    seed = int(seed) & (2 ** 64 - 1)
+    seed = _u64(seed)
     e = np.asarray(episodes, dtype=np.uint64)
     counter = np.empty(e.shape + (4,), np.uint32)
     counter[..., 0] = (e & _U32).astype(np.uint32)
@@ -814,10 +831,10 @@ def sym(words):
 def explore_threshold(epsilon) -> int:
     """eps24 of the exploration coin — a step explores iff ``(x0 >> 8) < eps24`` — from the float32 ``epsilon`` as the
     library computes it: ``llrint((double)epsilon * 2^24)``.  0 never explores, 2^24 always does."""
-    eps = np.float32(epsilon)
-    if not (eps >= 0.0 and eps <= 1.0):
+    eps = float(np.float32(epsilon))
+    if not 0.0 <= eps <= 1.0:
         raise ValueError("epsilon must lie in [0, 1]")
-    return int(np.rint(np.float64(eps) * 16777216.0))
+    return round(eps * 16777216.0)                 # exact in double, ties to even: llrint
 
 
 def random_action_index(words, n_actions):
@@ -841,7 +858,7 @@ def _noise_vector(state_noise, D):
 
 def _checked_action_noise(action_noise) -> np.float32:
     a = np.float32(action_noise)
-    if not (np.isfinite(a) and a >= 0):
+    if not 0 <= a < np.inf:
         raise ValueError("action_noise must be finite and not negative")
     return a
 
