@@ -53,6 +53,12 @@ SIGNATURES = {
                                                ctypes.c_float, _vp, _vp]),
     "pi_expect_value_sweep": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_float, _vp, _vp, _vp]),
+    "pi_robust_eval_sweeps": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_float, ctypes.c_int, _vp, _vp]),
+    "pi_robust_improve_sweep": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_float, _vp, _vp]),
+    "pi_robust_value_sweep": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_float, _vp, _vp, _vp]),
     "pi_reach_planes": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
     "pi_reach_depth_max": (ctypes.c_int, [_vp]),
     "pi_reach_units": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
@@ -107,6 +113,10 @@ SIGNATURES = {
     "pi_infer_set_expect_greedy": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
     "pi_infer_set_disturbances": (ctypes.c_int, [_vp, ctypes.c_int, _f32p, _f32p, _f32p]),
     "pi_infer_expect_greedy": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "pi_infer_set_robust": (ctypes.c_int, [_vp, _f32p, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]),
+    "pi_infer_robust": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pi_infer_rollout_adversary": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                                  ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
     "pi_infer_rollout_expect_greedy": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                                       ctypes.c_float, ctypes.c_float, _f32p, ctypes.c_uint64, ctypes.c_uint64,
                                                       _vp, _vp, _vp, _vp, _vp, ctypes.c_int, _vp]),
@@ -488,6 +498,19 @@ class Engine:
         _check(lib().pi_expect_value_sweep(self._h, V, Vnew, policy, term, s_begin, s_end, gamma,
                                            d_delta or None, d_changed or None, stream or None), "pi_expect_value_sweep")
 
+    # -- worst-case solving: the minimum over the points of the same set (weight 0: no part) --
+    def robust_eval_sweeps(self, Va, Vb, policy, term, s_begin, s_end, gamma, n_sweeps, d_delta=0, stream=0):
+        _check(lib().pi_robust_eval_sweeps(self._h, Va, Vb, policy, term, s_begin, s_end, gamma, n_sweeps,
+                                           d_delta or None, stream or None), "pi_robust_eval_sweeps")
+
+    def robust_improve_sweep(self, V, policy, term, s_begin, s_end, gamma, d_changed=0, stream=0):
+        _check(lib().pi_robust_improve_sweep(self._h, V, policy, term, s_begin, s_end, gamma,
+                                             d_changed or None, stream or None), "pi_robust_improve_sweep")
+
+    def robust_value_sweep(self, V, Vnew, policy, term, s_begin, s_end, gamma, d_delta=0, d_changed=0, stream=0):
+        _check(lib().pi_robust_value_sweep(self._h, V, Vnew, policy, term, s_begin, s_end, gamma,
+                                           d_delta or None, d_changed or None, stream or None), "pi_robust_value_sweep")
+
     def reach_planes(self, term, s_begin, s_end, d_bitmap, stream=0, dim=0):
         _check(lib().pi_reach_planes(self._h, term, s_begin, s_end, int(dim), d_bitmap, stream or None),
                "pi_reach_planes")
@@ -827,6 +850,26 @@ class InferenceEngine:
         buffer at `d_words` (pi_infer_random_words; asynchronous)."""
         _check(lib().pi_infer_random_words(self._h, int(seed), int(first_episode), int(m), int(step), int(block),
                                            d_words or None, stream or None), "pi_infer_random_words")
+
+    def set_robust(self, action_space) -> str:
+        """Upload the action table of the robust lookahead and build the adversary kernels behind the plugin of the last
+        set_dynamics (a compile check on a host-only handle); needs set_values and set_dynamics; returns the compiler's
+        log.  A later set_dynamics drops the module again.  The set is that of set_disturbances."""
+        return self._build("set_robust", *self._table(action_space))
+
+    def robust(self, d_points, m, gamma, d_best=0, d_action=0, d_q_best=0, d_q_all=0, d_worst=0, stream=0) -> None:
+        """The robust one-step lookahead at m query points in one launch (pi_infer_robust; raw device pointers,
+        asynchronous): the outputs of `greedy` plus d_worst (m) int32, the adversary's point against the winner."""
+        _check(lib().pi_infer_robust(self._h, d_points or None, int(m), float(gamma), d_best or None, d_action or None,
+                                     d_q_best or None, d_q_all or None, d_worst or None, stream or None), "pi_infer_robust")
+
+    def rollout_adversary(self, d_start, m, n_steps, lookahead_gamma, controller, gamma=1.0, d_final=0, d_return=0,
+                          d_length=0, d_terminated=0, d_traj=0, traj_every=0, stream=0) -> None:
+        """m episodes of n_steps closed-loop steps against the adversary in one launch (pi_infer_rollout_adversary; raw
+        device pointers, asynchronous).  controller: 0, the policy table; 1, the robust lookahead."""
+        self._rollout("pi_infer_rollout_adversary", (self._h,), d_start, m, n_steps, gamma,
+                      (float(lookahead_gamma), int(controller)), d_final, d_return, d_length, d_terminated, d_traj,
+                      traj_every, stream)
 
     def set_expect_greedy(self, action_space) -> str:
         """Upload the action table of the expected-value greedy controller and build its kernels behind the plugin of the

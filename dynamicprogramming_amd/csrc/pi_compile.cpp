@@ -211,6 +211,7 @@ int load_module(pi_handle* h, const std::vector<char>& image) {
         PI_HIP(hipModuleUnload(h->module_expect));
         h->module_expect = nullptr;
         h->f_expect_eval = h->f_expect_improve = h->f_expect_value = nullptr;
+        h->f_robust_eval = h->f_robust_improve = h->f_robust_value = nullptr;
     }
     PI_HIP(hipModuleLoadData(&h->module, image.data()));
     PI_HIP(hipModuleGetFunction(&h->f_eval, h->module, "pi_eval_sweep_kernel"));
@@ -308,6 +309,9 @@ int ensure_expect_module(pi_handle* h) {
         PI_HIP(hipModuleGetFunction(&h->f_expect_eval, h->module_expect, "pi_expect_eval_kernel"));
         PI_HIP(hipModuleGetFunction(&h->f_expect_improve, h->module_expect, "pi_expect_improve_kernel"));
         PI_HIP(hipModuleGetFunction(&h->f_expect_value, h->module_expect, "pi_expect_value_kernel"));
+        PI_HIP(hipModuleGetFunction(&h->f_robust_eval, h->module_expect, "pi_robust_eval_kernel"));       // the worst-case fold
+        PI_HIP(hipModuleGetFunction(&h->f_robust_improve, h->module_expect, "pi_robust_improve_kernel"));
+        PI_HIP(hipModuleGetFunction(&h->f_robust_value, h->module_expect, "pi_robust_value_kernel"));
     }
     h->expect_built = true;
     return 0;

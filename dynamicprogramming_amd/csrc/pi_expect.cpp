@@ -1,5 +1,6 @@
-// pi_expect.cpp — noise-aware solving: the disturbance set of a handle and the expectation sweeps over it
-// (csrc/pi_expect_kernels.hip; the semantics are written out in include/pi_mi355.h at pi_set_disturbances).
+// pi_expect.cpp — noise-aware solving: the disturbance set of a handle, the expectation sweeps over it and the worst-case
+// sweeps over it (csrc/pi_expect_kernels.hip; the semantics are written out in include/pi_mi355.h at pi_set_disturbances
+// and pi_robust_eval_sweeps).
 
 #include "pi_internal.h"
 
@@ -13,7 +14,7 @@ namespace {
 constexpr int kMaxPoints = pi::kMaxDisturbances;
 constexpr int kBlock = 256;         // PI_BLOCK_EXPECT: one chunk per workgroup
 
-// What every expectation sweep checks before it looks at its own arguments.  The set comes first, so that a caller who
+// What every expectation and worst-case sweep checks before it looks at its own arguments.  The set comes first, so that a caller who
 // forgot it is told so on any handle.
 int check_expect(const pi_handle* h, const char* who, int64_t s_begin, int64_t s_end) {
     if (!h) return fail("null handle");
@@ -24,6 +25,61 @@ int check_expect(const pi_handle* h, const char* who, int64_t s_begin, int64_t s
 unsigned int* delta_slots(pi_handle* h, bool want) { return want ? h->d_slots : nullptr; }
 unsigned int* changed_slots(pi_handle* h, bool want) { return want ? h->d_slots + kSlots : nullptr; }
 Grid2 blocks_for(int64_t count) { return {launch_blocks(kBlock, count, 1), 1u}; }
+
+// The three sweeps, each ONE host function for the expectation and the worst case: `kernel` is the instantiation of the
+// handle's expectation module that the entry point `who` launches (pi_expect_*_kernel or pi_robust_*_kernel: same
+// arguments, same chunking).
+int eval_sweeps(pi_handle* h, const char* who, hipFunction_t kernel, float* Va, float* Vb, const int32_t* policy,
+                const uint8_t* term, int64_t s_begin, int64_t s_end, float gamma, int n_sweeps, float* d_delta, void* stream) {
+    if (check_expect(h, who, s_begin, s_end)) return 1;
+    if (n_sweeps < 0) return fail("n_sweeps < 0");
+    if (!Va || !Vb || !policy) return fail("null device pointer");
+    if (Va == Vb) return fail("Va and Vb must be different buffers (Jacobi sweep)");
+    if (n_sweeps == 0) return 0;
+    drop_eval_list(h);                                       // ends a pi_eval_begin bracket
+    DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (s_end == s_begin) return zero_outputs(d_delta, nullptr, st);
+    for (int i = 0; i < n_sweeps; ++i) {
+        const float* src = (i & 1) ? Vb : Va;
+        float* dst = (i & 1) ? Va : Vb;
+        // every sweep copies the terminal states' values: both buffers hold them after the first, as pi_eval_sweeps leaves them
+        PI_HIP(launch(kernel, blocks_for(s_end - s_begin), kBlock, st, src, dst, policy, term, (const float*)h->d_tab,
+                      (const float*)h->d_dist, h->dist_k, h->dist_a_min, h->dist_a_max, (long long)s_begin, (long long)s_end,
+                      gamma, delta_slots(h, i == n_sweeps - 1 && d_delta)));
+    }
+    return finalize(h, d_delta, nullptr, st);
+}
+
+int improve_sweep(pi_handle* h, const char* who, hipFunction_t kernel, const float* V, int32_t* policy, const uint8_t* term,
+                  int64_t s_begin, int64_t s_end, float gamma, uint32_t* d_changed, void* stream) {
+    if (check_expect(h, who, s_begin, s_end)) return 1;
+    if (!V || !policy) return fail("null device pointer");
+    drop_eval_list(h);                                       // the policy is about to change
+    DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (s_end == s_begin) return zero_outputs(nullptr, d_changed, st);
+    PI_HIP(launch(kernel, blocks_for(s_end - s_begin), kBlock, st, V, policy, term, (const float*)h->d_tab,
+                  (const float*)h->d_dist, h->dist_k, h->dist_a_min, h->dist_a_max, (long long)s_begin, (long long)s_end, gamma,
+                  changed_slots(h, d_changed != nullptr)));
+    return finalize(h, nullptr, d_changed, st);
+}
+
+int value_sweep(pi_handle* h, const char* who, hipFunction_t kernel, const float* V, float* Vnew, int32_t* policy,
+                const uint8_t* term, int64_t s_begin, int64_t s_end, float gamma, float* d_delta, uint32_t* d_changed,
+                void* stream) {
+    if (check_expect(h, who, s_begin, s_end)) return 1;
+    if (!V || !Vnew || !policy) return fail("null device pointer");
+    if (V == Vnew) return fail("V and Vnew must be different buffers (Jacobi sweep)");
+    drop_eval_list(h);                                       // the policy is about to change
+    DeviceGuard guard(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (s_end == s_begin) return zero_outputs(d_delta, d_changed, st);
+    PI_HIP(launch(kernel, blocks_for(s_end - s_begin), kBlock, st, V, Vnew, policy, term, (const float*)h->d_tab,
+                  (const float*)h->d_dist, h->dist_k, h->dist_a_min, h->dist_a_max, (long long)s_begin, (long long)s_end, gamma,
+                  delta_slots(h, d_delta != nullptr), changed_slots(h, d_changed != nullptr)));
+    return finalize(h, d_delta, d_changed, st);
+}
 
 }  // namespace
 
@@ -88,53 +144,38 @@ int pi_set_disturbances(pi_handle* h, int K, const float* action_offsets, const 
 
 int pi_expect_eval_sweeps(pi_handle* h, float* Va, float* Vb, const int32_t* policy, const uint8_t* term, int64_t s_begin,
                           int64_t s_end, float gamma, int n_sweeps, float* d_delta, void* stream) {
-    if (check_expect(h, "pi_expect_eval_sweeps", s_begin, s_end)) return 1;
-    if (n_sweeps < 0) return fail("n_sweeps < 0");
-    if (!Va || !Vb || !policy) return fail("null device pointer");
-    if (Va == Vb) return fail("Va and Vb must be different buffers (Jacobi sweep)");
-    if (n_sweeps == 0) return 0;
-    drop_eval_list(h);                                       // ends a pi_eval_begin bracket
-    DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (s_end == s_begin) return zero_outputs(d_delta, nullptr, st);
-    for (int i = 0; i < n_sweeps; ++i) {
-        const float* src = (i & 1) ? Vb : Va;
-        float* dst = (i & 1) ? Va : Vb;
-        // every sweep copies the terminal states' values: both buffers hold them after the first, as pi_eval_sweeps leaves them
-        PI_HIP(launch(h->f_expect_eval, blocks_for(s_end - s_begin), kBlock, st, src, dst, policy, term, (const float*)h->d_tab,
-                      (const float*)h->d_dist, h->dist_k, h->dist_a_min, h->dist_a_max, (long long)s_begin, (long long)s_end,
-                      gamma, delta_slots(h, i == n_sweeps - 1 && d_delta)));
-    }
-    return finalize(h, d_delta, nullptr, st);
+    return eval_sweeps(h, "pi_expect_eval_sweeps", h ? h->f_expect_eval : nullptr, Va, Vb, policy, term, s_begin, s_end, gamma,
+                       n_sweeps, d_delta, stream);
+}
+
+int pi_robust_eval_sweeps(pi_handle* h, float* Va, float* Vb, const int32_t* policy, const uint8_t* term, int64_t s_begin,
+                          int64_t s_end, float gamma, int n_sweeps, float* d_delta, void* stream) {
+    return eval_sweeps(h, "pi_robust_eval_sweeps", h ? h->f_robust_eval : nullptr, Va, Vb, policy, term, s_begin, s_end, gamma,
+                       n_sweeps, d_delta, stream);
 }
 
 int pi_expect_improve_sweep(pi_handle* h, const float* V, int32_t* policy, const uint8_t* term, int64_t s_begin,
                             int64_t s_end, float gamma, uint32_t* d_changed, void* stream) {
-    if (check_expect(h, "pi_expect_improve_sweep", s_begin, s_end)) return 1;
-    if (!V || !policy) return fail("null device pointer");
-    drop_eval_list(h);                                       // the policy is about to change
-    DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (s_end == s_begin) return zero_outputs(nullptr, d_changed, st);
-    PI_HIP(launch(h->f_expect_improve, blocks_for(s_end - s_begin), kBlock, st, V, policy, term, (const float*)h->d_tab,
-                  (const float*)h->d_dist, h->dist_k, h->dist_a_min, h->dist_a_max, (long long)s_begin, (long long)s_end, gamma,
-                  changed_slots(h, d_changed != nullptr)));
-    return finalize(h, nullptr, d_changed, st);
+    return improve_sweep(h, "pi_expect_improve_sweep", h ? h->f_expect_improve : nullptr, V, policy, term, s_begin, s_end,
+                         gamma, d_changed, stream);
+}
+
+int pi_robust_improve_sweep(pi_handle* h, const float* V, int32_t* policy, const uint8_t* term, int64_t s_begin,
+                            int64_t s_end, float gamma, uint32_t* d_changed, void* stream) {
+    return improve_sweep(h, "pi_robust_improve_sweep", h ? h->f_robust_improve : nullptr, V, policy, term, s_begin, s_end,
+                         gamma, d_changed, stream);
 }
 
 int pi_expect_value_sweep(pi_handle* h, const float* V, float* Vnew, int32_t* policy, const uint8_t* term, int64_t s_begin,
                           int64_t s_end, float gamma, float* d_delta, uint32_t* d_changed, void* stream) {
-    if (check_expect(h, "pi_expect_value_sweep", s_begin, s_end)) return 1;
-    if (!V || !Vnew || !policy) return fail("null device pointer");
-    if (V == Vnew) return fail("V and Vnew must be different buffers (Jacobi sweep)");
-    drop_eval_list(h);                                       // the policy is about to change
-    DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (s_end == s_begin) return zero_outputs(d_delta, d_changed, st);
-    PI_HIP(launch(h->f_expect_value, blocks_for(s_end - s_begin), kBlock, st, V, Vnew, policy, term, (const float*)h->d_tab,
-                  (const float*)h->d_dist, h->dist_k, h->dist_a_min, h->dist_a_max, (long long)s_begin, (long long)s_end, gamma,
-                  delta_slots(h, d_delta != nullptr), changed_slots(h, d_changed != nullptr)));
-    return finalize(h, d_delta, d_changed, st);
+    return value_sweep(h, "pi_expect_value_sweep", h ? h->f_expect_value : nullptr, V, Vnew, policy, term, s_begin, s_end,
+                       gamma, d_delta, d_changed, stream);
+}
+
+int pi_robust_value_sweep(pi_handle* h, const float* V, float* Vnew, int32_t* policy, const uint8_t* term, int64_t s_begin,
+                          int64_t s_end, float gamma, float* d_delta, uint32_t* d_changed, void* stream) {
+    return value_sweep(h, "pi_robust_value_sweep", h ? h->f_robust_value : nullptr, V, Vnew, policy, term, s_begin, s_end,
+                       gamma, d_delta, d_changed, stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// pi_expect_kernels.hip — the EXPECTED Bellman backup over a disturbance set, for gfx950 (MI355X, CDNA4).
+// pi_expect_kernels.hip — the EXPECTED and the WORST-CASE Bellman backup over a disturbance set, for gfx950 (MI355X, CDNA4).
 //
 // Appended to the sweep translation unit (build_source + this file, ensure_expect_module in pi_compile.cpp) and built as a
 // further module of the handle by the first pi_set_disturbances after pi_compile; never compiled on its own.  No reference
@@ -14,6 +14,14 @@
 //   4. q_k = r_k + gamma * E_k, a multiply then an add;
 //   5. Q = p_0 * q_0, then Q = fmaf(p_k, q_k, Q).
 // With K = 1, da = dx = 0 and p = 1 this is pi_backup bit for bit.
+//
+// The WORST-CASE backup (pi_robust_*_kernel, include/pi_mi355.h at pi_robust_eval_sweeps) keeps steps 1-4 and folds
+//     Q(s, a) = min_k q_k over the points with p_k != 0
+// with comparisons: the first participating point gives Q, a later one replaces it when q_k < Q || q_k != q_k (strict: the
+// first of equal points stays, -0 does not replace +0; a NaN is taken and only another NaN replaces it).  A point with
+// p_k == 0 is skipped as if its row were not in the table — it neither starts nor breaks a run of equal da — and that
+// skip is a scalar branch on the row the wave holds in SGPRs.  Both folds are ONE point loop, pi_expect_q<WORST>; the
+// pi_expect_* kernels instantiate the expectation, the pi_robust_* kernels the minimum, in the same module.
 //
 // The table — K rows of {da, dx_0 .. dx_{D-1}, p}, dx in the USER's dimension order — is run-time data in a device buffer
 // of the handle: another set is another upload, never another build.  A workgroup stages it in LDS beside the bin table
@@ -46,8 +54,9 @@ __device__ __forceinline__ float pi_noise_word(const PiNoise& nz, int k, int j) 
     return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(nz.rows[k * PI_NOISE_ROW + j])));
 }
 
-// Q(s, a) of the header.  vp / held: the corner values of the cell the lane looked at last, kept by the caller across
-// points (and across its action loop).
+// Q(s, a) of the header, WORST: the minimum over the points of weight != 0 instead of the expectation.  vp / held: the
+// corner values of the cell the lane looked at last, kept by the caller across points (and across its action loop).
+template <bool WORST>
 __device__ __forceinline__ float pi_expect_q(const float (&x)[PI_D], float a, const PiNoise& nz,
                                              const float* __restrict__ V, float gamma, PiPair (&vp)[PI_NPAIR],
                                              unsigned int& held) {
@@ -58,9 +67,12 @@ __device__ __forceinline__ float pi_expect_q(const float (&x)[PI_D], float a, co
     // -0.0f + p * q is p * q for every value of the product, signed zeros and NaN included: the first point's multiply
     // and the later points' fmaf are one instruction
     float Q = -0.0f;
+    bool started = false;                                                // WORST: a point took part (wave-uniform)
     for (int k = 0; k < nz.K; ++k) {
+        // WORST: da is read with the weight, before the branch on it, so that a point opens with one LDS round trip, not two
         const float da = pi_noise_word(nz, k, 0);
-        if (k == 0 || da != da_prev) {                                   // wave-uniform
+        if (WORST && pi_noise_word(nz, k, PI_D + 1) == 0.0f) continue;   // no part in the minimum, nor in the runs of da
+        if ((WORST ? !started : k == 0) || da != da_prev) {              // wave-uniform
             const float ak = da == 0.0f ? a : fminf(fmaxf(a + da, nz.a_min), nz.a_max);
             pi_dynamics(x, ak, ns, &reward, &done);
             da_prev = da;
@@ -85,7 +97,12 @@ __device__ __forceinline__ float pi_expect_q(const float (&x)[PI_D], float a, co
             __builtin_amdgcn_s_setprio(0);
         }
         const float q = reward + gamma * e;
-        Q = fmaf(pi_noise_word(nz, k, PI_D + 1), q, Q);
+        if (WORST) {
+            if (!started || q < Q || q != q) Q = q;
+            started = true;
+        } else {
+            Q = fmaf(pi_noise_word(nz, k, PI_D + 1), q, Q);
+        }
     }
     return Q;
 }
@@ -103,46 +120,51 @@ __device__ __forceinline__ bool pi_expect_chunk(long long s_begin, long long s_e
 
 // ---- evaluation: Vn[s] = Q(s, actions[policy[s]]) for s in [s_begin, s_end); terminal states copy V[s] ---------------
 // delta_bits (nullable): the handle's slots, receiving the atomic max of the bit pattern of |Vn - V| (pi_finalize_kernel).
-extern "C" __global__ void __launch_bounds__(PI_BLOCK_EXPECT)
-pi_expect_eval_kernel(const float* __restrict__ V, float* __restrict__ Vn, const int* __restrict__ policy,
-                      const unsigned char* __restrict__ term, const float* __restrict__ tab,
-                      const float* __restrict__ dist, int K, float a_min, float a_max, long long s_begin, long long s_end,
-                      float gamma, unsigned int* __restrict__ delta_bits) {
-    __shared__ float lds_tab[PI_GRID.tab_len];
-    __shared__ float lds_noise[PI_NOISE_MAX * PI_NOISE_ROW];
-    long long sb;
-    unsigned int lane;
-    if (!pi_expect_chunk(s_begin, s_end, sb, lane)) return;
-    const bool need_old = delta_bits != nullptr || term != nullptr;      // the residual, the terminal copy (launch-uniform)
-    const PiStateIn in = pi_load_state(V, policy, term, sb, lane, need_old);
-    pi_stage_table<PI_BLOCK_EXPECT>(tab, lds_tab);
-    pi_stage_noise(dist, K, lds_noise);
-    __syncthreads();
-    const PiNoise nz = {lds_noise, K, a_min, a_max};
-
-    float nv = in.v_old;
-    if (!in.term) {
-        const unsigned int s = (unsigned int)sb + lane;
-        float x[PI_D];
-        pi_state_coords(s, lds_tab, x);
-        PiPair vp[PI_NPAIR];
-#pragma unroll
-        for (int p = 0; p < PI_NPAIR; ++p) vp[p] = PiPair{0.0f, 0.0f};
-        unsigned int held = 0xffffffffu;
-        nv = pi_expect_q(x, lds_tab[PI_TAB_ACT + pi_checked_action(in.action, s)], nz, V, gamma, vp, held);
+// The body stays in the kernel (a macro, not a function the two kernels inline): the expectation kernel then compiles to the
+// instructions and registers it had before the fold became a template argument.
+#define PI_EXPECT_EVAL_KERNEL(name, WORST)                                                                               \
+    extern "C" __global__ void __launch_bounds__(PI_BLOCK_EXPECT)                                                        \
+    name(const float* __restrict__ V, float* __restrict__ Vn, const int* __restrict__ policy,                            \
+         const unsigned char* __restrict__ term, const float* __restrict__ tab, const float* __restrict__ dist, int K,   \
+         float a_min, float a_max, long long s_begin, long long s_end, float gamma,                                      \
+         unsigned int* __restrict__ delta_bits) {                                                                        \
+        __shared__ float lds_tab[PI_GRID.tab_len];                                                                       \
+        __shared__ float lds_noise[PI_NOISE_MAX * PI_NOISE_ROW];                                                         \
+        long long sb;                                                                                                    \
+        unsigned int lane;                                                                                               \
+        if (!pi_expect_chunk(s_begin, s_end, sb, lane)) return;                                                          \
+        /* the residual, the terminal copy (launch-uniform) */                                                           \
+        const bool need_old = delta_bits != nullptr || term != nullptr;                                                  \
+        const PiStateIn in = pi_load_state(V, policy, term, sb, lane, need_old);                                         \
+        pi_stage_table<PI_BLOCK_EXPECT>(tab, lds_tab);                                                                   \
+        pi_stage_noise(dist, K, lds_noise);                                                                              \
+        __syncthreads();                                                                                                 \
+        const PiNoise nz = {lds_noise, K, a_min, a_max};                                                                 \
+                                                                                                                         \
+        float nv = in.v_old;                                                                                             \
+        if (!in.term) {                                                                                                  \
+            const unsigned int s = (unsigned int)sb + lane;                                                              \
+            float x[PI_D];                                                                                               \
+            pi_state_coords(s, lds_tab, x);                                                                              \
+            PiPair vp[PI_NPAIR];                                                                                         \
+            _Pragma("unroll") for (int p = 0; p < PI_NPAIR; ++p) vp[p] = PiPair{0.0f, 0.0f};                             \
+            unsigned int held = 0xffffffffu;                                                                             \
+            nv = pi_expect_q<WORST>(x, lds_tab[PI_TAB_ACT + pi_checked_action(in.action, s)], nz, V, gamma, vp, held);   \
+        }                                                                                                                \
+        float dmax = 0.0f;                                                                                               \
+        if (threadIdx.x == lane) {                                                                                       \
+            pi_store_lane(Vn + sb, lane, nv);                                                                            \
+            const float dlt = fabsf(nv - in.v_old);                                                                      \
+            dmax = dlt > dmax ? dlt : dmax;                                                                              \
+        }                                                                                                                \
+        if (delta_bits != nullptr) pi_wave_max_to<PI_BLOCK_EXPECT>(dmax, delta_bits);                                    \
     }
-    float dmax = 0.0f;
-    if (threadIdx.x == lane) {
-        pi_store_lane(Vn + sb, lane, nv);
-        const float dlt = fabsf(nv - in.v_old);
-        dmax = dlt > dmax ? dlt : dmax;
-    }
-    if (delta_bits != nullptr) pi_wave_max_to<PI_BLOCK_EXPECT>(dmax, delta_bits);
-}
+PI_EXPECT_EVAL_KERNEL(pi_expect_eval_kernel, false)
+PI_EXPECT_EVAL_KERNEL(pi_robust_eval_kernel, true)
 
 // ---- improvement and value sweep: policy[s] = argmax_a Q(s, a), strict '>' from -1.0e30f over ascending actions -------
 // Terminal states keep their entry.  WRITE_V: also Vn[s] = max_a Q(s, a) (terminal: copy) and the residual.
-template <bool WRITE_V>
+template <bool WRITE_V, bool WORST>
 __device__ __forceinline__ void pi_expect_improve_body(const float* __restrict__ V, float* __restrict__ Vn,
                                                        int* __restrict__ policy, const unsigned char* __restrict__ term,
                                                        const float* __restrict__ tab, const float* __restrict__ dist, int K,
@@ -175,7 +197,7 @@ __device__ __forceinline__ void pi_expect_improve_body(const float* __restrict__
         float best_q = -1.0e30f;
         int best = 0;
         for (int a = 0; a < PI_NA; ++a) {
-            const float q = pi_expect_q(x, lds_tab[PI_TAB_ACT + a], nz, V, gamma, vp, held);
+            const float q = pi_expect_q<WORST>(x, lds_tab[PI_TAB_ACT + a], nz, V, gamma, vp, held);
             if (q > best_q) { best_q = q; best = a; }
         }
         if (live) {
@@ -198,8 +220,8 @@ extern "C" __global__ void __launch_bounds__(PI_BLOCK_EXPECT)
 pi_expect_improve_kernel(const float* __restrict__ V, int* __restrict__ policy, const unsigned char* __restrict__ term,
                          const float* __restrict__ tab, const float* __restrict__ dist, int K, float a_min, float a_max,
                          long long s_begin, long long s_end, float gamma, unsigned int* __restrict__ changed) {
-    pi_expect_improve_body<false>(V, nullptr, policy, term, tab, dist, K, a_min, a_max, s_begin, s_end, gamma, nullptr,
-                                  changed);
+    pi_expect_improve_body<false, false>(V, nullptr, policy, term, tab, dist, K, a_min, a_max, s_begin, s_end, gamma, nullptr,
+                                         changed);
 }
 
 extern "C" __global__ void __launch_bounds__(PI_BLOCK_EXPECT)
@@ -207,5 +229,24 @@ pi_expect_value_kernel(const float* __restrict__ V, float* __restrict__ Vn, int*
                        const unsigned char* __restrict__ term, const float* __restrict__ tab,
                        const float* __restrict__ dist, int K, float a_min, float a_max, long long s_begin, long long s_end,
                        float gamma, unsigned int* __restrict__ delta_bits, unsigned int* __restrict__ changed) {
-    pi_expect_improve_body<true>(V, Vn, policy, term, tab, dist, K, a_min, a_max, s_begin, s_end, gamma, delta_bits, changed);
+    pi_expect_improve_body<true, false>(V, Vn, policy, term, tab, dist, K, a_min, a_max, s_begin, s_end, gamma, delta_bits,
+                                        changed);
+}
+
+// The same two with the worst-case fold.
+extern "C" __global__ void __launch_bounds__(PI_BLOCK_EXPECT)
+pi_robust_improve_kernel(const float* __restrict__ V, int* __restrict__ policy, const unsigned char* __restrict__ term,
+                         const float* __restrict__ tab, const float* __restrict__ dist, int K, float a_min, float a_max,
+                         long long s_begin, long long s_end, float gamma, unsigned int* __restrict__ changed) {
+    pi_expect_improve_body<false, true>(V, nullptr, policy, term, tab, dist, K, a_min, a_max, s_begin, s_end, gamma, nullptr,
+                                        changed);
+}
+
+extern "C" __global__ void __launch_bounds__(PI_BLOCK_EXPECT)
+pi_robust_value_kernel(const float* __restrict__ V, float* __restrict__ Vn, int* __restrict__ policy,
+                       const unsigned char* __restrict__ term, const float* __restrict__ tab,
+                       const float* __restrict__ dist, int K, float a_min, float a_max, long long s_begin, long long s_end,
+                       float gamma, unsigned int* __restrict__ delta_bits, unsigned int* __restrict__ changed) {
+    pi_expect_improve_body<true, true>(V, Vn, policy, term, tab, dist, K, a_min, a_max, s_begin, s_end, gamma, delta_bits,
+                                       changed);
 }

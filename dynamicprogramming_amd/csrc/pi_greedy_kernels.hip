@@ -89,8 +89,9 @@ __device__ __forceinline__ float pi_greedy_q(const float (&s)[PI_D], float a, co
     return *reward + future;
 }
 
-// The expected-greedy module (pi_expect_greedy_kernels.hip) takes the functions above and leaves the two kernels out.
-#ifndef PI_EXPECT_GREEDY
+// The expected-greedy module (pi_expect_greedy_kernels.hip) and the adversary module (pi_adversary_kernels.hip) take the
+// functions above and leave the two kernels out.
+#if !defined(PI_EXPECT_GREEDY) && !defined(PI_ADVERSARY)
 // Batched query.  Every output may be null: out_best (m) int32, out_action (m) = actions[best], out_qbest (m),
 // out_qall (m, n_actions) row-major.
 extern "C" __global__ void __launch_bounds__(PI_GR_BLOCK)
@@ -151,4 +152,4 @@ pi_greedy_rollout_kernel(const float* __restrict__ start, long long m, int n_ste
                             }
                         });
 }
-#endif  // PI_EXPECT_GREEDY
+#endif  // PI_EXPECT_GREEDY, PI_ADVERSARY

@@ -12,8 +12,10 @@
 //   pi_resample.cpp   the inference handle's solution interpolated onto another grid (grid continuation)
 //   pi_greedy.cpp     value-greedy control on the inference handle: one-step lookahead on V, queries and rollouts
 //   pi_stochastic.cpp stochastic rollouts on the inference handle: random baseline, epsilon-random actions, noise (Philox)
-//   pi_expect.cpp     the expected backup over a disturbance set: pi_set_disturbances and the pi_expect_* sweeps
+//   pi_expect.cpp     the expected and the worst-case backup over a disturbance set: pi_set_disturbances, the pi_expect_*
+//                     and the pi_robust_* sweeps (one host function per pair, parametrised on the kernel)
 //   pi_expect_greedy.cpp  expected-value greedy control on the inference handle: the lookahead over a disturbance set
+//   pi_adversary.cpp  the robust lookahead and the adversary rollout on the inference handle: the worst case over that set
 #pragma once
 
 #include "pi_knobs.h"
@@ -180,6 +182,7 @@ struct pi_handle {
     // {da, dx_0 .. dx_{D-1}, p} (owned, allocated once), dist_a_min / _a_max the extremes of the action table
     hipModule_t module_expect = nullptr;
     hipFunction_t f_expect_eval = nullptr, f_expect_improve = nullptr, f_expect_value = nullptr;
+    hipFunction_t f_robust_eval = nullptr, f_robust_improve = nullptr, f_robust_value = nullptr;   // same module: min over the set
     bool expect_built = false;
     int dist_k = 0;
     float* d_dist = nullptr;
@@ -299,8 +302,11 @@ struct pi_infer {
     //   hybrid_stochastic  (pi_infer_set_partner_stochastic, pi_hybrid.cpp)  a partner's grid + the functions of the hybrid
     //                  and the stochastic file + csrc/pi_hybrid_stochastic_kernels.hip; the table is the pair's exploration
     //                  table; partner_stochastic_defines: the partner grid it was built for
-    // A new plugin unloads the five that were built on the one before it.
-    pi::InferModule rollout, hybrid, greedy, stochastic, expect_greedy, hybrid_stochastic;
+    //   robust         (pi_infer_set_robust, pi_adversary.cpp)             the functions of the greedy file +
+    //                  csrc/pi_adversary_kernels.hip: the robust lookahead (f_query) and the adversary rollout over the set
+    //                  of pi_infer_set_disturbances; the extremes clamp a + da_k
+    // A new plugin unloads the six that were built on the one before it.
+    pi::InferModule rollout, hybrid, greedy, stochastic, expect_greedy, hybrid_stochastic, robust;
     std::string partner_defines, partner_stochastic_defines;
     // the resample module (pi_infer_set_values, pi_resample.cpp): this grid + csrc/pi_resample_kernels.hip, and the value
     // function of the solution.  d_resample_tab: the destination's bin tables | action map of the last pi_infer_resample

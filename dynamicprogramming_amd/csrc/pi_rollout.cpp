@@ -114,7 +114,7 @@ int pi_infer_set_dynamics(pi_infer* h, const char* dynamics_src, char* log, size
     std::vector<char> image;
     if (pi::build_infer_module(h, h->grid_defines, dynamics_src, {{"rollout kernel", pi_embedded_rollout}}, log, log_len, image))
         return 1;
-    for (pi::InferModule* mod : {&h->hybrid, &h->greedy, &h->stochastic, &h->expect_greedy, &h->hybrid_stochastic})   // they hold the previous plugin
+    for (pi::InferModule* mod : {&h->hybrid, &h->greedy, &h->stochastic, &h->expect_greedy, &h->hybrid_stochastic, &h->robust})   // they hold the previous plugin
         if (pi::unload(h, *mod)) return 1;
     h->dynamics_src = dynamics_src;
     return pi::install(h, h->rollout, image, nullptr, "pi_rollout_kernel", nullptr);

@@ -231,6 +231,22 @@ class HipSweepBackend:
                                        s_begin, s_end, gamma, 0 if d_delta is None else d_delta.data_ptr(),
                                        0 if d_changed is None else d_changed.data_ptr(), self._stream())
 
+    # -- worst-case solving: the same set, the minimum over its points (pi_robust_*: the same module) --
+    def robust_eval_sweeps(self, Va, Vb, policy, term, s_begin, s_end, gamma, n_sweeps, d_delta):
+        self.engine.robust_eval_sweeps(Va.data_ptr(), Vb.data_ptr(), policy.data_ptr(), self._ptr(term),
+                                       s_begin, s_end, gamma, n_sweeps,
+                                       0 if d_delta is None else d_delta.data_ptr(), self._stream())
+
+    def robust_improve_sweep(self, V, policy, term, s_begin, s_end, gamma, d_changed):
+        self.engine.robust_improve_sweep(V.data_ptr(), policy.data_ptr(), self._ptr(term), s_begin, s_end,
+                                         gamma, 0 if d_changed is None else d_changed.data_ptr(),
+                                         self._stream())
+
+    def robust_value_sweep(self, V, Vnew, policy, term, s_begin, s_end, gamma, d_delta, d_changed):
+        self.engine.robust_value_sweep(V.data_ptr(), Vnew.data_ptr(), policy.data_ptr(), self._ptr(term),
+                                       s_begin, s_end, gamma, 0 if d_delta is None else d_delta.data_ptr(),
+                                       0 if d_changed is None else d_changed.data_ptr(), self._stream())
+
     def close(self):
         # what the XCD-local kernel did, kept past the handle: evaluations run in it, how many of those were run again
         # in the placement-independent kernel, whole runs launched in it
@@ -302,6 +318,7 @@ class _CudaPolicyIterationBase(abc.ABC):
                       "sweeps_per_iter": [], "eval_seconds": 0.0, "improve_seconds": 0.0}
 
         self.disturbances = None          # set_disturbances: the set every sweep takes its expectation over
+        self.risk = "expected"            # ... or, with risk="worst", its minimum
 
         self._precompute_grid_metadata()
         self._order = self._choose_memory_order()
@@ -720,7 +737,7 @@ class _CudaPolicyIterationBase(abc.ABC):
             logger.info(f"rank {self._rank}/{self._world}: states [{self._s_begin:,}, {self._s_end:,})")
 
     # ── noise-aware solving ─────────────────────────────────────────────────────────
-    def set_disturbances(self, disturbances) -> None:
+    def set_disturbances(self, disturbances, risk: str = "expected") -> None:
         """Plan for noise: with a ``noise.Disturbances`` set installed, every sweep of ``run()``, ``policy_evaluation()``,
         ``policy_improvement()`` and ``value_iteration()`` backs up the EXPECTATION over its K points,
         ``Q(s, a) = sum_k p_k [r_k + gamma E[V](f(s, a (+) da_k) + dx_k)]`` (csrc/pi_expect_kernels.hip), instead of the one
@@ -729,15 +746,32 @@ class _CudaPolicyIterationBase(abc.ABC):
         one-launch shortcuts and the per-evaluation state list are not used while a set is installed.  Call it after
         construction, before or between runs; ``stats["disturbances"]`` = K, ``save()`` archives the set.
         ``rollout(controller="greedy")`` keeps its deterministic one-step lookahead; ``rollout(controller="expected")`` is
-        the lookahead that takes this expectation.  Single rank only."""
+        the lookahead that takes this expectation.  Single rank only.
+
+        ``risk="worst"`` plans against the WORST point of the set instead: every sweep backs up
+        ``Q(s, a) = min_k [r_k + gamma E[V](f(s, a (+) da_k) + dx_k)]`` over the points of weight != 0 (the
+        ``pi_robust_*`` sweeps of the same module; include/pi_mi355.h at ``pi_robust_eval_sweeps`` is the definition), so
+        ``run()`` and ``value_iteration()`` solve the max-min problem and ``policy_evaluation()`` is the adversary's value
+        iteration against the current policy.  ``self.risk`` holds the mode; ``stats["risk"] = "worst"`` and the ``risk``
+        entry of ``save()`` exist only in that mode."""
+        if risk not in ("expected", "worst"):
+            raise ValueError(f"risk must be 'expected' or 'worst', not {risk!r}")
         if self._comm is not None:
             raise NotImplementedError("set_disturbances: the expectation sweeps are not sharded; use a single-rank solver")
         self._backend.set_disturbances(disturbances)
         self.disturbances = disturbances
         self.stats["disturbances"] = 0 if disturbances is None else int(disturbances.K)
+        self.risk = risk if disturbances is not None else "expected"
+        self.stats.pop("risk", None)
+        if self.risk == "worst":
+            self.stats["risk"] = "worst"
 
     def _expects(self) -> bool:
         return getattr(self, "disturbances", None) is not None
+
+    def _set_sweep(self, kind: str):
+        """The backend's sweep over the installed set: ``expect_<kind>``, or ``robust_<kind>`` with risk="worst"."""
+        return getattr(self._backend, ("robust_" if getattr(self, "risk", "expected") == "worst" else "expect_") + kind)
 
     # ── policy iteration ────────────────────────────────────────────────────────────
     def _evaluation_sweeps(self, n: int, gamma: float) -> None:
@@ -746,7 +780,7 @@ class _CudaPolicyIterationBase(abc.ABC):
         if self._comm is not None:
             self._comm.evaluation_sweeps(self, n, gamma)
             return
-        sweeps = self._backend.expect_eval_sweeps if self._expects() else self._backend.eval_sweeps
+        sweeps = self._set_sweep("eval_sweeps") if self._expects() else self._backend.eval_sweeps
         sweeps(self.d_value_function, self.d_new_value_function, self.d_policy,
                self._mask_arg(), self._s_begin, self._s_end, gamma, n,
                self._d_delta)
@@ -760,7 +794,7 @@ class _CudaPolicyIterationBase(abc.ABC):
         if self._comm is not None:
             self._comm.improvement_sweep(self, gamma)
             return
-        sweep = self._backend.expect_improve_sweep if self._expects() else self._backend.improve_sweep
+        sweep = self._set_sweep("improve_sweep") if self._expects() else self._backend.improve_sweep
         sweep(self.d_value_function, self.d_policy, self._mask_arg(),
               self._s_begin, self._s_end, gamma, self._d_changed)
 
@@ -913,7 +947,7 @@ class _CudaPolicyIterationBase(abc.ABC):
         limit = cfg.max_eval_iter if max_iter is None else int(max_iter)
         delta = float("inf")
         sweeps = 0
-        sweep = self._backend.expect_value_sweep if self._expects() else self._backend.value_sweep
+        sweep = self._set_sweep("value_sweep") if self._expects() else self._backend.value_sweep
         for i in range(limit):
             check = i % SYNC_INTERVAL == 0 or i == limit - 1
             sweep(self.d_value_function, self.d_new_value_function, self.d_policy,
@@ -1112,12 +1146,55 @@ class _CudaPolicyIterationBase(abc.ABC):
         finally:
             dp.close()
 
+    def adversary_rollout(self, start_states, steps, controller="policy", disturbances=None, gamma=1.0, record_every=0,
+                          device=None):
+        """Closed-loop episodes in which the disturbance is chosen AGAINST the controller (extension; DevicePolicy.
+        adversary_rollout, csrc/pi_adversary_kernels.hip): per step the worst point of a disturbance set for the action the
+        controller took — the fold of the worst-case sweeps on this solver's value function with config.gamma — moves the
+        episode.  controller="policy": the interpolated action of the policy table; controller="robust": the robust
+        one-step lookahead, which needs only V.  The set is `disturbances` if given, else the solver's own
+        (set_disturbances, or the one a load()ed archive carries), as rollout(controller="expected") finds it.  No random
+        numbers.  Returns a RolloutResult of numpy arrays."""
+        from utils.barycentric import DevicePolicy
+        if controller not in ("policy", "robust"):
+            raise ValueError(f"controller must be 'policy' or 'robust', not {controller!r}")
+        if disturbances is None:
+            disturbances = getattr(self, "disturbances", None)
+            if disturbances is None:
+                raise RuntimeError("an adversary rollout needs a disturbance set: pass disturbances=, or install one with "
+                                   "set_disturbances (a load()ed archive carries the set it was solved with)")
+        values = getattr(self, "value_function", None)
+        if values is None and hasattr(self, "d_value_function") and self._comm is None:
+            values = np.ascontiguousarray(self._to_user(self.d_value_function[:self.n_states].cpu().numpy()))
+        if values is None:
+            raise RuntimeError("an adversary rollout needs a value function: call run(), value_iteration() or load() first")
+        robust = controller == "robust"
+        if not robust and getattr(self, "policy", None) is None:
+            raise RuntimeError("rollout needs a trained policy in host memory: call run() or load() first")
+        if device is None:
+            device = getattr(self, "_device_arg", None) or "cuda:0"
+        dp = DevicePolicy(None if robust else self.policy, self.action_space, self.bounds_low, self.bounds_high,
+                          self.grid_shape, self.strides, self.corner_bits, device=device)
+        try:
+            dp.set_dynamics(self._dynamics_cuda_src())
+            dp.set_values(values)
+            dp.set_robust()
+            dp.set_disturbances(disturbances)
+            out = dp.adversary_rollout(start_states, steps, gamma=gamma, record_every=record_every, controller=controller,
+                                       lookahead_gamma=self.config.gamma)
+            dp._torch.cuda.synchronize(dp.device)
+            return out
+        finally:
+            dp.close()
+
     # ── persistence (schema of :392-432) ────────────────────────────────────────────
     def save(self, filepath) -> None:
         filepath = Path(filepath).with_suffix(".npz")
         filepath.parent.mkdir(parents=True, exist_ok=True)
         # the set a noise-aware run planned for (set_disturbances): (K, D + 2) float32, columns da, dx.., p
         extra = {"disturbances": self.disturbances.table()} if self._expects() else {}
+        if self._expects() and getattr(self, "risk", "expected") == "worst":
+            extra["risk"] = np.array("worst")      # only in that mode: every other archive keeps its keys
         np.savez(filepath, value_function=self.value_function, policy=self.policy,
                  bounds_low=self.bounds_low, bounds_high=self.bounds_high,
                  grid_shape=self.grid_shape, strides=self.strides, corner_bits=self.corner_bits,
@@ -1139,6 +1216,12 @@ class _CudaPolicyIterationBase(abc.ABC):
         if "disturbances" in data.files:
             from .noise import Disturbances
             inst.disturbances = Disturbances.from_table(data["disturbances"])
+        inst.risk = "expected"
+        if "risk" in data.files:
+            inst.risk = str(data["risk"])
+            if inst.risk not in ("expected", "worst") or inst.disturbances is None:
+                raise ValueError(f"{filepath}: the archive's risk entry {inst.risk!r} is not 'expected' or 'worst', or it "
+                                 "comes without a disturbance set")
         inst.n_actions = len(inst.action_space)
         inst.n_states = len(inst.states_space)
         inst.config = CudaPIConfig()

@@ -258,6 +258,37 @@ int pi_expect_value_sweep(pi_handle* h, const float* V, float* Vnew, int32_t* po
                           int64_t s_end, float gamma, float* d_delta, uint32_t* d_changed, void* stream);
 
 /*
+ * Worst-case solving over the same set: the max-min backup, Q(s, a) = min_k q_k over the points that take part, for a
+ * bounded disturbance chosen against the controller (same files; no reference counterpart).
+ * Worst-case fold.  Steps 1-4 of the definition at pi_set_disturbances stay as they are: a_k, step_dynamics, dx_k added
+ * where it is not zero, q_k = r_k + gamma * E_k.  Step 5 becomes, over the points in ascending k:
+ *   - a point with p_k == 0.0f takes no part, as if its row were not in the table: it neither starts nor breaks a run of
+ *     equal da that shares one dynamics step;
+ *   - the first participating point gives Q = q_k and k* = k;
+ *   - every later participating point replaces both when q_k < Q || q_k != q_k.  The comparison is strict, so the first of
+ *     equal points stays, and -0.0f does not replace +0.0f;
+ *   - a NaN point is taken, and nothing replaces a NaN afterwards except another NaN: a NaN in any participating point
+ *     gives Q = NaN, which never wins the strict > argmax — as the expectation's fmaf chain behaves;
+ *   - comparisons, not fminf: the sign of a zero and the NaN rule are the same on the device, in C++ and in numpy.
+ * Weights are otherwise ignored; the validation of pi_set_disturbances (finite, >= 0, sum 1 within 1e-4) stays, so at
+ * least one point participates.  With the one-point zero set this is the backup of pi_eval_sweep / pi_improve_sweep bit
+ * for bit.  max_a min_k is a gamma-contraction; the evaluation sweeps of a fixed policy, V'(s) = min_k q_k(s, pi(s)), are
+ * the adversary's value iteration against that policy.
+ *   pi_robust_eval_sweeps, pi_robust_improve_sweep, pi_robust_value_sweep
+ *                       pi_expect_eval_sweeps, pi_expect_improve_sweep and pi_expect_value_sweep with that fold: the same
+ *                       arguments, refusals (no set, no pi_compile, range, null pointers, Va == Vb), pi_eval_begin
+ *                       handling and limits.  The kernels (pi_robust_*_kernel) are further instantiations in the handle's
+ *                       expectation module: nothing more is built, and no mode is kept on the handle — the caller says
+ *                       which backup it wants by the call it makes, and may alternate the two on one set.
+ */
+int pi_robust_eval_sweeps(pi_handle* h, float* Va, float* Vb, const int32_t* policy, const uint8_t* term, int64_t s_begin,
+                          int64_t s_end, float gamma, int n_sweeps, float* d_delta, void* stream);
+int pi_robust_improve_sweep(pi_handle* h, const float* V, int32_t* policy, const uint8_t* term, int64_t s_begin,
+                            int64_t s_end, float gamma, uint32_t* d_changed, void* stream);
+int pi_robust_value_sweep(pi_handle* h, const float* V, float* Vnew, int32_t* policy, const uint8_t* term, int64_t s_begin,
+                          int64_t s_end, float gamma, float* d_delta, uint32_t* d_changed, void* stream);
+
+/*
  * Which planes of V can the states of [s_begin, s_end) read, under ANY action?  Along dimension
  * `dim`: d_bitmap (device, ceil(grid_shape[dim] / 32) uint32 words, zeroed here) receives one bit
  * per index: that of every successor cell and the one above it.  No counterpart in the reference
@@ -712,6 +743,35 @@ int pi_infer_rollout_expect_greedy(pi_infer* h, const float* d_start, int64_t m,
                                    float lookahead_gamma, float epsilon, float action_noise, const float* state_noise,
                                    uint64_t seed, uint64_t first_episode, float* d_final, float* d_return,
                                    int32_t* d_length, uint8_t* d_terminated, float* d_traj, int traj_every, void* stream);
+/*
+ * The robust lookahead and the adversary in the closed loop (csrc/pi_adversary_kernels.hip, csrc/pi_adversary.cpp; no
+ * reference counterpart): the worst-case fold at pi_robust_eval_sweeps over the set of pi_infer_set_disturbances, at
+ * arbitrary continuous states.
+ * Adversary step.  At a state s with an action value a the controller has chosen: k* is that fold with
+ * E_k = pi_greedy_expect(s'_k) (the sweeps' arithmetic, as the lookaheads use it), the discount lookahead_gamma and the
+ * clamp of a + da_k to the extremes of the table of pi_infer_set_robust.  The episode moves to s'_{k*}, which is
+ * f(s, a (+) da_{k*}) + dx_{k*} with no dx on a `done` step, and collects r_{k*} and done_{k*}.
+ * Robust lookahead.  best = argmax_a Q_worst(s, actions[a]), strict > from -1.0e30f over ascending indices.  The
+ * adversary's answer to the winner is the k* computed for it.  The successor, reward and flag that are kept are action 0's
+ * until an action wins.
+ *   pi_infer_set_robust   host array: the action table (n_actions >= 1 finite float32), copied to the device; builds the
+ *                       handle's adversary module (a further code object, cached like the others).  Needs
+ *                       pi_infer_set_values and pi_infer_set_dynamics; a later pi_infer_set_dynamics drops the module.
+ *   pi_infer_robust     the batched query: the arguments, nullable outputs and rules of pi_infer_greedy plus d_worst (m)
+ *                       int32, the k* of the winning action as a row index of the installed table, -1 when no action won.
+ *   pi_infer_rollout_adversary  m episodes of n_steps steps, one launch, no random numbers; the outputs of
+ *                       pi_infer_rollout.  controller 0: the action of the interpolated policy table (needs
+ *                       pi_infer_set_policy), then the adversary step; controller 1: the robust lookahead and the
+ *                       adversary's answer to it, nothing stepped twice.
+ * Refusals, by return code, in this order: a missing module, then a missing set; NaN discounts; a controller other than
+ * 0 or 1; controller 0 on a handle without a policy; then what the other rollouts refuse.
+ */
+int pi_infer_set_robust(pi_infer* h, const float* action_space, int n_actions, char* log, size_t log_len);
+int pi_infer_robust(pi_infer* h, const float* d_points, int64_t m, float gamma, int32_t* d_best, float* d_action,
+                    float* d_q_best, float* d_q_all, int32_t* d_worst, void* stream);
+int pi_infer_rollout_adversary(pi_infer* h, const float* d_start, int64_t m, int n_steps, float gamma, float lookahead_gamma,
+                               int controller, float* d_final, float* d_return, int32_t* d_length, uint8_t* d_terminated,
+                               float* d_traj, int traj_every, void* stream);
 int pi_infer_set_partner_stochastic(pi_infer* h, pi_infer* partner, const float* action_space, int n_actions, char* log,
                                     size_t log_len);
 int pi_infer_rollout_hybrid_stochastic(pi_infer* h, pi_infer* partner, const float* d_start, int64_t m, int n_steps,

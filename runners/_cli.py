@@ -49,6 +49,11 @@ deterministic successor — every sweep backs up the expectation over the tensor
 quantity (dynamicprogramming_amd.noise.Disturbances.uniform, solver.set_disturbances; csrc/pi_expect_kernels.hip), on
 every continuation level.  The set is saved with the policy.  They act on training only: when a saved policy is loaded
 instead, a note says that they had no effect.
+--rollout --adversary [policy|robust] (extension) runs the episodes against an adversary instead: at every step the worst
+point of the policy's disturbance set (the archive's, or the one the --train-*-noise flags name) for the action taken moves
+the episode (solver.adversary_rollout; csrc/pi_adversary_kernels.hip), under the policy table or the robust lookahead.
+--train-risk worst (extension, default expected) backs up the WORST point of that set instead of its expectation
+(solver.set_disturbances(set, risk="worst"): the max-min policy); the archive then carries a `risk` entry.
 
 The ignored group drives the reference's gymnasium / pygame / matplotlib evaluation harness, which is
 outside the scope of this package: training, saving and loading behave as in
@@ -89,23 +94,30 @@ def training_disturbances(env_name: str, action_noise: float = 0.0, state_noise=
 
 def train(env_name: str, bins: int | None = None, save_path: Path | str | None = None,
           value_iteration: bool = False, coarse_bins=(), train_action_noise: float = 0.0, train_state_noise=None,
-          train_noise_points: int = 3, **kw):
+          train_noise_points: int = 3, train_risk: str = "expected", **kw):
     """Build the env on its reference grid, run policy iteration on the GPU, save the .npz
     (reference: each runner's train(), e.g. pendulum_cuda.py:116-130).  value_iteration=True (extension):
     fused value-iteration sweeps to the same theta instead, at most max_pi_iter slices of max_eval_iter.
     coarse_bins (extension): grid continuation — solve at each of these bins per dimension first, every level
     (the last one at `bins`) continued from the one before it.  train_action_noise / train_state_noise /
-    train_noise_points (extension): noise-aware training — every level plans for that noise (training_disturbances)."""
+    train_noise_points (extension): noise-aware training — every level plans for that noise (training_disturbances);
+    train_risk="worst" (extension): against the worst point of that set instead of its expectation."""
     from dynamicprogramming_amd import envs
     noise = training_disturbances(env_name, train_action_noise, train_state_noise, train_noise_points)
-    if noise is not None:
+    if noise is not None and train_risk == "worst":
+        print(f"[{env_name}] worst-case training: max-min backup over {noise.K} disturbance points")
+    elif noise is not None:
         print(f"[{env_name}] noise-aware training: expected backup over {noise.K} disturbance points")
+    elif train_risk == "worst":
+        print(f"[{env_name}] note: --train-risk worst chooses among the points of the training noise, and neither "
+              "--train-action-noise nor --train-state-noise names any: it had no effect, training is deterministic")
+    risk = {"risk": "worst"} if train_risk == "worst" else {}
     previous = None
     for level in coarse_bins:
         t0 = time.perf_counter()
         coarse = envs.make(env_name, int(level), **kw)
         if noise is not None:
-            coarse.set_disturbances(noise)
+            coarse.set_disturbances(noise, **risk)
         if previous is not None:
             coarse.continue_from(previous)
         coarse.run()
@@ -115,7 +127,7 @@ def train(env_name: str, bins: int | None = None, save_path: Path | str | None =
         previous = coarse
     solver = envs.make(env_name, bins, **kw)
     if noise is not None:
-        solver.set_disturbances(noise)
+        solver.set_disturbances(noise, **risk)
     t0 = time.perf_counter()
     if previous is not None:
         solver.continue_from(previous)
@@ -193,11 +205,19 @@ def build_parser(env_name: str, default_save: str) -> argparse.ArgumentParser:
                         "step (one value for every dimension, or one per dimension)")
     p.add_argument("--train-noise-points", type=int, default=3, metavar="P",
                    help="(extension) Gauss-Legendre nodes per noisy quantity of the training noise (default: 3)")
+    p.add_argument("--adversary", nargs="?", const="policy", default=None, choices=("policy", "robust"),
+                   help="(extension, with --rollout) the disturbance is chosen against the controller at every step, from the "
+                        "set the policy was trained with (or the one the --train-*-noise flags name): under the policy "
+                        "table (default) or under the robust one-step lookahead")
+    p.add_argument("--train-risk", choices=("expected", "worst"), default="expected",
+                   help="(extension) what training backs up over the training noise's points: their expectation, or the "
+                        "worst of them (max-min: the policy that is best against the worst disturbance)")
     return p
 
 
 def training_noise_requested(args) -> bool:
-    return args.train_action_noise != 0.0 or args.train_state_noise is not None or args.train_noise_points != 3
+    return (args.train_action_noise != 0.0 or args.train_state_noise is not None or args.train_noise_points != 3
+            or args.train_risk != "expected")
 
 
 STEADY_WINDOW = 100     # states per episode in results/last_trajectory.npz (the reference's STATS_WINDOW)
@@ -205,12 +225,14 @@ STEADY_WINDOW = 100     # states per episode in results/last_trajectory.npz (the
 
 def evaluate(env_name: str, pi, episodes: int, steps: int, seed: int, start_x: float | None = None,
              traj_path: Path | None = None, controller: str = "policy", epsilon: float = 0.0, action_noise: float = 0.0,
-             state_noise=None, disturbances=None):
+             state_noise=None, disturbances=None, adversary=None):
     """--rollout: `episodes` closed-loop episodes of at most `steps` steps in one kernel launch (solver.rollout), one
     line each.  `traj_path`: also dump the last min(100, length + 1) states of every episode, concatenated, as the
     reference's evaluate() does for its scoring script (double_cartpole_swingup_cuda.py:583-592).  `controller`:
     "policy", "greedy" or "expected" (--controller; `disturbances`: the set of "expected" when the solver has none).  `epsilon`, `action_noise`, `state_noise` (--epsilon, --action-noise,
-    --state-noise): a stochastic rollout, its stream seeded by `seed` like the starts.  Returns the RolloutResult."""
+    --state-noise): a stochastic rollout, its stream seeded by `seed` like the starts.  `adversary` ("policy" or "robust",
+    --adversary): the episodes run against the worst point of `disturbances` (None: the solver's own set) under that
+    controller instead (solver.adversary_rollout); the lines keep their form.  Returns the RolloutResult."""
     import numpy as np
     from dynamicprogramming_amd import envs
     cls = envs.ENVS[env_name]
@@ -218,8 +240,12 @@ def evaluate(env_name: str, pi, episodes: int, steps: int, seed: int, start_x: f
     kw = {} if start_x is None else {"start_x": start_x}
     starts = cls.start_states(rng, episodes, **kw)
     extra = {} if disturbances is None else {"disturbances": disturbances}
-    res = pi.rollout(starts, steps, gamma=1.0, record_every=1 if traj_path is not None else 0, controller=controller,
-                     epsilon=epsilon, action_noise=action_noise, state_noise=state_noise, seed=seed, **extra)
+    if adversary is not None:
+        res = pi.adversary_rollout(starts, steps, controller=adversary, gamma=1.0,
+                                   record_every=1 if traj_path is not None else 0, **extra)
+    else:
+        res = pi.rollout(starts, steps, gamma=1.0, record_every=1 if traj_path is not None else 0, controller=controller,
+                         epsilon=epsilon, action_noise=action_noise, state_noise=state_noise, seed=seed, **extra)
     for ep in range(episodes):
         outcome = "terminated" if res.terminated[ep] else f"{steps} steps"
         final = "  ".join(f"{v:+.4f}" for v in res.states[ep])
@@ -266,7 +292,8 @@ def ignored_flags(args) -> list:
                             ("--controller", harness and args.controller != "policy"),
                             ("--epsilon", harness and args.epsilon != 0.0),
                             ("--action-noise", harness and args.action_noise != 0.0),
-                            ("--state-noise", harness and args.state_noise is not None)) if on]
+                            ("--state-noise", harness and args.state_noise is not None),
+                            ("--adversary", harness and args.adversary is not None)) if on]
 
 
 def main(env_name: str, default_save: str, argv=None):
@@ -292,14 +319,15 @@ def main(env_name: str, default_save: str, argv=None):
         print(f"[+] Loading existing policy from {path}")
         pi = cls.load(path)
         print(f"[{env_name}] {pi.n_states:,} states, {pi.n_actions} actions; use --retrain to recompute")
-        if training_noise_requested(args):
+        if training_noise_requested(args) and not (args.rollout and args.adversary is not None):   # (there they name the set)
             print(f"[{env_name}] note: --train-action-noise, --train-state-noise and --train-noise-points act on training "
-                  "only; a saved policy was loaded, so they had no effect")
+                  "only; a saved policy was loaded, so they had no effect"
+                  + (" (nor had --train-risk)" if args.train_risk != "expected" else ""))
     else:
         print("[*] Training new policy...")
         pi = train(env_name, args.bins, path, value_iteration=args.value_iteration, coarse_bins=args.coarse_bins,
                    train_action_noise=args.train_action_noise, train_state_noise=args.train_state_noise,
-                   train_noise_points=args.train_noise_points, **kw)
+                   train_noise_points=args.train_noise_points, train_risk=args.train_risk, **kw)
     lookahead_set = None
     if args.rollout and args.controller == "expected" and getattr(pi, "disturbances", None) is None:
         lookahead_set = training_disturbances(env_name, args.action_noise, args.state_noise, args.train_noise_points)
@@ -307,9 +335,17 @@ def main(env_name: str, default_save: str, argv=None):
             sys.exit(f"[{env_name}] --controller expected needs a disturbance set: train with --train-action-noise / "
                      "--train-state-noise, load an archive that carries one, or give --action-noise / --state-noise")
         print(f"[{env_name}] expected lookahead over {lookahead_set.K} disturbance points of the rollout's noise")
+    if args.rollout and args.adversary is not None:
+        # the set the adversary chooses from: what the --train-*-noise flags name when given, else the archive's own
+        named = training_disturbances(env_name, args.train_action_noise, args.train_state_noise, args.train_noise_points)
+        lookahead_set = named if named is not None else getattr(pi, "disturbances", None)
+        if lookahead_set is None:
+            sys.exit(f"[{env_name}] --adversary needs a disturbance set: load an archive trained with --train-action-noise / "
+                     "--train-state-noise, or give those flags")
+        print(f"[{env_name}] adversary over {lookahead_set.K} disturbance points, controller: {args.adversary}")
     if args.rollout:
         evaluate(env_name, pi, args.episodes, args.steps, args.seed, start_x=getattr(args, "start_x", None),
                  traj_path=Path("results") / "last_trajectory.npz" if env_name == "double_cartpole_swingup" else None,
                  controller=args.controller, epsilon=args.epsilon, action_noise=args.action_noise,
-                 state_noise=args.state_noise, disturbances=lookahead_set)
+                 state_noise=args.state_noise, disturbances=lookahead_set, adversary=args.adversary)
     return pi

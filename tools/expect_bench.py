@@ -16,9 +16,14 @@ Disturbances.uniform of the rollout's noise (solver.set_disturbances) — then b
 solver.rollout(action_noise=..., state_noise=...) with the same noise, seed and starts, 4 096 episodes of --steps
 steps: mean return and the share of episodes that terminated.
 
+--risk worst adds the WORST-CASE backup over the same sets (pi_robust_*, the same module; solver.set_disturbances(d,
+risk="worst")): the sweep table gains C2 (pendulum 200^2 x 21), the worst-case sweep timed in the same alternation, and the
+spread (max - min) of the expectation sweep's own --repeat samples, the margin the two are compared within; the closed
+loop trains a third, worst-case table under the same caps.  The table then goes to profiles/r16/robust.txt.
+
 The driver (no --part) runs every part in a child process of its own under `timeout -k 10`, one after the other, and
 stops at the first child that fails.  The table goes to --out.
-usage: python tools/expect_bench.py [--out profiles/r11/expected_backup.txt] [--repeat 5] [--steps 1000]
+usage: python tools/expect_bench.py [--out profiles/r11/expected_backup.txt] [--repeat 5] [--steps 1000] [--risk worst]
 """
 import argparse
 import json
@@ -29,7 +34,7 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
-CONFIGS = {"c3": ("cartpole_swingup", 50), "c4": ("double_pendulum_swingup", 80), "c5": ("double_cartpole", 25)}
+CONFIGS = {"c2": ("pendulum", 200), "c3": ("cartpole_swingup", 50), "c4": ("double_pendulum_swingup", 80), "c5": ("double_cartpole", 25)}
 # closed loop: env -> (bins, action noise as a share of the action range, state noise per dimension in cell widths,
 # training caps).  Velocities are disturbed (a push), positions are not.
 LOOPS = {"pendulum": (200, 0.2, (0.0, 1.0), dict(max_eval_iter=2000, max_pi_iter=30)),
@@ -69,11 +74,11 @@ def part_sweeps(args):
     gamma = float(np.float32(cls.CONFIG["gamma"]))
     p = [t.data_ptr() for t in (Va, Vb, pol)]
 
-    def calls(expect):
-        e = eng
-        return {"eval": (lambda: (e.expect_eval_sweeps if expect else e.eval_sweeps)(p[0], p[1], p[2], 0, 0, n, gamma, 4), 4),
-                "improve": (lambda: (e.expect_improve_sweep if expect else e.improve_sweep)(p[0], p[2], 0, 0, n, gamma), 1),
-                "value": (lambda: (e.expect_value_sweep if expect else e.value_sweep)(p[0], p[1], p[2], 0, 0, n, gamma), 1)}
+    def calls(prefix):                                         # "": deterministic, "expect_", "robust_"
+        fn = lambda name: getattr(eng, prefix + name)          # noqa: E731
+        return {"eval": (lambda: fn("eval_sweeps")(p[0], p[1], p[2], 0, 0, n, gamma, 4), 4),
+                "improve": (lambda: fn("improve_sweep")(p[0], p[2], 0, 0, n, gamma), 1),
+                "value": (lambda: fn("value_sweep")(p[0], p[1], p[2], 0, 0, n, gamma), 1)}
 
     def timed(fn):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -88,14 +93,21 @@ def part_sweeps(args):
     for label, d in _sets(D, cell, float(acts.max() - acts.min())):
         eng.set_disturbances(d.action_offsets, d.state_offsets, d.weights)
         for kind in ("eval", "improve", "value"):
-            (det, per), (exp, _) = calls(False)[kind], calls(True)[kind]
+            (det, per), (exp, _) = calls("")[kind], calls("expect_")[kind]
+            worst = calls("robust_")[kind][0] if args.risk == "worst" else None
             det(), exp()                                       # warm-up of both paths
-            t_det, t_exp = [], []
+            if worst:
+                worst()
+            t_det, t_exp, t_worst = [], [], []
             for _ in range(args.repeat):                       # alternating, so that drift hits both alike
                 t_det.append(timed(det) / per)
                 t_exp.append(timed(exp) / per)
+                if worst:
+                    t_worst.append(timed(worst) / per)
             rows.append({"set": label, "K": d.K, "kind": kind, "det_ms": min(t_det), "expect_ms": min(t_exp),
                          "det_ms_all": t_det, "expect_ms_all": t_exp})
+            if worst:
+                rows[-1].update({"worst_ms": min(t_worst), "worst_ms_all": t_worst})
     print(json.dumps({"config": args.config, "env": env, "bins": bins, "D": D, "actions": len(acts), "states": n, "rows": rows}))
 
 
@@ -116,10 +128,12 @@ def part_loop(args):
     cfg = CudaPIConfig(**{**cls.CONFIG, **caps})
     starts = cls.start_states(np.random.default_rng(args.seed), 4096)
     out = {"env": env, "bins": bins, "action_noise": a_noise, "state_noise": x_noise, "caps": caps, "steps": args.steps, "runs": {}}
-    for label, d in (("nominal", None), ("noise-aware", Disturbances.uniform(len(tabs), state_noise=x_noise, action_noise=a_noise))):
+    rule = Disturbances.uniform(len(tabs), state_noise=x_noise, action_noise=a_noise)
+    tables = [("nominal", None, {}), ("noise-aware", rule, {})] + ([("worst-case", rule, {"risk": "worst"})] if args.risk == "worst" else [])
+    for label, d, risk in tables:
         solver = envs.make(env, bins, cfg, device="cuda:0", transport=False)
         if d is not None:
-            solver.set_disturbances(d)
+            solver.set_disturbances(d, **risk)
         t0 = time.perf_counter()
         solver.run()
         seconds = time.perf_counter() - t0
@@ -138,7 +152,8 @@ def main():
     ap.add_argument("--part", choices=("sweeps", "loop"), default=None)
     ap.add_argument("--config", choices=tuple(CONFIGS), default="c3")
     ap.add_argument("--env", choices=tuple(LOOPS), default="pendulum")
-    ap.add_argument("--out", type=Path, default=ROOT / "profiles" / "r11" / "expected_backup.txt")
+    ap.add_argument("--out", type=Path, default=None)
+    ap.add_argument("--risk", choices=("expected", "worst"), default="expected")
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=42)
@@ -148,11 +163,16 @@ def main():
         return part_sweeps(args)
     if args.part == "loop":
         return part_loop(args)
-    lines = ["expected Bellman backup over a disturbance set (tools/expect_bench.py)" + (f", commit {args.commit}" if args.commit else ""),
+    worst = args.risk == "worst"
+    if args.out is None:
+        args.out = ROOT / "profiles" / ("r16/robust.txt" if worst else "r11/expected_backup.txt")
+    lines = [("worst-case and expected" if worst else "expected") + " Bellman backup over a disturbance set (tools/expect_bench.py"
+             + (" --risk worst)" if worst else ")") + (f", commit {args.commit}" if args.commit else ""),
              "", "sweep time per kind, ms per sweep, best of %d (deterministic = csrc/pi_sweep_kernels.hip, byte-identical to the parent's)" % args.repeat,
-             f"{'config':28s} {'set':26s} {'kind':8s} {'det ms':>9s} {'expect ms':>10s} {'x det':>7s} {'x K det':>8s}"]
-    common = ["--repeat", str(args.repeat), "--steps", str(args.steps), "--seed", str(args.seed)]
-    parts = [("sweeps", ["--config", c]) for c in CONFIGS] + [("loop", ["--env", e]) for e in LOOPS]
+             f"{'config':28s} {'set':26s} {'kind':8s} {'det ms':>9s} {'expect ms':>10s} {'x det':>7s} {'x K det':>8s}"
+             + (f" {'spread':>8s} {'worst ms':>9s} {'- expect':>9s}" if worst else "")]
+    common = ["--repeat", str(args.repeat), "--steps", str(args.steps), "--seed", str(args.seed), "--risk", args.risk]
+    parts = [("sweeps", ["--config", c]) for c in CONFIGS if worst or c != "c2"] + [("loop", ["--env", e]) for e in LOOPS]
     loops = []
     for part, extra in parts:
         cmd = ["timeout", "-k", "10", str(CHILD_SECONDS), sys.executable, str(Path(__file__).resolve()), "--part", part] + extra + common
@@ -168,6 +188,9 @@ def main():
                 ratio = row["expect_ms"] / row["det_ms"]
                 lines.append(f"{name:28s} {row['set']:26s} {row['kind']:8s} {row['det_ms']:9.4f} {row['expect_ms']:10.4f} "
                              f"{ratio:7.2f} {ratio / row['K']:8.2f}")
+                if worst:
+                    spread = max(row["expect_ms_all"]) - min(row["expect_ms_all"])
+                    lines[-1] += f" {spread:8.4f} {row['worst_ms']:9.4f} {row['worst_ms'] - row['expect_ms']:+9.4f}"
         else:
             loops.append(r)
     for r in loops:

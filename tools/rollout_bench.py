@@ -44,7 +44,13 @@ launch, the loop it replaces (per step a query on each handle, the words of pi_i
 mixing as torch ops), the deterministic hybrid rollout and the single-policy stochastic rollout of the same batch — a sample
 of a fused path is ten calls back to back —, then the registers and scratch of the kernel and of the hybrid kernel beside
 it.  The table is written to --out.
-usage: python tools/rollout_bench.py [--hybrid | --greedy | --stochastic | --expected | --hybrid --stochastic] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
+--adversary: the adversary rollouts (pi_infer_rollout_adversary, csrc/pi_adversary_kernels.hip): per config the fused
+adversary rollout under the policy table and under the robust lookahead at K = 9 and 27 beside the expected-greedy rollout of
+the same batch and, for the robust controller, the step-by-step loop it replaces (robust() + torch + pi_probe_step per step)
+with a comparison of the bits, then the closed loop of tools/expect_bench.py's two settings — nominal, noise-aware and worst-case tables
+under the sampled noise and under the adversary.
+
+usage: python tools/rollout_bench.py [--hybrid | --greedy | --stochastic | --expected | --adversary | --hybrid --stochastic] [--out profiles/r07/rollout.txt] [--commit HASH] [--steps 1000] [--repeat 3]
 """
 import argparse
 import json
@@ -59,6 +65,7 @@ sys.path.insert(0, str(ROOT))
 CONFIGS = {"c2": ("pendulum", 200), "c3": ("cartpole_swingup", 50), "c5": ("double_cartpole", 25)}
 BATCHES = (5, 4096, 262144)
 CHILD_SECONDS = 420
+DEFAULT_OUT = str(ROOT / "profiles" / "r07" / "rollout.txt")
 
 
 def child(args):
@@ -1080,9 +1087,192 @@ def driver(args):
     print(out.read_text())
 
 
+# ── --adversary: the adversary rollouts (pi_infer_rollout_adversary, csrc/pi_adversary_kernels.hip) ───────────────────────
+def adversary_child(args):
+    """Timing on one config: 4 096 episodes x --steps steps on a random V and policy, K = 9 and 27: the adversary rollout
+    under both controllers beside the expected-greedy rollout (no noise) of the same batch, better of --repeat; and, for
+    the robust controller, the step-by-step loop it replaces — per step one robust() query, the adversary's answer applied
+    with torch (the clamp of a + da_k*, dx_k* on steps that are not done) and one pi_probe_step launch — with its bits."""
+    import numpy as np
+    import torch
+    import utils.barycentric as B
+    from itertools import product
+    from dynamicprogramming_amd import _native, envs
+    from dynamicprogramming_amd.noise import Disturbances
+    env, bins = CONFIGS[args.config]
+    cls = envs.ENVS[env]
+    tabs = [np.asarray(t, np.float32) for t in cls.bins_space(bins).values()]
+    D = len(tabs)
+    shape = np.array([len(t) for t in tabs], np.int32)
+    lo, hi = np.array([t.min() for t in tabs], np.float32), np.array([t.max() for t in tabs], np.float32)
+    strides = np.array([int(np.prod(shape[d + 1:])) for d in range(D)], np.int32)
+    bits = np.array(list(product([0, 1], repeat=D)), dtype=np.int32)
+    acts = np.asarray(cls.ACTIONS, np.float32)
+    rng = np.random.default_rng(0)
+    n = int(np.prod(shape.astype(np.int64)))
+    policy = rng.integers(0, len(acts), size=n, dtype=np.int32)
+    V = (30.0 * rng.standard_normal(n, dtype=np.float32)).astype(np.float32)
+    a_noise = float(np.float32(0.1) * (acts.max() - acts.min()))
+    s_noise = (np.float32(0.002) * (hi - lo)).astype(np.float32)
+    one, two = np.zeros(D), np.zeros(D)
+    one[1] = two[0] = two[1] = 1.0
+    sets = {9: Disturbances.uniform(D, state_noise=one * s_noise, action_noise=a_noise),
+            27: Disturbances.uniform(D, state_noise=two * s_noise, action_noise=a_noise)}
+    dev = torch.device("cuda:0")
+    starts = torch.from_numpy((lo + (hi - lo) * rng.random((args.m, D), dtype=np.float32)).astype(np.float32)).to(dev)
+    dp = B.DevicePolicy(policy, acts, lo, hi, shape, strides, bits, device=dev)
+    dp.set_dynamics(envs.dynamics_source(env))
+    dp.set_values(V)
+    dp.set_expected_greedy()
+    dp.set_robust()
+    eng = _native.Engine(D, shape, lo, hi, tabs, acts, device=0)
+    eng.compile(envs.dynamics_source(env))
+    st = torch.cuda.current_stream(dev).cuda_stream
+    m = args.m
+    a_lo, a_hi = torch.tensor(float(acts.min()), device=dev), torch.tensor(float(acts.max()), device=dev)
+
+    def loop(d):                                          # the robust controller against the adversary, one launch per piece
+        da = torch.from_numpy(d.action_offsets).to(dev)
+        dx = torch.from_numpy(d.state_offsets).to(dev)
+        states = starts.clone()
+        nxt = torch.empty_like(states)
+        rew = torch.empty(m, dtype=torch.float32, device=dev)
+        done = torch.empty(m, dtype=torch.uint8, device=dev)
+        ret = torch.zeros(m, dtype=torch.float32, device=dev)
+        length = torch.zeros(m, dtype=torch.int32, device=dev)
+        ended = torch.zeros(m, dtype=torch.bool, device=dev)
+        won = torch.ones((), dtype=torch.bool, device=dev)
+        for t in range(args.steps):
+            _, act, _, worst = dp.robust(states, 0.99)
+            won = won & (worst >= 0).all()                # (no winner: the fused kernel keeps action 0's step, which this
+            k = worst.clamp(min=0).to(torch.int64)        # loop cannot know — never the case on a finite V)
+            push = da[k]
+            act = torch.where(push == 0, act, torch.fmin(torch.fmax(act + push, a_lo), a_hi)).contiguous()
+            eng.probe_step(states.data_ptr(), act.data_ptr(), nxt.data_ptr(), rew.data_ptr(), done.data_ptr(), m, st)
+            shift = dx[k]
+            moved = torch.where(shift != 0, nxt + shift, nxt)
+            nxt2 = torch.where((done == 0)[:, None], moved, nxt)
+            run = ~ended
+            ret = torch.where(run, ret + rew, ret)
+            states = torch.where(run[:, None], nxt2, states)
+            length = torch.where(run, torch.full_like(length, t + 1), length)
+            ended = ended | (run & (done != 0))
+        assert bool(won.item()), "an episode had no winning action: the loop is not the fused rollout there"
+        return B.RolloutResult(states, ret, length, ended, None)
+
+    def timed(fn):
+        best = float("inf")
+        fn()
+        for _ in range(args.repeat):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0.record()
+            res = fn()
+            t1.record()
+            torch.cuda.synchronize()
+            best = min(best, t0.elapsed_time(t1))
+        return best, float(res.lengths.float().mean())
+    rows = []
+    for K, d in sets.items():
+        dp.set_disturbances(d)
+        row = {"K": K}
+        for label, fn in (("expected", lambda: dp.rollout(starts, args.steps, controller="expected", lookahead_gamma=0.99)),
+                          ("adv_policy", lambda: dp.adversary_rollout(starts, args.steps, controller="policy", lookahead_gamma=0.99)),
+                          ("adv_robust", lambda: dp.adversary_rollout(starts, args.steps, controller="robust", lookahead_gamma=0.99))):
+            row[label + "_ms"], row[label + "_len"] = timed(fn)
+        a, b = dp.adversary_rollout(starts, args.steps, controller="robust", lookahead_gamma=0.99), loop(d)
+        torch.cuda.synchronize()
+        row["same_bits"] = bool(torch.equal(a.states.view(torch.int32), b.states.view(torch.int32))
+                                and torch.equal(a.returns.view(torch.int32), b.returns.view(torch.int32))
+                                and torch.equal(a.lengths, b.lengths) and torch.equal(a.terminated != 0, b.terminated))
+        row["loop_ms"], row["loop_len"] = timed(lambda: loop(d))
+        row["launches_loop"] = 2 * args.steps
+        rows.append(row)
+    print(json.dumps({"config": args.config, "env": env, "bins": bins, "D": D, "actions": len(acts), "m": args.m,
+                      "steps": args.steps, "rows": rows}))
+    dp.close()
+    eng.close()
+
+
+def adversary_loop_child(args):
+    """Closed loop on one env of tools/expect_bench.py's settings: the nominal, noise-aware and worst-case tables, each under
+    the sampled noise planned for and under the adversary over the same set (its policy table acting): mean return and the
+    share of episodes that terminated."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT / "tools"))
+    from expect_bench import LOOPS
+    from dynamicprogramming_amd import envs
+    from dynamicprogramming_amd.noise import Disturbances
+    from dynamicprogramming_amd.solver import CudaPIConfig
+    env = args.env
+    bins, a_share, x_cells, caps = LOOPS[env]
+    cls = envs.ENVS[env]
+    tabs = [np.asarray(b, np.float64) for b in cls.bins_space(bins).values()]
+    cell = np.array([(t.max() - t.min()) / (len(t) - 1) for t in tabs])
+    acts = np.asarray(cls.ACTIONS, np.float64)
+    a_noise = a_share * float(acts.max() - acts.min())
+    x_noise = [float(c * w) for c, w in zip(x_cells, cell)]
+    rule = Disturbances.uniform(len(tabs), state_noise=x_noise, action_noise=a_noise)
+    starts = cls.start_states(np.random.default_rng(args.seed), args.m)
+    out = {"env": env, "bins": bins, "K": rule.K, "steps": args.loop_steps, "m": args.m, "runs": {}}
+    for label, d, risk in (("nominal", None, {}), ("noise-aware", rule, {}), ("worst-case", rule, {"risk": "worst"})):
+        solver = envs.make(env, bins, CudaPIConfig(**{**cls.CONFIG, **caps}), device="cuda:0", transport=False)
+        if d is not None:
+            solver.set_disturbances(d, **risk)
+        solver.run()
+        run = {}
+        for world, res in (("sampled", solver.rollout(starts, args.loop_steps, gamma=1.0, action_noise=a_noise, state_noise=x_noise, seed=args.seed)),
+                           ("adversary", solver.adversary_rollout(starts, args.loop_steps, controller="policy", disturbances=rule)),
+                           ("adversary_robust", solver.adversary_rollout(starts, args.loop_steps, controller="robust", disturbances=rule))):
+            run[world] = {"mean_return": float(np.mean(res.returns)), "terminated_share": float(np.mean(res.terminated)),
+                          "mean_length": float(np.mean(res.lengths))}
+        out["runs"][label] = run
+    print(json.dumps(out))
+
+
+def adversary_driver(args):
+    if args.out == DEFAULT_OUT:                            # not the first rollout profile: a file of this part's own
+        args.out = str(ROOT / "profiles" / "r16" / "adversary_rollouts.txt")
+    me = [sys.executable, str(Path(__file__).resolve())]
+    lines = [f"adversary rollouts (tools/rollout_bench.py --adversary), MI355X, commit {args.commit}", "",
+             f"timing: {args.m} episodes x {args.steps} steps, random V and policy, ms per launch (better of {args.repeat}) and mean "
+             "episode length",
+             f"{'config':28s} {'K':>3s} {'expected-greedy':>16s} {'len':>7s} {'adversary, table':>17s} {'len':>7s} {'adversary, robust':>18s} {'len':>7s}"
+             f" {'its per-step loop':>18s} {'same bits':>10s}"]
+    jobs = [("timing", ["--config", c]) for c in CONFIGS] + [("loop", ["--env", e]) for e in ("pendulum", "cartpole_swingup")]
+    loops = []
+    for kind, extra in jobs:
+        res = subprocess.run(["timeout", "-k", "10", str(CHILD_SECONDS), *me, "--child", "--adversary", "--part", kind, *extra,
+                              "--steps", str(args.steps), "--repeat", str(args.repeat), "--m", str(args.m),
+                              "--loop-steps", str(args.loop_steps), "--seed", str(args.seed)], capture_output=True, text=True)
+        print(f"[rollout_bench --adversary] {kind} {' '.join(extra)}: status {res.returncode}", flush=True)
+        if res.returncode != 0:
+            lines.append(f"NOT MEASURED: {kind} {' '.join(extra)} ended with status {res.returncode}: {res.stderr.strip()[-400:]}")
+            break
+        r = json.loads(res.stdout.strip().splitlines()[-1])
+        if kind == "timing":
+            name = f"{r['config']} {r['env']} {r['bins']}^{r['D']} x {r['actions']}"
+            for row in r["rows"]:
+                lines.append(f"{name:28s} {row['K']:3d} {row['expected_ms']:16.3f} {row['expected_len']:7.1f} {row['adv_policy_ms']:17.3f} "
+                             f"{row['adv_policy_len']:7.1f} {row['adv_robust_ms']:18.3f} {row['adv_robust_len']:7.1f} "
+                             f"{row['loop_ms']:18.3f} {str(row['same_bits']):>10s}")
+        else:
+            loops.append(r)
+    for r in loops:
+        lines += ["", f"closed loop: {r['env']} {r['bins']} bins, the {r['K']}-point rule of tools/expect_bench.py, {r['m']} episodes of "
+                      f"{r['steps']} steps: mean return / share terminated",
+                  f"{'table':12s} | {'sampled noise':>22s} | {'adversary, its table':>22s} | {'adversary, robust lookahead on its V':>36s}"]
+        for label, run in r["runs"].items():
+            cell = lambda w: f"{run[w]['mean_return']:12.3f} / {run[w]['terminated_share']:.4f}"      # noqa: E731
+            lines.append(f"{label:12s} | {cell('sampled'):>22s} | {cell('adversary'):>22s} | {cell('adversary_robust'):>36s}")
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "r07" / "rollout.txt"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
     ap.add_argument("--commit", default="unknown")
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--repeat", type=int, default=3)
@@ -1092,6 +1282,7 @@ def main():
     ap.add_argument("--greedy", action="store_true")
     ap.add_argument("--stochastic", action="store_true")
     ap.add_argument("--expected", action="store_true")
+    ap.add_argument("--adversary", action="store_true")
     ap.add_argument("--part", choices=("timing", "loop"), default="timing")
     ap.add_argument("--env", default="pendulum")
     ap.add_argument("--seed", type=int, default=42)
@@ -1105,6 +1296,8 @@ def main():
         (greedy_child if args.child else greedy_driver)(args)
     elif args.stochastic:
         (stochastic_child if args.child else stochastic_driver)(args)
+    elif args.adversary:
+        ((adversary_child if args.part == "timing" else adversary_loop_child) if args.child else adversary_driver)(args)
     elif args.expected:
         ((expected_child if args.part == "timing" else expected_loop_child) if args.child else expected_driver)(args)
     elif args.hybrid:

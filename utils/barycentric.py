@@ -123,6 +123,7 @@ class DevicePolicy:
     _greedy_actions = None                     # the table of the last set_greedy; None: no greedy module
     _stochastic_actions = None                 # the table of the last set_stochastic; None: no stochastic module
     _expected_actions = None                   # the table of the last set_expected_greedy; None: no such module
+    _robust_actions = None                     # the table of the last set_robust; None: no such module
     _disturbances = None                       # the set of the last set_disturbances
     _partner_stochastic = None                 # (serial, secondary, table) HybridPolicy built this handle's noisy module for
 
@@ -189,6 +190,7 @@ class DevicePolicy:
         self._greedy_actions = None                                           # the library dropped the greedy module
         self._stochastic_actions = None                                       # ... and the stochastic one
         self._expected_actions = None                                         # ... and the expected-greedy one
+        self._robust_actions = None                                           # ... and the adversary one
         return log
 
     def _rollout_buffers(self, states, steps, record_every, need_policy=True):
@@ -301,6 +303,58 @@ class DevicePolicy:
         ``set_values`` and ``set_disturbances`` only replace what it reads."""
         return self._build_module("set_expected_greedy", "the expected controller", action_space,
                                   self._engine.set_expect_greedy, "_expected_actions")
+
+    def set_robust(self, action_space=None) -> str:
+        """Build the robust lookahead and the adversary rollout — the worst case over the set of ``set_disturbances`` on
+        the value function of ``set_values`` through the plugin of ``set_dynamics`` — over ``action_space`` (default: the
+        table the constructor was given; its extremes clamp ``a + da_k``); returns the compiler's log.  ``set_dynamics``
+        drops it again; ``set_values`` and ``set_disturbances`` only replace what it reads."""
+        return self._build_module("set_robust", "the robust controller", action_space, self._engine.set_robust,
+                                  "_robust_actions")
+
+    def _need_robust(self) -> None:
+        if self._robust_actions is None:
+            raise RuntimeError("the robust controller needs set_robust() (again after every set_dynamics)")
+        if self._disturbances is None:
+            raise RuntimeError("the robust controller needs a disturbance set: call set_disturbances(...) first")
+
+    def robust(self, states, gamma, q_values=False):
+        """The robust one-step lookahead at ``states`` (m, D) in ONE kernel launch — the device twin of
+        ``dynamicprogramming_amd.noise.robust_action``, same bits: ``(best_index int32, action, q_best, worst int32)`` and,
+        with ``q_values=True``, ``Q (m, n_actions)``; ``worst`` is the point of the set the adversary answers the winner
+        with, -1 when no action won.  In/out conventions of ``greedy``.  After ``set_robust`` and ``set_disturbances``."""
+        self._need_robust()
+        torch = self._torch
+        on_device, d_pts, m = self._device_states(states)
+        best = torch.empty(m, dtype=torch.int32, device=self.device)
+        act = torch.empty(m, dtype=torch.float32, device=self.device)
+        qb = torch.empty(m, dtype=torch.float32, device=self.device)
+        worst = torch.empty(m, dtype=torch.int32, device=self.device)
+        out = [best, act, qb, worst]
+        if q_values:
+            out.append(torch.empty((m, len(self._robust_actions)), dtype=torch.float32, device=self.device))
+        self._engine.robust(d_pts.data_ptr(), m, gamma, d_best=best.data_ptr(), d_action=act.data_ptr(),
+                            d_q_best=qb.data_ptr(), d_q_all=out[4].data_ptr() if q_values else 0,
+                            d_worst=worst.data_ptr(), stream=self._stream())
+        return tuple(out) if on_device else tuple(x.cpu().numpy() for x in out)
+
+    def adversary_rollout(self, states, steps, gamma=1.0, record_every=0, controller="policy", lookahead_gamma=None):
+        """Closed-loop episodes in which the disturbance is chosen AGAINST the controller, in ONE kernel launch — the
+        device twin of ``dynamicprogramming_amd.noise.adversary_rollout``, same bits.  ``controller="policy"``: the
+        interpolated action of the policy table, then the worst point of the set for it (the fold of the worst-case
+        sweeps on the value function, discount ``lookahead_gamma``, required) moves the episode and gives its reward and
+        flag.  ``controller="robust"``: the robust lookahead and the adversary's answer to its winner; no policy table
+        needed.  No random numbers.  The outputs and in/out conventions are ``rollout``'s.  After ``set_robust`` and
+        ``set_disturbances``."""
+        if controller not in ("policy", "robust"):
+            raise ValueError(f"controller must be 'policy' or 'robust', not {controller!r}")
+        if lookahead_gamma is None:
+            raise ValueError("adversary_rollout needs lookahead_gamma, the discount the value function was solved with")
+        self._need_robust()
+        on_device, d_start, m, steps, out, outs = \
+            self._rollout_buffers(states, steps, record_every, need_policy=controller == "policy")
+        self._engine.rollout_adversary(d_start.data_ptr(), m, steps, lookahead_gamma, int(controller == "robust"), gamma, **outs)
+        return _result(RolloutResult, on_device, out)
 
     def _build_module(self, setter, who, action_space, build, record, needs_values=True) -> str:
         """What set_greedy, set_stochastic and set_expected_greedy do: the table (default: the constructor's), the
