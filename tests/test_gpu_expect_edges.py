@@ -112,9 +112,22 @@ def _all_kinds(dv, c, twin, what, ranges, check=_check, same=H.assert_bits_equal
             check(got, _expected(c, twin, kind, a, b), kind, f"{what} [{a}, {b})")
 
 
+FOLD_NAMES = {"expect": "expectation", "robust": "worst-case"}
+
+
+def _fold(fold):
+    """(device class, whole-grid twin of (grid, set), risk of the twins) of the expectation sweeps ("expect") or of the
+    worst-case sweeps ("robust": tests/test_gpu_robust_edges.py runs section 0 and section e of this file with it)."""
+    if fold == "expect":
+        return _Device, _twin, "expected"
+    from tests import test_gpu_robust as R
+    assert fold == "robust"
+    return R._Sweeps, R._twin, "worst"
+
+
 # ---- 0. the checked handle's report ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("grid", FORM_GRIDS)
-def test_checked_handle_reports_what_the_expectation_sweeps_met(grid, cuda_device, monkeypatch):
+def test_checked_handle_reports_what_the_expectation_sweeps_met(grid, cuda_device, monkeypatch, fold="expect"):
     """PI_MI355_DEBUG=1 with a set installed: clean expectation sweeps of the three kinds report nothing and give the
     unchecked handle's bits; three corrupt policy entries (one past the end, -1, 2^30) met by expect_eval_sweeps are
     reported — 3 violations, kind 1, `where` one of the three states — and contained: V' is that of the policy with 0 at
@@ -122,14 +135,15 @@ def test_checked_handle_reports_what_the_expectation_sweeps_met(grid, cuda_devic
     together 6.  The handle's push module is loaded as well (Option.BUILD_PUSH), so the report walks all three modules;
     no kernel of the push module runs on one device: that third of the report is covered for a clean tally only."""
     monkeypatch.delenv("PI_MI355_DEBUG", raising=False)
+    Device, twin_of, risk = _fold(fold)
     c = _case(grid)
     n = c["n"]
-    twin = _twin(grid, "S2")
+    twin = twin_of(grid, "S2")
     d = twin[0]
     plain = _engine(c, cuda_device)
     assert plain.info(Info.DEBUG_CHECKS) == 0
     _install(plain, d)
-    dv = _Device(plain, c, cuda_device)
+    dv = Device(plain, c, cuda_device)
     want = {kind: dv.sweep(kind, 0, n) for kind in KINDS}
     plain.close()
     monkeypatch.setenv("PI_MI355_DEBUG", "1")
@@ -137,7 +151,7 @@ def test_checked_handle_reports_what_the_expectation_sweeps_met(grid, cuda_devic
     assert chk.info(Info.DEBUG_CHECKS) == 1 and "#define PI_DEBUG_BOUNDS 1" in chk.kernel_source(c["src"])
     _install(chk, d)
     chk.set_option(Option.BUILD_PUSH, 1)
-    dv = _Device(chk, c, cuda_device)
+    dv = Device(chk, c, cuda_device)
     clean = {"violations": 0, "kind": 0, "where": 0, "value": 0}
     for kind in KINDS:
         got = dv.sweep(kind, 0, n)
@@ -154,7 +168,8 @@ def test_checked_handle_reports_what_the_expectation_sweeps_met(grid, cuda_devic
     fixed = c["pol"].copy()
     fixed[where] = 0                                        # what the checked kernel substitutes
     e_Vb = np.array(twin[1])
-    e_Vb[where] = noise.expected_q(c["chk"].step, c["states"][where], c["acts"][0], d, c["V"], c["acts"], *c["grid"], c["gamma"])
+    e_Vb[where] = noise.expected_q(c["chk"].step, c["states"][where], c["acts"][0], d, c["V"], c["acts"], *c["grid"], c["gamma"],
+                                   risk=risk)
     got = dv.sweep("eval", 0, n, pol=bad)
     rep = chk.debug_report()
     assert rep["violations"] == 3 and rep["kind"] == 1 and rep["where"] in where, rep
@@ -554,11 +569,14 @@ def test_sets_with_edge_entries(size, cuda_device):
 
 
 # ---- e. large handles --------------------------------------------------------------------------------------------------
-def _large_twin(g, d, coords, pol_at, V_user):
+def _large_twin(g, d, coords, pol_at, V_user, risk="expected"):
     """The twin at sample points (node coordinates): evaluation under the policy's action; argmax and maximum."""
     grid = g.meta
-    V_eval = noise.expected_q(g.chk.step, coords, g.acts[pol_at], d, V_user, g.acts, *grid, g.gamma)
-    best, _, best_q = noise.expected_greedy_action(g.chk.step, coords, d, V_user, g.acts, *grid, g.gamma)
+    V_eval = noise.expected_q(g.chk.step, coords, g.acts[pol_at], d, V_user, g.acts, *grid, g.gamma, risk=risk)
+    if risk == "worst":                                      # the argmax of the worst-case sweeps' twins
+        best, best_q = noise._argmax(g.chk.step, coords, np.arange(len(coords)), d, V_user, g.acts, grid, g.gamma, risk)
+    else:
+        best, _, best_q = noise.expected_greedy_action(g.chk.step, coords, d, V_user, g.acts, *grid, g.gamma)
     return V_eval, best, best_q
 
 
@@ -568,7 +586,7 @@ def _large_set(g):
     return _make_set("S2", g.D, cell, g.acts)
 
 
-def test_large_default_handle_64_4(cuda_device):
+def test_large_default_handle_64_4(cuda_device, fold="expect", sample_shift=0):
     """double_pendulum_swingup 64^4 (2^24 states): the unit's own sweeps run 1024 / 512 threads and the pair table by
     default (the strip schedule is the library's choice for 6-D grids of this size only: Info.STRIP_STATES is 0 here, and
     is asserted to be); the expectation kernels keep 256 threads, one chunk, the slab schedule and V itself.  S2,
@@ -578,6 +596,7 @@ def test_large_default_handle_64_4(cuda_device):
     peak device memory as torch counts it 0.4 GiB."""
     from tests.test_gpu_addr64 import _free, _grid, _points, _report_peak, _seeded_state, _torch
     torch = _torch()
+    risk = _fold(fold)[2]
     torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
     name = "double_pendulum_swingup"
@@ -590,23 +609,23 @@ def test_large_default_handle_64_4(cuda_device):
         d = _large_set(g)
         _install(eng, d)
         Vh, polh, _, d_V, d_pol, _ = _seeded_state(g, 23, None, cuda_device, scale=30.0)
-        idx = np.unique(np.concatenate([np.random.default_rng(2023).integers(0, n, size=1 << 16, dtype=np.int64),
+        idx = np.unique(np.concatenate([np.random.default_rng(2023).integers(0, n, size=(1 << 16) >> sample_shift, dtype=np.int64),
                                         np.arange(n - (1 << 12), n, dtype=np.int64)]))
         flat_user, coords = _points(g, idx)
-        e_eval, e_best, e_best_q = _large_twin(g, d, coords, polh[flat_user], Vh)
+        e_eval, e_best, e_best_q = _large_twin(g, d, coords, polh[flat_user], Vh, risk)
         d_idx = torch.from_numpy(idx).to(cuda_device)
         d_Vn = torch.full((n,), float("nan"), dtype=torch.float32, device=cuda_device)
         d_delta = torch.full((1,), 123.0, dtype=torch.float32, device=cuda_device)
         d_changed = torch.full((1,), 77, dtype=torch.int32, device=cuda_device)
-        eng.expect_eval_sweeps(d_V.data_ptr(), d_Vn.data_ptr(), d_pol.data_ptr(), 0, 0, n, g.gamma, 1, d_delta.data_ptr())
+        getattr(eng, f"{fold}_eval_sweeps")(d_V.data_ptr(), d_Vn.data_ptr(), d_pol.data_ptr(), 0, 0, n, g.gamma, 1, d_delta.data_ptr())
         torch.cuda.synchronize()
         assert not bool(torch.isnan(d_Vn).any())
         H.assert_bits_equal(d_Vn[d_idx].cpu().numpy(), e_eval, f"64^4 evaluation at {len(idx)} states")
         assert float(d_delta.item()) == float((d_Vn - d_V).abs_().max().item())
         d_Vn.fill_(float("nan"))
         d_p = d_pol.clone()
-        eng.expect_value_sweep(d_V.data_ptr(), d_Vn.data_ptr(), d_p.data_ptr(), 0, 0, n, g.gamma, d_delta.data_ptr(),
-                               d_changed.data_ptr())
+        getattr(eng, f"{fold}_value_sweep")(d_V.data_ptr(), d_Vn.data_ptr(), d_p.data_ptr(), 0, 0, n, g.gamma, d_delta.data_ptr(),
+                                            d_changed.data_ptr())
         torch.cuda.synchronize()
         assert not bool(torch.isnan(d_Vn).any())
         H.assert_bits_equal(d_Vn[d_idx].cpu().numpy(), e_best_q, f"64^4 value sweep at {len(idx)} states")
@@ -617,12 +636,12 @@ def test_large_default_handle_64_4(cuda_device):
         del d_V, d_pol, d_Vn, d_p, Vh, polh
     finally:
         g.eng.close()
-        _report_peak("expectation sweeps, 64^4")
-        print(f"[expect edges] 64^4: {time.perf_counter() - t0:.2f} s")
+        _report_peak(f"{FOLD_NAMES[fold]} sweeps, 64^4")
+        print(f"[{fold} edges] 64^4: {time.perf_counter() - t0:.2f} s")
         _free()
 
 
-def test_large_handle_with_v_byte_offsets_beyond_2_pow_31(cuda_device):
+def test_large_handle_with_v_byte_offsets_beyond_2_pow_31(cuda_device, fold="expect", sample_shift=0):
     """double_pendulum_swingup (160, 161, 159, 162), n = 663 526 080 in [2^29, 2^30): the three kinds on sub-ranges only —
     the last 2^20 states, an unaligned window in the middle, and 2^19 states of the last theta1 plane with small negative
     th1_dot — compared at the states of that third window whose (undisturbed) successor cell lies in the top 1/64 of the
@@ -634,6 +653,7 @@ def test_large_handle_with_v_byte_offsets_beyond_2_pow_31(cuda_device):
     from tests.test_gpu_addr64 import _free, _grid, _points, _report_peak, _seeded_state, _torch
     from tests.test_gpu_offsets32 import SHAPE_V_4D
     torch = _torch()
+    risk = _fold(fold)[2]
     torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
     name = "double_pendulum_swingup"
@@ -654,25 +674,25 @@ def test_large_handle_with_v_byte_offsets_beyond_2_pow_31(cuda_device):
         rng = np.random.default_rng(2029)
         # the top-1/64 sample, picked on the host from that window with the checker's step and cell search
         a, b = windows["below the top"]
-        cand = np.unique(rng.integers(a, b, size=1 << 15, dtype=np.int64))
+        cand = np.unique(rng.integers(a, b, size=(1 << 15) >> sample_shift, dtype=np.int64))
         flat_user, coords = _points(g, cand)
         nxt, _, done = g.chk.step(coords, g.acts[polh[flat_user]])
         cells, _ = g.chk.interp(nxt, lo, hi, gshape, strides)
         top = cand[~done & (cells.astype(np.int64).max(axis=1) >= n - n // 64)]
         print(f"[expect edges] {len(top)} of {len(cand)} candidates have their successor cell in the top 1/64 of the table")
-        assert len(top) >= 10_000 and 4 * int(cells.astype(np.int64).max()) >= 1 << 31
+        assert len(top) >= 10_000 >> sample_shift and 4 * int(cells.astype(np.int64).max()) >= 1 << 31
         d_Vb = torch.full((n,), float(SENTINEL), dtype=torch.float32, device=cuda_device)
         d_p = d_pol.clone()
         d_delta = torch.full((1,), 123.0, dtype=torch.float32, device=cuda_device)
         d_changed = torch.full((1,), 77, dtype=torch.int32, device=cuda_device)
         for where, (a, b) in windows.items():
-            idx = np.unique(rng.integers(a, b, size=1 << 13, dtype=np.int64))
+            idx = np.unique(rng.integers(a, b, size=(1 << 13) >> sample_shift, dtype=np.int64))
             if where == "below the top":
                 idx = np.unique(np.concatenate([idx, top]))
             if b == n:
                 idx = np.unique(np.concatenate([idx, np.arange(n - 256, n, dtype=np.int64)]))
             flat_user, coords = _points(g, idx)
-            e_eval, e_best, e_best_q = _large_twin(g, d, coords, polh[flat_user], Vh)
+            e_eval, e_best, e_best_q = _large_twin(g, d, coords, polh[flat_user], Vh, risk)
             d_idx = torch.from_numpy(idx).to(cuda_device)
             what = f"{g.shape} {where} [{a}, {b})"
 
@@ -681,22 +701,22 @@ def test_large_handle_with_v_byte_offsets_beyond_2_pow_31(cuda_device):
                 assert int(torch.count_nonzero(d_Vb[b:] != float(SENTINEL)).item()) == 0
                 assert torch.equal(d_p[:a], d_pol[:a]) and torch.equal(d_p[b:], d_pol[b:])
 
-            eng.expect_eval_sweeps(d_V.data_ptr(), d_Vb.data_ptr(), d_pol.data_ptr(), 0, a, b, g.gamma, 1, d_delta.data_ptr())
+            getattr(eng, f"{fold}_eval_sweeps")(d_V.data_ptr(), d_Vb.data_ptr(), d_pol.data_ptr(), 0, a, b, g.gamma, 1, d_delta.data_ptr())
             torch.cuda.synchronize()
             H.assert_bits_equal(d_Vb[d_idx].cpu().numpy(), e_eval, f"{what}: evaluation at {len(idx)} states")
             assert float(d_delta.item()) == float((d_Vb[a:b] - d_V[a:b]).abs_().max().item())
             assert int(torch.count_nonzero(d_Vb[a:b] == float(SENTINEL)).item()) == 0
             outside_untouched()
             d_Vb[a:b] = float(SENTINEL)
-            eng.expect_improve_sweep(d_V.data_ptr(), d_p.data_ptr(), 0, a, b, g.gamma, d_changed.data_ptr())
+            getattr(eng, f"{fold}_improve_sweep")(d_V.data_ptr(), d_p.data_ptr(), 0, a, b, g.gamma, d_changed.data_ptr())
             torch.cuda.synchronize()
             assert np.array_equal(d_p[d_idx].cpu().numpy(), e_best), f"{what}: improvement at {len(idx)} states"
             assert int(d_changed.item()) == int(torch.count_nonzero(d_p[a:b] != d_pol[a:b]).item()) > 0
             assert int(torch.count_nonzero(d_Vb != float(SENTINEL)).item()) == 0
             outside_untouched()
             d_p[a:b] = d_pol[a:b]
-            eng.expect_value_sweep(d_V.data_ptr(), d_Vb.data_ptr(), d_p.data_ptr(), 0, a, b, g.gamma, d_delta.data_ptr(),
-                                   d_changed.data_ptr())
+            getattr(eng, f"{fold}_value_sweep")(d_V.data_ptr(), d_Vb.data_ptr(), d_p.data_ptr(), 0, a, b, g.gamma, d_delta.data_ptr(),
+                                                d_changed.data_ptr())
             torch.cuda.synchronize()
             H.assert_bits_equal(d_Vb[d_idx].cpu().numpy(), e_best_q, f"{what}: value sweep at {len(idx)} states")
             assert np.array_equal(d_p[d_idx].cpu().numpy(), e_best)
@@ -708,6 +728,6 @@ def test_large_handle_with_v_byte_offsets_beyond_2_pow_31(cuda_device):
         del d_V, d_pol, d_Vb, d_p, Vh, polh
     finally:
         g.eng.close()
-        _report_peak("expectation sweeps, 32-bit V offsets beyond 2^31")
-        print(f"[expect edges] (160, 161, 159, 162): {time.perf_counter() - t0:.2f} s")
+        _report_peak(f"{FOLD_NAMES[fold]} sweeps, 32-bit V offsets beyond 2^31")
+        print(f"[{fold} edges] (160, 161, 159, 162): {time.perf_counter() - t0:.2f} s")
         _free()
