@@ -59,6 +59,10 @@ SIGNATURES = {
                                                ctypes.c_float, _vp, _vp]),
     "pi_robust_value_sweep": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_float, _vp, _vp, _vp]),
+    "pi_accel_update": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int64, _vp, _vp]),
+    "pi_accel_combine": (ctypes.c_int, [_vp, _vp, _vp, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int64, _vp,
+                                        _vp]),
     "pi_reach_planes": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
     "pi_reach_depth_max": (ctypes.c_int, [_vp]),
     "pi_reach_units": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
@@ -510,6 +514,21 @@ class Engine:
     def robust_value_sweep(self, V, Vnew, policy, term, s_begin, s_end, gamma, d_delta=0, d_changed=0, stream=0):
         _check(lib().pi_robust_value_sweep(self._h, V, Vnew, policy, term, s_begin, s_end, gamma,
                                            d_delta or None, d_changed or None, stream or None), "pi_robust_value_sweep")
+
+    # -- Anderson-accelerated policy evaluation (csrc/pi_accel_kernels.hip; dynamicprogramming_amd/accel.py is the twin) --
+    def accel_update(self, x, g, f_prev, g_prev, dF, dG, m, slot, k_used, first, n, d_dots, stream=0):
+        """One pass after a full batch (pi_accel_update; raw device pointers, asynchronous): the new column of the (m, n)
+        rings dF / dG at `slot`, (f_prev, g_prev) replaced, 2 k_used + 1 float64 dot products into d_dots."""
+        _check(lib().pi_accel_update(self._h, x or None, g or None, f_prev or None, g_prev or None, dF or None, dG or None,
+                                     int(m), int(slot), int(k_used), int(bool(first)), int(n), d_dots or None,
+                                     stream or None), "pi_accel_update")
+
+    def accel_combine(self, g, dG, coeffs, k_used, n, out, stream=0):
+        """out <- g - dG c over the first k_used ring positions (pi_accel_combine; raw device pointers, `coeffs` host
+        floats; `out` may be `g`; asynchronous)."""
+        c = (ctypes.c_double * max(int(k_used), 1))(*[float(v) for v in list(coeffs)[:max(int(k_used), 0)]])
+        _check(lib().pi_accel_combine(self._h, g or None, dG or None, c, int(k_used), int(n), out or None, stream or None),
+               "pi_accel_combine")
 
     def reach_planes(self, term, s_begin, s_end, d_bitmap, stream=0, dim=0):
         _check(lib().pi_reach_planes(self._h, term, s_begin, s_end, int(dim), d_bitmap, stream or None),

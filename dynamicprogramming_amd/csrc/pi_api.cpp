@@ -105,8 +105,9 @@ void free_device_state(pi_handle* h) {
     if (h->module) (void)hipModuleUnload(h->module);
     if (h->module_push) (void)hipModuleUnload(h->module_push);
     if (h->module_expect) (void)hipModuleUnload(h->module_expect);
+    if (h->module_accel) (void)hipModuleUnload(h->module_accel);
     for (void* p : {(void*)h->d_tab, (void*)h->d_slots, (void*)h->d_live, (void*)h->d_eval_list, (void*)h->d_eval_cursor,
-                    h->d_flow, h->d_xcd, (void*)h->d_pairs, (void*)h->d_dist})
+                    h->d_flow, h->d_xcd, (void*)h->d_pairs, (void*)h->d_dist, (void*)h->d_accel_part})
         if (p) (void)hipFree(p);
 }
 

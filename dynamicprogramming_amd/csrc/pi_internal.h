@@ -16,6 +16,7 @@
 //                     and the pi_robust_* sweeps (one host function per pair, parametrised on the kernel)
 //   pi_expect_greedy.cpp  expected-value greedy control on the inference handle: the lookahead over a disturbance set
 //   pi_adversary.cpp  the robust lookahead and the adversary rollout on the inference handle: the worst case over that set
+//   pi_accel.cpp      Anderson-accelerated policy evaluation: the acceleration module, pi_accel_update and pi_accel_combine
 #pragma once
 
 #include "pi_knobs.h"
@@ -187,6 +188,15 @@ struct pi_handle {
     int dist_k = 0;
     float* d_dist = nullptr;
     float dist_a_min = 0.0f, dist_a_max = 0.0f;
+    // fourth module, built by the first pi_accel_update / pi_accel_combine from csrc/pi_accel_kernels.hip alone (pi_accel.cpp:
+    // it depends on neither the grid nor the env, so a later pi_compile keeps it); accel_built: that build went through
+    // (host-only handles: it compiled).  d_accel_part: 17 rows of accel_tiles float64 tile partials (owned, grown on demand)
+    hipModule_t module_accel = nullptr;
+    hipFunction_t f_accel_update = nullptr, f_accel_update_vec = nullptr, f_accel_fold = nullptr, f_accel_combine = nullptr,
+                  f_accel_combine_vec = nullptr;
+    bool accel_built = false;
+    double* d_accel_part = nullptr;
+    int64_t accel_tiles = 0;
     bool has_cache_dir = false;
     bool fast_first = true;              // the unit holds the plugin's common-path instantiation too (pi_compile clears it for a plugin that cannot take that form)
     hipFunction_t f_eval = nullptr, f_eval_live = nullptr, f_policy_list = nullptr, f_scan_slots = nullptr, f_mask_list = nullptr, f_improve = nullptr, f_improve_live = nullptr, f_value = nullptr, f_finalize = nullptr,

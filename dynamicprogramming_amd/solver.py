@@ -32,7 +32,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import _knobs, _native
+from . import _knobs, _native, accel
 from ._native import Info, Option, XcdFailure
 
 try:  # the reference logs through loguru; use it when present, stdlib logging otherwise
@@ -247,6 +247,14 @@ class HipSweepBackend:
                                        s_begin, s_end, gamma, 0 if d_delta is None else d_delta.data_ptr(),
                                        0 if d_changed is None else d_changed.data_ptr(), self._stream())
 
+    # -- Anderson-accelerated policy evaluation (accel.py; csrc/pi_accel_kernels.hip) --
+    def accel_update(self, x, g, f_prev, g_prev, dF, dG, slot, k_used, first, n, d_dots):
+        self.engine.accel_update(x.data_ptr(), g.data_ptr(), f_prev.data_ptr(), g_prev.data_ptr(), dF.data_ptr(), dG.data_ptr(),
+                                 dF.shape[0], slot, k_used, first, n, d_dots.data_ptr(), self._stream())
+
+    def accel_combine(self, g, dG, coeffs, k_used, n, out):
+        self.engine.accel_combine(g.data_ptr(), dG.data_ptr(), coeffs, k_used, n, out.data_ptr(), self._stream())
+
     def close(self):
         # what the XCD-local kernel did, kept past the handle: evaluations run in it, how many of those were run again
         # in the placement-independent kernel, whole runs launched in it
@@ -319,6 +327,7 @@ class _CudaPolicyIterationBase(abc.ABC):
 
         self.disturbances = None          # set_disturbances: the set every sweep takes its expectation over
         self.risk = "expected"            # ... or, with risk="worst", its minimum
+        self.acceleration = None          # set_acceleration: accel.Anderson while policy_evaluation() extrapolates
 
         self._precompute_grid_metadata()
         self._order = self._choose_memory_order()
@@ -758,6 +767,9 @@ class _CudaPolicyIterationBase(abc.ABC):
             raise ValueError(f"risk must be 'expected' or 'worst', not {risk!r}")
         if self._comm is not None:
             raise NotImplementedError("set_disturbances: the expectation sweeps are not sharded; use a single-rank solver")
+        if disturbances is not None and risk == "worst" and getattr(self, "acceleration", None) is not None:
+            raise NotImplementedError("set_disturbances: risk='worst' under set_acceleration — the worst-case evaluation is "
+                                      "not linear; call set_acceleration(None) first")
         self._backend.set_disturbances(disturbances)
         self.disturbances = disturbances
         self.stats["disturbances"] = 0 if disturbances is None else int(disturbances.K)
@@ -768,6 +780,91 @@ class _CudaPolicyIterationBase(abc.ABC):
 
     def _expects(self) -> bool:
         return getattr(self, "disturbances", None) is not None
+
+    # ── accelerated evaluation ──────────────────────────────────────────────────────
+    def set_acceleration(self, settings) -> None:
+        """Anderson-accelerate ``policy_evaluation()`` (extension; accel.py holds the method): with an ``accel.Anderson``
+        installed, every full batch of SYNC_INTERVAL sweeps is followed by one extrapolation over a ring of up to
+        ``settings.window`` past batches (csrc/pi_accel_kernels.hip), guarded by the restart rule of ``accel.evaluate``.
+        The stopping rule is the plain loop's, so the result is a plain sweep's output within gamma theta / (1 - gamma) of
+        the policy's value.  ``None`` restores the plain loop — every path, bit and count as without this call — and frees
+        the history ((2 window + 3) n floats, allocated by the first accelerated evaluation).  Works with the
+        deterministic sweeps and with ``set_disturbances(..., risk="expected")``; the one-launch shortcuts and the
+        pi_eval_begin bracket are not taken while it is on.  ``stats`` gains ``accel_extrapolations`` and
+        ``accel_restarts`` (totals) and ``accel_per_iter`` ((extrapolations, restarts) per evaluation); ``eval_sweeps``
+        and ``sweeps_per_iter`` keep counting real sweeps.  ``value_iteration()`` is not accelerated.  Single rank only."""
+        if settings is not None and not isinstance(settings, accel.Anderson):
+            raise TypeError(f"set_acceleration takes an accel.Anderson or None, not {type(settings).__name__}")
+        if settings is not None and self._comm is not None:
+            raise NotImplementedError("set_acceleration on a sharded solver: the multi-GPU path is frozen; use a single-rank "
+                                      "solver")
+        if settings is not None and self._expects() and getattr(self, "risk", "expected") == "worst":
+            raise NotImplementedError("set_acceleration with risk='worst': the worst-case evaluation is not linear")
+        self.acceleration = settings
+        self._accel_buffers = None
+        if settings is not None:
+            self.stats.setdefault("accel_extrapolations", 0)
+            self.stats.setdefault("accel_restarts", 0)
+            self.stats.setdefault("accel_per_iter", [])
+
+    def _accelerated(self) -> bool:
+        return getattr(self, "acceleration", None) is not None
+
+    def _policy_evaluation_accelerated(self, gamma: float, t0: float) -> float:
+        """The loop of accel.evaluate over the device tensors: the sweeps of `_evaluation_sweeps`, the two kernels of the
+        backend, and ONE host read per batch that brings the residual and the dot products together."""
+        import torch
+        cfg, settings, n = self.config, self.acceleration, self.n_states
+        solver, backend = self, self._backend
+        dev = self.d_value_function.device
+        buf = getattr(self, "_accel_buffers", None)
+        if buf is None or buf["dF"].shape != (settings.window, n):
+            buf = {"x": torch.zeros(n, dtype=torch.float32, device=dev),
+                   "f_prev": torch.zeros(n, dtype=torch.float32, device=dev),
+                   "g_prev": torch.zeros(n, dtype=torch.float32, device=dev),
+                   "dF": torch.zeros((settings.window, n), dtype=torch.float32, device=dev),
+                   "dG": torch.zeros((settings.window, n), dtype=torch.float32, device=dev),
+                   # the 2 * 8 + 1 dot products, then the batch's residual: one device-to-host copy per batch
+                   "dots": torch.zeros(2 * accel.MAX_WINDOW + 2, dtype=torch.float64, device=dev)}
+            self._accel_buffers = buf
+
+        class Ops:
+            def snapshot(self):
+                buf["x"].copy_(solver.d_value_function[:n])
+
+            def sweeps(self, count):
+                solver._evaluation_sweeps(count, gamma)
+
+            def update(self, slot, k_used, first):
+                backend.accel_update(buf["x"], solver.d_value_function, buf["f_prev"], buf["g_prev"], buf["dF"], buf["dG"],
+                                     slot, k_used, first, n, buf["dots"])
+
+            def read(self, count):
+                buf["dots"][-1:].copy_(solver._d_delta)                # float32 -> float64: exact
+                host = buf["dots"].cpu().tolist()                      # the one host sync of the batch
+                return host[-1], host[:count]
+
+            def combine(self, coeffs, k_used):
+                backend.accel_combine(solver.d_value_function, buf["dG"], coeffs, k_used, n, solver.d_value_function)
+
+        def on_check(check, delta):
+            if check % cfg.log_interval == 0:
+                logger.debug(f"  Eval iter {check:5d} | delta = {delta:.4e}")
+
+        delta, sweeps, extrapolations, restarts, converged = accel.evaluate(
+            Ops(), float(cfg.theta), int(cfg.max_eval_iter), settings, SYNC_INTERVAL, on_check)
+        if converged:
+            logger.success(f"  Eval converged at iter {sweeps - 1} | delta = {delta:.2e} "
+                           f"({extrapolations} extrapolations, {restarts} restarts)")
+        else:
+            logger.warning(f"  Eval hit max_eval_iter={cfg.max_eval_iter} | delta = {delta:.2e}")
+        self.stats["eval_sweeps"] += sweeps
+        self.stats["sweeps_per_iter"].append(sweeps)
+        self.stats["accel_extrapolations"] += extrapolations
+        self.stats["accel_restarts"] += restarts
+        self.stats["accel_per_iter"].append((extrapolations, restarts))
+        self.stats["eval_seconds"] += time.perf_counter() - t0
+        return delta
 
     def _set_sweep(self, kind: str):
         """The backend's sweep over the installed set: ``expect_<kind>``, or ``robust_<kind>`` with risk="worst"."""
@@ -805,6 +902,8 @@ class _CudaPolicyIterationBase(abc.ABC):
         gamma = float(np.float32(cfg.gamma))
         delta = float("inf")
         t0 = time.perf_counter()
+        if self._accelerated():
+            return self._policy_evaluation_accelerated(gamma, t0)
         if (self._comm is None and not self._expects() and getattr(self._backend, "resident", False)
                 and cfg.max_eval_iter >= 1):
             delta = self._policy_evaluation_resident(gamma, t0)
@@ -905,7 +1004,8 @@ class _CudaPolicyIterationBase(abc.ABC):
         cls = type(self)
         own = (cls.policy_evaluation is _CudaPolicyIterationBase.policy_evaluation
                and cls.policy_improvement is _CudaPolicyIterationBase.policy_improvement)
-        if (self._comm is not None or not own or self._expects() or not getattr(self._backend, "whole_run", False)
+        if (self._comm is not None or not own or self._expects() or self._accelerated()
+                or not getattr(self._backend, "whole_run", False)
                 or cfg.max_eval_iter < 1 or cfg.max_pi_iter < 1):
             return False
         t0 = time.perf_counter()
@@ -1069,7 +1169,7 @@ class _CudaPolicyIterationBase(abc.ABC):
         self.value_function = np.ascontiguousarray(self._to_user(self.d_value_function[:n].cpu().numpy()))
         self.policy = np.ascontiguousarray(self._to_user(self.d_policy[:n].cpu().numpy()))
         for attr in ["d_terminal_mask", "_term_arg", "d_value_function", "d_new_value_function", "d_policy",
-                     "_d_delta", "_d_changed"]:
+                     "_d_delta", "_d_changed", "_accel_buffers"]:
             if hasattr(self, attr):
                 delattr(self, attr)
         if self._comm is not None:

@@ -289,6 +289,46 @@ int pi_robust_value_sweep(pi_handle* h, const float* V, float* Vnew, int32_t* po
                           int64_t s_end, float gamma, float* d_delta, uint32_t* d_changed, void* stream);
 
 /*
+ * Anderson-accelerated policy evaluation (csrc/pi_accel_kernels.hip, csrc/pi_accel.cpp; no reference counterpart).
+ * Evaluating a fixed policy is a linear fixed-point iteration; once per full batch of sweeps the solver extrapolates over
+ * a ring of up to 8 past batches (dynamicprogramming_amd/accel.py holds the loop, the small solve and the numpy twin of
+ * everything below).  Per full batch: x the iterate before it, g the iterate after it, f = g - x.  The ring holds columns
+ * dF_j = f - f_prev, dG_j = g - g_prev of earlier batches at ring positions j; (m, n) float32 arrays, column j at element
+ * offset j * n (64-bit).  The arithmetic, so that the device and numpy agree bit for bit:
+ *   - f, dF and dG are float32, each ONE float32 subtraction;
+ *   - a dot product accumulates float64 products (double)a * (double)b, a multiply then an add, never contracted;
+ *   - its reduction tree is fixed and independent of the launch: the flat index (memory order) is cut into tiles of
+ *     4 096 consecutive elements, each of 4 chunks of 1 024; thread t of 256 owns elements 4t .. 4t + 3 of every chunk
+ *     and adds their products to 0.0 in ascending index; the 256 thread sums are added wave by wave (4 waves of 64
+ *     lanes), in each wave lanes 0 .. o - 1 adding lanes o .. 2o - 1 for o = 32, 16, 8, 4, 2, 1, and the four wave sums as
+ *     (w0 + w2) + (w1 + w3); elements past n take no part.  The tile sums are folded the same way: thread t of 256 adds
+ *     tile sums t, t + 256, .. to 0.0 in ascending order, then the same tree over the 256 threads.  No atomics;
+ *   - the combine is out[s] = (float)((double)g[s] - S), S = 0.0 + c_0 * (double)dG_0[s] + c_1 * (double)dG_1[s] + ..
+ *     in ascending ring position, each term a multiply then an add, then one subtraction and one rounding.  Where every
+ *     column is zero at s — terminal states, states whose successor is terminal — S is +0.0 and out[s] has g[s]'s bits,
+ *     -0.0 included.
+ *   pi_accel_update     one streaming pass after a full batch.  first != 0 (k_used = 0): (f_prev, g_prev) <- (f, g), no
+ *                       column is written, d_dots[0] = f . f.  Otherwise (1 <= k_used <= m, slot < k_used): column `slot`
+ *                       of dF and dG is overwritten by (f - f_prev, g - g_prev), then (f_prev, g_prev) <- (f, g), and
+ *                       d_dots (device, 2 k_used + 1 float64) receives dF_j . f for j < k_used, then dF_j . dF_slot for
+ *                       j < k_used — the new column's row of the Gram matrix; the caller keeps the older entries —, then
+ *                       f . f.  The columns in use are ring positions 0 .. k_used - 1.  Asynchronous on `stream`.
+ *   pi_accel_combine    out <- g - dG c over the k_used columns at ring positions 0 .. k_used - 1; `coeffs`: k_used HOST
+ *                       float64, passed to the kernel by value.  `out` may be `g`.  Asynchronous on `stream`.
+ * 16-byte accesses when n is a multiple of 4 and every base is 16-byte aligned, float by float otherwise: same results.
+ * Refusals, an error code and pi_last_error, never a launch, in this order: null handle; null pointers; n <= 0; m outside
+ * [1, 8]; k_used outside [0, min(m, 8)]; slot outside [0, m); first with k_used != 0, or a later push with k_used = 0 or
+ * slot >= k_used; coefficients that are not finite; arrays that overlap, `out == g` excepted.  The first call builds the
+ * handle's acceleration module (hipRTC, the sweeps' flags, the code-object cache of pi_compile if it has run): it depends
+ * on neither the grid nor the env, so it is the same code object for every handle and survives a later pi_compile; on
+ * device = -1 handles a call is those checks and that build.
+ */
+int pi_accel_update(pi_handle* h, const float* x, const float* g, float* f_prev, float* g_prev, float* dF, float* dG, int m,
+                    int slot, int k_used, int first, int64_t n, double* d_dots, void* stream);
+int pi_accel_combine(pi_handle* h, const float* g, const float* dG, const double* coeffs, int k_used, int64_t n, float* out,
+                     void* stream);
+
+/*
  * Which planes of V can the states of [s_begin, s_end) read, under ANY action?  Along dimension
  * `dim`: d_bitmap (device, ceil(grid_shape[dim] / 32) uint32 words, zeroed here) receives one bit
  * per index: that of every successor cell and the one above it.  No counterpart in the reference

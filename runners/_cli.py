@@ -55,6 +55,11 @@ the episode (solver.adversary_rollout; csrc/pi_adversary_kernels.hip), under the
 --train-risk worst (extension, default expected) backs up the WORST point of that set instead of its expectation
 (solver.set_disturbances(set, risk="worst"): the max-min policy); the archive then carries a `risk` entry.
 
+--accelerate [M] (extension, off by default; M = 4 when the flag stands alone) Anderson-accelerates the policy evaluations
+of training: once per batch of 25 sweeps the solver extrapolates over a window of M past batches
+(solver.set_acceleration(accel.Anderson(window=M)); csrc/pi_accel_kernels.hip), on every continuation level.  The sweeps,
+extrapolations and restarts of every round are printed.  It does not act on --value-iteration, nor with --train-risk worst.
+
 The ignored group drives the reference's gymnasium / pygame / matplotlib evaluation harness, which is
 outside the scope of this package: training, saving and loading behave as in
 the reference (train when the archive is missing or --retrain is given, otherwise load it), the
@@ -94,15 +99,24 @@ def training_disturbances(env_name: str, action_noise: float = 0.0, state_noise=
 
 def train(env_name: str, bins: int | None = None, save_path: Path | str | None = None,
           value_iteration: bool = False, coarse_bins=(), train_action_noise: float = 0.0, train_state_noise=None,
-          train_noise_points: int = 3, train_risk: str = "expected", **kw):
+          train_noise_points: int = 3, train_risk: str = "expected", accelerate: int | None = None, **kw):
     """Build the env on its reference grid, run policy iteration on the GPU, save the .npz
     (reference: each runner's train(), e.g. pendulum_cuda.py:116-130).  value_iteration=True (extension):
     fused value-iteration sweeps to the same theta instead, at most max_pi_iter slices of max_eval_iter.
     coarse_bins (extension): grid continuation — solve at each of these bins per dimension first, every level
     (the last one at `bins`) continued from the one before it.  train_action_noise / train_state_noise /
     train_noise_points (extension): noise-aware training — every level plans for that noise (training_disturbances);
-    train_risk="worst" (extension): against the worst point of that set instead of its expectation."""
-    from dynamicprogramming_amd import envs
+    train_risk="worst" (extension): against the worst point of that set instead of its expectation.
+    accelerate (extension): the window of the Anderson acceleration of every policy evaluation (None: off)."""
+    from dynamicprogramming_amd import accel, envs
+    settings = None
+    if accelerate is not None and (value_iteration or (train_risk == "worst" and training_disturbances(
+            env_name, train_action_noise, train_state_noise, train_noise_points) is not None)):
+        print(f"[{env_name}] note: --accelerate acts on the policy evaluations of expected-value policy iteration only; "
+              "it had no effect")
+    elif accelerate is not None:
+        settings = accel.Anderson(window=int(accelerate))
+        print(f"[{env_name}] accelerated policy evaluation: one extrapolation per 25 sweeps over a window of {settings.window}")
     noise = training_disturbances(env_name, train_action_noise, train_state_noise, train_noise_points)
     if noise is not None and train_risk == "worst":
         print(f"[{env_name}] worst-case training: max-min backup over {noise.K} disturbance points")
@@ -118,6 +132,8 @@ def train(env_name: str, bins: int | None = None, save_path: Path | str | None =
         coarse = envs.make(env_name, int(level), **kw)
         if noise is not None:
             coarse.set_disturbances(noise, **risk)
+        if settings is not None:
+            coarse.set_acceleration(settings)
         if previous is not None:
             coarse.continue_from(previous)
         coarse.run()
@@ -128,6 +144,8 @@ def train(env_name: str, bins: int | None = None, save_path: Path | str | None =
     solver = envs.make(env_name, bins, **kw)
     if noise is not None:
         solver.set_disturbances(noise, **risk)
+    if settings is not None:
+        solver.set_acceleration(settings)
     t0 = time.perf_counter()
     if previous is not None:
         solver.continue_from(previous)
@@ -152,6 +170,9 @@ def train(env_name: str, bins: int | None = None, save_path: Path | str | None =
         print(f"[{env_name}] {st['pi_iterations']} PI iterations, {st['eval_sweeps']} eval sweeps, "
               f"{st['improve_sweeps']} improve sweeps in {dt:.2f} s  ({backups / dt:.3e} backups/s), "
               f"stable={st.get('stable')}")
+        if settings is not None:
+            for k, (sweeps, (extrapolations, restarts)) in enumerate(zip(st["sweeps_per_iter"], st["accel_per_iter"])):
+                print(f"[{env_name}]   round {k + 1}: {sweeps} sweeps, {extrapolations} extrapolations, {restarts} restarts")
     if save_path is not None:
         solver.save(save_path)
     return solver
@@ -212,6 +233,9 @@ def build_parser(env_name: str, default_save: str) -> argparse.ArgumentParser:
     p.add_argument("--train-risk", choices=("expected", "worst"), default="expected",
                    help="(extension) what training backs up over the training noise's points: their expectation, or the "
                         "worst of them (max-min: the policy that is best against the worst disturbance)")
+    p.add_argument("--accelerate", type=int, nargs="?", const=4, default=None, metavar="M", choices=range(1, 9),
+                   help="(extension) Anderson-accelerate the policy evaluations of training: one extrapolation per 25 sweeps "
+                        "over a window of M past batches (1 .. 8; 4 when M is left out)")
     return p
 
 
@@ -327,7 +351,8 @@ def main(env_name: str, default_save: str, argv=None):
         print("[*] Training new policy...")
         pi = train(env_name, args.bins, path, value_iteration=args.value_iteration, coarse_bins=args.coarse_bins,
                    train_action_noise=args.train_action_noise, train_state_noise=args.train_state_noise,
-                   train_noise_points=args.train_noise_points, train_risk=args.train_risk, **kw)
+                   train_noise_points=args.train_noise_points, train_risk=args.train_risk, accelerate=args.accelerate,
+                   **kw)
     lookahead_set = None
     if args.rollout and args.controller == "expected" and getattr(pi, "disturbances", None) is None:
         lookahead_set = training_disturbances(env_name, args.action_noise, args.state_noise, args.train_noise_points)
